@@ -13,6 +13,12 @@ hg38 is not available offline: the genome is a seeded synthetic one (size --geno
 JSON line says so.  N>1: one process per GPU (torchrun), chunks are the shard unit (every chunk is
 independent in the reference, so the output equals the single-GPU run); NCCL(=RCCL) carries only the
 barrier and the final reduction of counts/timings.
+
+A plain run sets up, warms up, times --steps chunks and prints the headline line.  --full adds what takes
+runs of its own: the stand-alone chunk (per-launch times, the reference's FM-block count), the CPU baseline
+and the sub-records (the other genome profile, 1 kb reads, the command line end to end).  --dump-outputs DIR
+writes the SAM of the last timed chunk as arrays (sam_arrays) so that two builds can be compared output for
+output; the inputs are seeded, identical from run to run for the same arguments.
 """
 import argparse
 import ctypes as C
@@ -22,6 +28,7 @@ import subprocess
 import sys
 import time
 
+T_START = time.time()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -46,6 +53,9 @@ def main():
                     help="hg38-like (the headline since round 5: BASELINE's metric is quoted vs hg38): i.i.d. bases + interspersed repeat families with up to a million copies, ~43 %% repeats (csrc/host/sim.c); clean: i.i.d. bases + 5 %% planted repeats (the headline of rounds 1-4, now the sub-record clean_genome)")
     ap.add_argument("--no-cli", action="store_true", help="skip the cli_end_to_end sub-record (FASTQ text in -> SAM text out through biscuit_align, tools/cli_e2e.py)")
     ap.add_argument("--sub", action="store_true", help="(internal) this run is a sub-record of another: no sub-records of its own")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: the stand-alone chunk after the timed region, the CPU baseline and the "
+                    "sub-records (each still switched off by its --no-* option); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the SAM of the last timed chunk as DIR/<name>.npy (float64; sam_arrays)")
     args = ap.parse_args()
     genome_given = args.genome_mbp is not None or "BSX_BENCH_GENOME_MBP" in os.environ
     if args.genome_mbp is None:
@@ -60,17 +70,11 @@ def main():
     share_gpu = world > 1 and os.environ.get("BSX_BENCH_SHARE_GPU") == "1"
     if share_gpu:
         local_rank = 0
-    import torch
-    dist = None
-    if world > 1:
-        import torch.distributed as dist_
-        dist = dist_
-        torch.cuda.set_device(local_rank)
-        if share_gpu:
-            dist.init_process_group("gloo")
-        else:
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-
+    # the library binds to the HIP runtime torch brings (its libamdhip64.so.7 is torch's copy once that is loaded): that runtime is
+    # loaded first, by its path, so that torch itself can be imported while the genome is generated
+    torch_first = not load_torch_hip()
+    if torch_first:
+        import torch
     from biscuit_amd import _lib as B
     from biscuit_amd.api import Index, Device, default_opt
     L = B.lib()   # raises if libbiscuit_amd.so has not been built
@@ -83,16 +87,24 @@ def main():
     os.environ["BSX_HOST_THREADS"] = str(host_threads)
     n_bases = int(args.genome_mbp * 1e6)
 
+    dist = None
+
     def barrier():
         if dist is not None:
             dist.barrier()
 
     # genome + both FM indices: generated (seeded) and indexed on this rank's own GPU (csrc/hip/k_index.hip; an hg38-sized
-    # genome takes ~5 s to generate and ~13 s to index), resident in HBM from then on.  Rank 0 of a single-GPU run also
-    # takes the file-format arrays back to the host: the CPU baseline needs them.
+    # genome takes ~5 s to generate and ~13 s to index), resident in HBM from then on.  Rank 0 of a single-GPU run with --full also
+    # takes the file-format arrays back to the host: the CPU baseline needs them.  The set-up overlaps what does not depend on
+    # each other (the ctypes calls run without the GIL): the synthetic genome is generated while torch is imported and the device
+    # opened, and the chunks' reads (which read only the genome) are simulated while the device builds the index.
+    from concurrent.futures import ThreadPoolExecutor
+    # three workers: the genome, then the index build beside two threads simulating reads (more of them slow the index build down,
+    # and two finish the reads well within it)
+    setup_pool = ThreadPoolExecutor(max_workers=3)
     t0 = time.time()
-    dev = Device(local_rank)
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    start_up = {"library": round(t0 - T_START, 2)}   # seconds since the start of the process at which each part of the set-up ended
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     # "vs hg38 index (pre-built files at $BISCUIT_HG38_INDEX; if absent, a synthetic 3.1 Gbp genome ...)".  The real
     # genome when the box has it -- $BISCUIT_HG38_INDEX = the <base> of a `biscuit index` file set (<base>.{par,dau}.{bwt,sa} +
     # <base>.bis.{ann,amb,pac}), or $BISCUIT_HG38_FA = the FASTA, indexed on the GPU at start-up -- and only for the headline record; the
@@ -101,19 +113,38 @@ def main():
     if args.genome_profile == "hg38-like" and not args.single_end and not genome_given and not args.sub:
         real_genome = real_genome_source()
     if real_genome and real_genome[0] == "index":
-        idx = Index(real_genome[1])
-        dev.upload_index(idx)
+        idx_fut = setup_pool.submit(Index, real_genome[1])
     elif real_genome:
-        idx = Index.from_fasta(real_genome[1])
-        dev.build_index(idx, fill_host=want_cpu)
+        idx_fut = setup_pool.submit(Index.from_fasta, real_genome[1])
     else:
-        idx = Index.synthetic(n_bases, seed=2024, n_contigs=24 if n_bases >= 1_000_000_000 else 8, profile=1 if args.genome_profile == "hg38-like" else 0)
-        dev.build_index(idx, fill_host=want_cpu)
+        idx_fut = setup_pool.submit(Index.synthetic, n_bases, seed=2024, n_contigs=24 if n_bases >= 1_000_000_000 else 8,
+                                    profile=1 if args.genome_profile == "hg38-like" else 0)
+    if not torch_first:
+        import torch
+    if world > 1:
+        import torch.distributed as dist_
+        dist = dist_
+        torch.cuda.set_device(local_rank)
+        if share_gpu:
+            dist.init_process_group("gloo")
+        else:
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+    start_up["torch"] = round(time.time() - T_START, 2)
+    dev = Device(local_rank)
+    start_up["device_open"] = round(time.time() - T_START, 2)
+    # and while the genome is generated, what the set-up of the timed region imports and initialises in any case: the record gather's
+    # module and torch's own context on the device
+    from biscuit_amd.gather import ChunkGather
+    torch.cuda.synchronize()
+    idx = idx_fut.result()
+    start_up["genome"] = round(time.time() - T_START, 2)
+    if real_genome and real_genome[0] == "index":
+        dev_fut = setup_pool.submit(dev.upload_index, idx)
+    else:
+        dev_fut = setup_pool.submit(dev.build_index, idx, fill_host=want_cpu)
     if real_genome:
         n_bases = int(idx.l_pac)
         args.genome_mbp = n_bases / 1e6
-    t_build = time.time() - t0
-    barrier()
 
     opt = default_opt()
     opt.n_threads = threads
@@ -134,14 +165,20 @@ def main():
         B.check(L.bsx_sim_pairs(idx.h, n_pairs, args.read_len, seed, frag[0], frag[1], 0.005, 0.0, C.byref(p)), "sim_pairs")
         return p
 
-    C.c_int.in_dll(L, "bsx_verbose").value = 1   # silence per-chunk messages inside the timed region
-
     # a bounded set of distinct chunks, reused round-robin (a chunk is only pushed again long after it has completed and its
     # SAM text has been dropped): keeps the host memory of a rank at a few GB whatever --steps is
     class Ring(list):
         def __getitem__(self, i):
             return list.__getitem__(self, i % len(self))
-    chunks = Ring(gen(1000 * (rank + 1) + s, pairs_per_step) for s in range(min(args.warmup + args.steps, 8)))
+    chunk_futs = [setup_pool.submit(gen, 1000 * (rank + 1) + s, pairs_per_step) for s in range(min(args.warmup + args.steps, 8))]
+    dev_fut.result()
+    t_build = time.time() - t0
+    start_up["index"] = round(time.time() - T_START, 2)
+    chunks = Ring(f.result() for f in chunk_futs)
+    start_up["reads"] = round(time.time() - T_START, 2)
+    setup_pool.shutdown()
+    C.c_int.in_dll(L, "bsx_verbose").value = 1   # silence per-chunk messages inside the timed region
+    barrier()
     # chunks go through the two-deep pipeline of include/bsx.h (front half of chunk k+1 on the device while the host
     # finishes chunk k); --no-pipeline runs them one at a time through bsx_process_seqs instead
     L.bsx_stream_open.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
@@ -164,6 +201,7 @@ def main():
         n_processed += n_reads
     if not args.no_pipeline:
         B.check(L.bsx_stream_flush(stream), "stream_flush(warmup)")
+    start_up["warm_up"] = round(time.time() - T_START, 2)
     L.bsx_sim_reset_reads.argtypes = [C.c_void_p, C.c_int64]
     for s_ in range(args.warmup):
         L.bsx_sim_reset_reads(chunks[s_], n_reads)   # drop the warm-up chunks' SAM text
@@ -176,7 +214,6 @@ def main():
     phase_tot = {}
     # the gather of the records to rank 0 (below) is part of the timed region; its connections are made here, as part of the warm-up
     import numpy as np
-    from biscuit_amd.gather import ChunkGather
     gathered = [0, 0]
 
     def sink(k, buf):
@@ -190,6 +227,7 @@ def main():
     import resource
     ru0 = resource.getrusage(resource.RUSAGE_SELF)
     t0 = time.time()
+    start_up["timed_region_start"] = round(t0 - T_START, 2)
     sam_bytes_box = [0]
     L.bsx_sim_reset_reads.argtypes = [C.c_void_p, C.c_int64]
 
@@ -201,6 +239,7 @@ def main():
     retire_q = queue.Queue()
     retire_s = [0.0]
     retired = set()
+    last_text = [None]   # the SAM text of the last timed chunk, for --dump-outputs (the consumer makes it in any case)
     # the per-chunk alignment records (SAM text) of every rank stream to rank 0 while the following chunks are
     # aligned (biscuit_amd/gather.py: sizes, then exactly the payload, rank -> rank 0 over RCCL); rank 0 takes them in chunk
     # order and drops them (a real run writes them).  Chunk s of rank r is global chunk s * world + r.  All of it is inside
@@ -219,6 +258,8 @@ def main():
             text = np.empty(nb, dtype=np.uint8)
             L.bsx_hook_chunk_sam(chunks[k], n_reads, text.ctypes.data_as(C.c_void_p), nb)
             sam_bytes_box[0] += nb
+            if k == args.warmup + args.steps - 1 and args.dump_outputs:
+                last_text[0] = text
             L.bsx_sim_reset_reads(chunks[k], n_reads)
             retire_s[0] += time.time() - tr
             retired.add(k)
@@ -306,7 +347,10 @@ def main():
     region_launch_ms = None
     ref_blocks_per_read, ref_seed_ms = None, None
     tab_touch = [ctr[0] + ctr[1], dev.seed_table()[0], dev.seed_table()[1]]   # FM blocks and table entries the seeding kernel read in the timed region
-    if not args.no_pipeline:
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, sam_arrays(last_text[0], pairs_per_step))
+    last_text[0] = None
+    if args.full and not args.no_pipeline:
         for k in range(8):
             dev.kernel_time(k, reset=True)
         dev.seed_passes(reset=True)
@@ -489,7 +533,7 @@ def main():
                                              "rate": round(b_read * tot_reads / tmax / 1e9, 2), "unit": "GB/s", "frac_of_hbm_peak": round(b_read * tot_reads / tmax / 1e9 / (PEAK_HBM * world), 5),
                                              "meaning": "SURVEY 8(d)'s B(read), the bytes the reference algorithm touches for these reads, over this run's wall time: the rate at which the path gets through the reference's memory work -- not bytes this implementation moves (the table of k-mer intervals and the dense suffix-array sample replace most of them)"}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(L, B, idx, dev, opt, args, ncores)
 
     repeats = ("with hg38-like repeat content (SINE/LINE/LTR-like families of up to a million copies, satellite arrays: ~43 % repeats)"
@@ -529,18 +573,22 @@ def main():
             "host_cores_busy_per_gpu": round(((ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)) / max(1e-9, dt), 2),
             "sam_bytes_per_read": round(sam_bytes / float(n_reads * args.steps), 1),
             "genome_and_index_build_s": round(t_build, 1), "device": dev.name,
+            # seconds since the start of the process at which each part of the set-up ended and the timed region began (the parts
+            # overlap: the genome with torch's import and the device's opening, the reads with the index)
+            "start_up_s": start_up,
             "hbm_bytes_free_of_total_after_the_run": list(hbm_free),
         }
     if not args.no_pipeline:
         L.bsx_stream_close(stream)
-    for c in list.__iter__(chunks):
-        L.bsx_sim_free_reads(c, n_reads)
+    if args.full:   # (a plain run ends the process right after its line: freeing millions of reads one by one first would take a second)
+        for c in list.__iter__(chunks):
+            L.bsx_sim_free_reads(c, n_reads)
     if rank == 0:
         # Sub-records, each in a process of its own after this one has given the device back (the headline line must not depend on them):
         #   clean_genome     the same measurement, shorter, on the genome of rounds 1-4's headline (i.i.d. bases + 5 % planted repeats)
         #   long_reads       BASELINE configs[4] shape (1 kb single-end reads), with its own roofline and CPU baseline
         #   cli_end_to_end   SURVEY 8(d)'s second number: FASTQ text in -> SAM text out through the command line (tools/cli_e2e.py)
-        if world == 1 and not args.sub and not args.no_pipeline:
+        if args.full and world == 1 and not args.sub and not args.no_pipeline:
             dev.close()
             idx.close()
             keep = ("value", "unit", "steps", "warmup", "ms_per_step", "roofline", "roofline_seeding", "roofline_whole_path", "cpu_baseline", "kernel_ms_per_step",
@@ -548,7 +596,7 @@ def main():
                     "push_loop_s_per_step", "host_cores_busy_per_gpu")
 
             def sub_run(key, extra_args, timeout):
-                cmd = [sys.executable, os.path.abspath(__file__), "--sub", "--genome-mbp", str(synth_mbp), "--threads", str(threads)] + extra_args
+                cmd = [sys.executable, os.path.abspath(__file__), "--sub", "--full", "--genome-mbp", str(synth_mbp), "--threads", str(threads)] + extra_args
                 if args.no_cpu_baseline:
                     cmd.append("--no-cpu-baseline")
                 try:
@@ -578,8 +626,23 @@ def main():
             if isinstance(out.get(key), dict) and out[key].get("value") is not None:
                 out[top] = out[key]["value"]
         print(json.dumps(out))
+        sys.stdout.flush()
+        sys.stderr.write("[bench] result line printed %.1f s after the start\n" % (time.time() - T_START))
     if dist is not None:
         dist.destroy_process_group()
+
+
+def load_torch_hip():
+    """Load the HIP runtime torch ships (torch/lib/libamdhip64.so) by its path, before the library and torch; False when there is
+    none (torch is then imported first, which loads it)."""
+    import importlib.util
+    spec = importlib.util.find_spec("torch")
+    for d in (spec.submodule_search_locations or []) if spec else []:
+        p = os.path.join(d, "lib", "libamdhip64.so")
+        if os.path.exists(p):
+            C.CDLL(p, mode=C.RTLD_GLOBAL)
+            return True
+    return False
 
 
 def real_genome_source():
@@ -597,6 +660,67 @@ def real_genome_source():
             return ("fasta", fa, "FASTA %s, indexed on the GPU at start-up" % fa)
         sys.stderr.write("[bench] $BISCUIT_HG38_FA=%s does not exist; falling back\n" % fa)
     return None
+
+
+SAM_SAMPLE_PAIRS = 65536
+SAM_FIELDS = ("pair", "flag", "rname_crc32", "pos", "mapq", "cigar_crc32", "rnext_crc32", "pnext", "tlen", "tag_AS", "tag_XS", "tag_NM", "line_crc32")
+
+
+def sam_arrays(text, n_pairs, sample=SAM_SAMPLE_PAIRS, seed=7):
+    """What the timed path hands its caller for one chunk -- SAM text, a record per line -- as float64 arrays, within tens of MB at any
+    chunk size: sam_summary = [lines, bytes, CRC-32 of the whole text]; sam_<field> over every line of a fixed, seeded sample of the
+    chunk's read pairs (by QNAME, so that it picks the same reads whatever the output), in output order.  Strings are given as their
+    CRC-32 (RNAME, CIGAR, RNEXT with "=" resolved; a "*" is -1), absent tags as -1, line_crc32 covers the whole line."""
+    import zlib
+    import numpy as np
+    buf = bytes(memoryview(text)) if text is not None else b""
+    arr = np.frombuffer(buf, dtype=np.uint8)
+    ends = np.flatnonzero(arr == 10)
+    if len(buf) and buf[-1:] != b"\n":
+        ends = np.append(ends, len(buf))
+    starts = np.concatenate(([0], ends[:-1] + 1)).astype(np.int64)
+    keep = (ends > starts) & (arr[np.minimum(starts, max(0, len(buf) - 1))] != ord("@")) if len(buf) else np.zeros(0, dtype=bool)
+    starts, ends = starts[keep], ends[keep]
+    pick = np.zeros(max(1, n_pairs), dtype=bool)
+    pick[np.random.default_rng(seed).choice(n_pairs, min(sample, n_pairs), replace=False) if n_pairs > 0 else []] = True
+    # the simulated reads are named p%09d: their pair numbers are read off all lines at once; other names go one by one
+    pair = np.full(len(starts), -1, dtype=np.int64)
+    fixed = (ends - starts > 11)
+    fixed[fixed] = (arr[starts[fixed]] == ord("p")) & (arr[starts[fixed] + 10] == 9)
+    dig = arr[starts[fixed, None] + 1 + np.arange(9)].astype(np.int64) - ord("0")
+    ok = ((dig >= 0) & (dig <= 9)).all(axis=1)
+    pair[np.flatnonzero(fixed)[ok]] = dig[ok] @ (10 ** np.arange(8, -1, -1, dtype=np.int64))
+    for i in np.flatnonzero(pair < 0):
+        q = buf[starts[i]:buf.index(b"\t", starts[i], ends[i]) if b"\t" in buf[starts[i]:ends[i]] else ends[i]]
+        try:
+            pair[i] = int(q.lstrip(b"p"))
+        except ValueError:
+            pair[i] = zlib.crc32(q) % max(1, n_pairs)
+    sel = np.flatnonzero((pair >= 0) & (pair < n_pairs))
+    sel = sel[pick[pair[sel]]]
+
+    def crc(s):
+        return -1.0 if s == b"*" else float(zlib.crc32(s))
+    rows = []
+    for p, b0, b1 in zip(pair[sel].tolist(), starts[sel].tolist(), ends[sel].tolist()):
+        ln = buf[b0:b1]
+        f = ln.split(b"\t")
+        tags = {t[:2]: t[5:] for t in f[11:] if t[2:5] == b":i:"}
+        rnext = f[2] if f[6] == b"=" else f[6]
+        rows.append((p, int(f[1]), crc(f[2]), int(f[3]), int(f[4]), crc(f[5]), crc(rnext), int(f[7]), int(f[8]),
+                     int(tags.get(b"AS", -1)), int(tags.get(b"XS", -1)), int(tags.get(b"NM", -1)), zlib.crc32(ln)))
+    cols = np.array(rows, dtype=np.float64).reshape(-1, len(SAM_FIELDS))
+    out = {"sam_summary": np.array([len(starts), len(buf), zlib.crc32(buf)], dtype=np.float64)}
+    for i, name in enumerate(SAM_FIELDS):
+        out["sam_" + name] = np.ascontiguousarray(cols[:, i])
+    return out
+
+
+def write_outputs(d, arrays):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def effective_cores():

@@ -31,7 +31,7 @@ def test_two_rank_bench_line():
 def test_single_rank_bench_line_small():
     """the default command's line at a small genome: the contract keys, the rooflines' byte definitions, and the CPU baseline's sample
     through both paths with identical SAM (bench.py, cpu_baseline.sam_identical)"""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--genome-mbp", "8", "--cpu-sample-pairs", "3000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--genome-mbp", "8", "--cpu-sample-pairs", "3000",
            "--no-long-reads", "--no-cli", "--no-hard-genome"]
     p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
@@ -59,7 +59,7 @@ def test_real_genome_hook(tmp_path):
     d = str(tmp_path)
     simdata.write_genome(d + "/g.fa", simdata.make_genome(3000000, seed=31, n_contigs=3))
     Index.build(d + "/g.fa", d + "/g").close()
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--threads", "1", "--cpu-sample-pairs", "1000",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--threads", "1", "--cpu-sample-pairs", "1000",
             "--no-long-reads", "--no-cli", "--no-hard-genome"]
     env = {k: v for k, v in os.environ.items() if k not in ("BISCUIT_HG38_INDEX", "BISCUIT_HG38_FA", "BSX_BENCH_GENOME_MBP")}
     for how, e in (("index", {"BISCUIT_HG38_INDEX": d + "/g"}), ("fasta", {"BISCUIT_HG38_FA": d + "/g.fa"})):
@@ -76,3 +76,33 @@ def test_real_genome_hook(tmp_path):
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     r = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
     assert r["data"] == "synthetic" and "SYNTHETIC 8 Mbp" in r["config"]["workload"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run times exactly --steps chunks and leaves the figures that take runs of their own to --full; --dump-outputs writes
+    the last timed chunk's SAM as float arrays, the same for a plain and a --full run of the same arguments (seeded inputs)"""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--genome-mbp", "8"]
+    lines = {}
+    for how, extra in (("plain", []), ("full", ["--full", "--cpu-sample-pairs", "1000", "--no-long-reads", "--no-cli", "--no-hard-genome"])):
+        p = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / how)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines[how] = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
+    d = lines["plain"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["reads_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    assert d["cpu_baseline"] is None and d["kernel_ms_per_step_standalone"] is None and "clean_genome" not in d
+    assert lines["full"]["cpu_baseline"]["sam_identical"] is True and lines["full"]["kernel_ms_per_step_standalone"] is not None
+    import numpy as np
+    names = sorted(os.listdir(str(tmp_path / "plain")))
+    assert names == sorted(os.listdir(str(tmp_path / "full"))) and "sam_summary.npy" in names and "sam_line_crc32.npy" in names
+    total = 0
+    for n in names:
+        a, b = np.load(str(tmp_path / "plain" / n)), np.load(str(tmp_path / "full" / n))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    s = np.load(str(tmp_path / "plain" / "sam_summary.npy"))
+    assert s[0] >= d["config"]["reads_per_step_per_gpu"] and s[1] > 0   # a line per read at least
+    assert len(np.load(str(tmp_path / "plain" / "sam_pair.npy"))) > 1000

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 GP=${GENOME_PROFILE:-hg38-like}
-BENCH="python $ROOT/bench.py --genome-profile $GP --genome-mbp ${GENOME_MBP:-3100} --steps ${STEPS:-12} --warmup 1 --no-cpu-baseline --sub"
+BENCH="python $ROOT/bench.py --genome-profile $GP --genome-mbp ${GENOME_MBP:-3100} --steps ${STEPS:-12} --warmup 1 --no-cpu-baseline --sub --full"
 cd /tmp
 $BENCH > "$OUT/bench_untraced.json" 2> "$OUT/bench_untraced.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o bench -- $BENCH > "$OUT/bench_under_trace.json" 2> "$OUT/trace.err"
