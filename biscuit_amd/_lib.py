@@ -88,7 +88,16 @@ class GlbTag(C.Structure):
 
 class Backend(C.Structure):  # bsx_backend_t (csrc/host/bsx_core.h)
     _fields_ = [("ctx", C.c_void_p), ("name", C.c_char_p)] + [(n, C.c_void_p) for n in
-                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p)]
+                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p)]
+
+
+class GlbCtx(C.Structure):  # bsx_glb_ctx_t: [strand hypothesis][A, C, G, T, N context][retained, converted]
+    _fields_ = [("n", C.c_uint16 * 20)]
+
+
+class BsconvConf(C.Structure):  # bsx_bsconv_conf_t
+    _fields_ = [(n, C.c_int) for n in ("annotate", "filter_u", "show_filtered", "max_cph", "max_cpa", "max_cpc", "max_cpt", "max_cpy")] + \
+               [("max_cph_frac", C.c_float), ("max_cpy_frac", C.c_float)]
 
 
 class PhaseStats(C.Structure):

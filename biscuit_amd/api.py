@@ -208,6 +208,25 @@ class Device(Batches):
             _libc_free(md)
         return res, pool, tags, out
 
+    def global_tags_ctx(self, jobs, pool_len):
+        """bsx_global_batch_tags_ctx: the above plus, per job, the retention / conversion counts by cytosine context of both bisulfite-strand
+        hypotheses -> (res, pool, tags, [md], ctx[n, 2, 5, 2] uint16: [strand][A, C, G, T, N context][retained, converted])"""
+        jobs = np.ascontiguousarray(jobs, dtype=GLB_DT)
+        n = len(jobs)
+        res = np.zeros(n, dtype=GLBRES_DT)
+        pool = np.zeros(max(1, pool_len), dtype=np.uint32)
+        tags = np.zeros(n, dtype=np.dtype(B.GlbTag))
+        ctx = np.zeros((n, 2, 5, 2), dtype=np.uint16)
+        md = C.c_void_p()
+        cap = C.c_int64(0)
+        f = B.lib().bsx_global_batch_tags_ctx
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
+        B.check(f(self.h, n, _p(jobs), _p(res), _p(pool), pool.size, _p(tags), C.byref(md), C.byref(cap), _p(ctx)), "bsx_global_batch_tags_ctx")
+        out = [None if tags[k]["l_md"] < 0 else C.string_at(md.value + int(tags[k]["md_off"]), int(tags[k]["l_md"]) + 1) for k in range(n)]
+        if md.value:
+            _libc_free(md)
+        return res, pool, tags, out, ctx
+
     def counters(self, reset=False):
         c = (C.c_uint64 * 4)()
         B.check(B.lib().bsx_device_counters(self.h, c, int(reset)), "bsx_device_counters")

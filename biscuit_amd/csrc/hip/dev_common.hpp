@@ -40,6 +40,9 @@ struct DevIndex {
 	const uint8_t *ctg_alt;    // n_seqs: is_alt
 	int32_t n_seqs;
 	DevSeedTab tab;
+	// the N holes of the forward strand (.bis.amb: bntamb1_t offset and offset + len), sorted, disjoint; read by k_global_ctx only
+	const int64_t *hole_off, *hole_end;
+	int32_t n_holes, pad2_;
 };
 
 // the options the region kernel reads (mem_opt_t fields of the same name)

@@ -11,6 +11,9 @@
 // (lib/aln/bwa.c:342-418): NM, the MD string, BISCUIT's conversion (ZC) and retention (ZR) counts.  The read is already in
 // LDS; the target bases are staged there by the wave when they fit; lane 0 walks twice (lengths, then bytes: the strings
 // are packed, each job taking exactly its length from one cursor).
+// k_global<NC, true> is the same kernel with one more pass over the CIGAR: retention / conversion counts by cytosine context for both
+// bisulfite-strand hypotheses (what `biscuit bsconv` computes from the BAM; bsx_glb_ctx_t), a lane per column over forward bases staged
+// with both neighbours of the window, LDS counters; targets beyond the LDS stage take one lane, as for MD.
 #include <hip/hip_runtime.h>
 #include "dev_common.hpp"
 #include "wave.hpp"
@@ -19,11 +22,35 @@
 #define G_MINUS_INF (-0x40000000)
 #define G_INACTIVE  (-0x7f000000)
 
-template <int NC>
+// is forward coordinate f inside one of the reference's N holes?  h0: the first hole that can matter (the ones before it end at or before the window)
+__device__ __forceinline__ bool ctx_in_hole(const DevIndex &ix, int h0, int64_t f)
+{
+	for (int h = h0; h < ix.n_holes && ix.hole_off[h] <= f; ++h) if (f < ix.hole_end[h]) return true;
+	return false;
+}
+
+// how many of the n sorted values a[] are <= key, found by the whole wave: 64 probes a step (two dependent loads for 4096 entries where a
+// binary search by one lane makes twelve); every lane returns the same number
+__device__ __forceinline__ int wave_count_le(const int64_t *a, int n, int64_t key, int lane)
+{
+	int lo = 0, hi = n;   // the answer lies in [lo, hi]
+	while (hi > lo) {
+		const int step = (hi - lo + 63) >> 6, idx = lo + lane * step;
+		const bool le = idx < hi && a[idx] <= key;
+		const int c = __popcll(__ballot(le));   // a[] is sorted: the lanes that say yes are the first c
+		if (c == 0) hi = lo;
+		else { const int nhi = lo + c * step; lo = lo + (c - 1) * step + 1; hi = nhi < hi ? nhi : hi; }
+	}
+	return lo;
+}
+
+// CTX: the instantiation that also counts retention / conversion by context for both strand hypotheses (bsx_glb_ctx_t, include/bsx.h);
+// a template parameter, so that the plain kernels keep their code and registers
+template <int NC, bool CTX = false>
 __global__ void __launch_bounds__(256)
 k_global(DevIndex ix, DevScoring sc, const uint8_t *reads, const bsx_glb_job_t *jobs, const int *order, long long n,
          bsx_glb_res_t *res, uint32_t *pool, uint8_t *zscratch, size_t zstride, int qcap,
-         bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, int tcap, int32_t *hbm_rows)
+         bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, int tcap, int32_t *hbm_rows, bsx_glb_ctx_t *ctxo)
 {
 	extern __shared__ int32_t lds[];
 	const int lane = wave_lane();
@@ -296,6 +323,91 @@ k_global(DevIndex ix, DevScoring sc, const uint8_t *reads, const bsx_glb_job_t *
 			#undef MD_BASE
 			#undef MD_DIGITS
 		}
+		if constexpr (CTX) if (tags && ctxo && J.want_cigar) {
+			// Retention / conversion by context (src/bsconv.c:63-109), in forward-genome terms.  The view's columns map to forward coordinates
+			// f0 + k * dirf; on a complemented view (tpos >= l_pac) both sequences are complemented back.  One search by the wave says whether
+			// the window and its two neighbours touch a contig end or an N hole: almost never, and then no base needs a second look.
+			const bool comp = J.tpos >= ix.l_pac;
+			const int dirf = comp ? -(int)J.tdir : (int)J.tdir;
+			const int64_t f0 = comp ? (ix.l_pac << 1) - 1 - J.tpos : J.tpos;
+			const int64_t wlo = dirf > 0 ? f0 - 1 : f0 - tlen, whi = dirf > 0 ? f0 + tlen : f0 + 1;
+			int ci = wave_count_le(ix.ctg_off, ix.n_seqs + 1, f0, lane) - 1;
+			ci = ci < 0 ? 0 : ci > ix.n_seqs - 1 ? ix.n_seqs - 1 : ci;
+			const int64_t cb = ix.ctg_off[ci], ce = ix.ctg_off[ci + 1];
+			const int h0 = wave_count_le(ix.hole_end, ix.n_holes, wlo, lane);   // the holes before this one end at or before wlo
+			const bool holes = h0 < ix.n_holes && ix.hole_off[h0] <= whi;
+			const bool special = holes || wlo < cb || whi >= ce;
+			// forward base at forward coordinate f, 4 = outside the contig or in a hole
+			#define CTX_IS_N(f) ((f) < cb || (f) >= ce || (holes && ctx_in_hole(ix, h0, (f))))
+			const bool ctx_staged = n_cigar > 0 && tlen <= tcap && !hbm_rows && 80 + tlen + 2 <= 8 * (qcap + 2);
+			WAVE_SYNC();   // the MD bytes in the rows' LDS have been copied out
+			if (ctx_staged) {
+				int32_t *cnt = lds + wave * stride;                        // 20 counters, then the tlen + 2 forward bases
+				uint8_t *fx = reinterpret_cast<uint8_t*>(cnt + 20);
+				if (lane < 20) cnt[lane] = 0;
+				for (int k = lane; k < tlen + 2; k += 64) {
+					const int i = k - 1;
+					const int64_t f = f0 + (int64_t)i * dirf;
+					int b = 4;
+					if (i >= 0 && i < tlen) b = tb[i];
+					else if (f >= 0 && f < ix.l_pac) b = dev_ref_base(ix.pac, ix.l_pac, J.tpos + (long long)i * J.tdir);
+					if (b < 4 && comp) b = 3 - b;
+					if (b < 4 && special && CTX_IS_N(f)) b = 4;
+					fx[k] = (uint8_t)b;
+				}
+				WAVE_SYNC();
+				int x = 0, y = 0;
+				for (int k = 0; k < n_cigar; ++k) {
+					const uint32_t cg = (uint32_t)__builtin_amdgcn_readfirstlane((int)cig[k]);
+					const int op = (int)(cg & 0xf), len = (int)(cg >> 4);
+					if (op == 0) {
+						for (int i = lane; i < len; i += 64) {
+							const int q0 = qb[x + i], q = comp ? (q0 < 4 ? 3 - q0 : 4) : q0;
+							const int r = fx[y + i + 1];
+							if (r == 1 || r == 2) {
+								const int nb = r == 1 ? fx[y + i + 1 + dirf] : fx[y + i + 1 - dirf];
+								const int bucket = r == 1 || nb == 4 ? nb : 3 - nb;
+								const bool ret = q == r, conv = r == 1 ? q == 3 : q == 0;
+								if (ret || conv) atomicAdd(&cnt[(r - 1) * 10 + bucket * 2 + (conv ? 1 : 0)], 1);
+							}
+						}
+						x += len; y += len;
+					} else if (op == 2) y += len;
+					else if (op == 1) x += len;
+				}
+				WAVE_SYNC();
+				if (lane < 20) { const int v = cnt[lane]; (&ctxo[job].n[0][0][0])[lane] = (uint16_t)(v > 65535 ? 65535 : v); }
+			} else if (lane == 0) { // no CIGAR, or a target beyond the LDS stage: one lane, bases from pac
+				int c[20];
+				for (int k = 0; k < 20; ++k) c[k] = 0;
+				int x = 0, y = 0;
+				for (int k = 0; k < (n_cigar > 0 ? n_cigar : 0); ++k) {
+					const int op = (int)(cig[k] & 0xf), len = (int)(cig[k] >> 4);
+					if (op == 0) {
+						for (int i = 0; i < len; ++i) {
+							const int rv = dev_ref_base(ix.pac, ix.l_pac, J.tpos + (long long)(y + i) * J.tdir), r = comp ? 3 - rv : rv;
+							if (r != 1 && r != 2) continue;
+							const int64_t f = f0 + (int64_t)(y + i) * dirf, fn = r == 1 ? f + 1 : f - 1;
+							if (special && CTX_IS_N(f)) continue;
+							const int q0 = qb[x + i], q = comp ? (q0 < 4 ? 3 - q0 : 4) : q0;
+							const bool ret = q == r, conv = r == 1 ? q == 3 : q == 0;
+							if (!ret && !conv) continue;
+							int nb = 4;
+							if (fn >= 0 && fn < ix.l_pac && !(special && CTX_IS_N(fn))) nb = dev_ref_base(ix.pac, ix.l_pac, fn);   // (a forward coordinate)
+							const int slot = (r - 1) * 10 + (r == 1 || nb == 4 ? nb : 3 - nb) * 2 + (conv ? 1 : 0);
+							// (no indexed register array: the twenty counters are picked by a chain of selects the compiler keeps in registers)
+							#pragma unroll
+							for (int t = 0; t < 20; ++t) c[t] += t == slot ? 1 : 0;
+						}
+						x += len; y += len;
+					} else if (op == 2) y += len;
+					else if (op == 1) x += len;
+				}
+				#pragma unroll
+				for (int t = 0; t < 20; ++t) (&ctxo[job].n[0][0][0])[t] = (uint16_t)(c[t] > 65535 ? 65535 : c[t]);
+			}
+			#undef CTX_IS_N
+		}
 		WAVE_SYNC();
 	}
 }
@@ -303,27 +415,34 @@ k_global(DevIndex ix, DevScoring sc, const uint8_t *reads, const bsx_glb_job_t *
 template <int NC>
 static void launch_glb_nc(hipStream_t st, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_glb_job_t *jobs, const int *order,
                           long long n, bsx_glb_res_t *res, uint32_t *pool, uint8_t *zscratch, size_t zstride, int qcap, int blocks, int wpb,
-                          bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, int tcap, void *hbm_rows = nullptr)
+                          bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, int tcap, void *hbm_rows = nullptr,
+                          bsx_glb_ctx_t *ctx = nullptr)
 {
 	const int stride = 2 * (qcap + 2) + ((qcap + 3) >> 2) + 1 + ((tcap + 3) >> 2);
 	const size_t lds = hbm_rows ? 0 : (size_t)wpb * stride * 4;
-	if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_global<NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-	hipLaunchKernelGGL(k_global<NC>, dim3(blocks), dim3(wpb * 64), lds, st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap,
-	                   tags, md_pool, md_cap, md_cursor, tcap, (int32_t*)hbm_rows);
+	if (ctx) {
+		if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_global<NC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		hipLaunchKernelGGL((k_global<NC, true>), dim3(blocks), dim3(wpb * 64), lds, st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap,
+		                   tags, md_pool, md_cap, md_cursor, tcap, (int32_t*)hbm_rows, ctx);
+		return;
+	}
+	if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_global<NC, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+	hipLaunchKernelGGL((k_global<NC, false>), dim3(blocks), dim3(wpb * 64), lds, st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap,
+	                   tags, md_pool, md_cap, md_cursor, tcap, (int32_t*)hbm_rows, (bsx_glb_ctx_t*)nullptr);
 }
 size_t global_hbm_row_bytes(int qcap) { return (size_t)(2 * (qcap + 2) + ((qcap + 3) >> 2) + 1) * 4; }
 void launch_global_hbm(hipStream_t st, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_glb_job_t *jobs, const int *order,
                        long long n, bsx_glb_res_t *res, uint32_t *pool, uint8_t *zscratch, size_t zstride, int qcap, int blocks,
-                       bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, void *rows)
+                       bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, void *rows, bsx_glb_ctx_t *ctx)
 {
-	launch_glb_nc<32>(st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap, blocks, 1, tags, md_pool, md_cap, md_cursor, 0, rows);
+	launch_glb_nc<32>(st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap, blocks, 1, tags, md_pool, md_cap, md_cursor, 0, rows, ctx);
 }
 
 void launch_global(hipStream_t st, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_glb_job_t *jobs, const int *order,
                    long long n, bsx_glb_res_t *res, uint32_t *pool, uint8_t *zscratch, size_t zstride, int qcap, int nc, int blocks, int wpb,
-                   bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, int tcap)
+                   bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, int tcap, bsx_glb_ctx_t *ctx)
 {
-	if (nc <= 4) launch_glb_nc<4>(st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap, blocks, wpb, tags, md_pool, md_cap, md_cursor, tcap);
-	else if (nc <= 16) launch_glb_nc<16>(st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap, blocks, wpb, tags, md_pool, md_cap, md_cursor, tcap);
-	else launch_glb_nc<32>(st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap, blocks, wpb, tags, md_pool, md_cap, md_cursor, tcap);
+	if (nc <= 4) launch_glb_nc<4>(st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap, blocks, wpb, tags, md_pool, md_cap, md_cursor, tcap, nullptr, ctx);
+	else if (nc <= 16) launch_glb_nc<16>(st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap, blocks, wpb, tags, md_pool, md_cap, md_cursor, tcap, nullptr, ctx);
+	else launch_glb_nc<32>(st, ix, sc, reads, jobs, order, n, res, pool, zscratch, zstride, qcap, blocks, wpb, tags, md_pool, md_cap, md_cursor, tcap, nullptr, ctx);
 }

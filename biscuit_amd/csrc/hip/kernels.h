@@ -32,14 +32,15 @@ void launch_extend_hbm(hipStream_t st, const DevIndex &ix, const DevScoring &sc,
 size_t global_hbm_row_bytes(int qcap);
 void launch_global_hbm(hipStream_t st, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_glb_job_t *jobs, const int *order,
                        long long n, bsx_glb_res_t *res, uint32_t *pool, uint8_t *zscratch, size_t zstride, int qcap, int blocks,
-                       bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, void *rows);   // one wave per workgroup
+                       bsx_glb_tag_t *tags, char *md_pool, unsigned long long md_cap, unsigned long long *md_cursor, void *rows, bsx_glb_ctx_t *ctx = nullptr);   // one wave per workgroup; ctx: the k_global_ctx form
 void launch_sw(hipStream_t st, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_sw_job_t *jobs, const int *order,
                long long n, bsx_sw_res_t *res, unsigned long long *bscratch, int bcap, int blocks, int nc);
 void launch_swl(hipStream_t st, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_sw_job_t *jobs, const int *order,
                 long long n, bsx_sw_res_t *res, unsigned long long *bscratch, int bcap, int blocks, int slen_max);   // k_swl.hip: byte-sized jobs, four to a wavefront
 void launch_global(hipStream_t st, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_glb_job_t *jobs, const int *order,
                    long long n, bsx_glb_res_t *res, uint32_t *pool, uint8_t *zscratch, size_t zstride, int qcap, int nc, int blocks, int wpb,
-                   bsx_glb_tag_t *tags = nullptr, char *md_pool = nullptr, unsigned long long md_cap = 0, unsigned long long *md_cursor = nullptr, int tcap = 0);
+                   bsx_glb_tag_t *tags = nullptr, char *md_pool = nullptr, unsigned long long md_cap = 0, unsigned long long *md_cursor = nullptr, int tcap = 0,
+                   bsx_glb_ctx_t *ctx = nullptr);   // ctx != nullptr (with tags): k_global_ctx, which also fills ctx[job] (bsx_global_batch_tags_ctx)
 // K4 four to a wavefront (k_ext4.hip): a row of 16 lanes per job, persistent rows taking jobs off *cursor (zero at launch).
 // launch_x4: the extensions of the best seed of every chain the tiers exported (records with has_ext), written into the records ahead of
 // launch_c2r; jobs = room for job_cap jobs of x4_job_bytes(), ctr32[0..3]: job counts and cursor (zeroed by the call).

@@ -38,7 +38,7 @@ struct Lane {
 	DevBuf qpack;            // the chunk's reads as base-3 digits for the seeding kernel (k_seedt.hip)
 	int64_t rb_tasks = 0;    // strand searches of the last regions batch (their regions, offsets and counts are still in regs / regmeta)
 	int flt_key[3] = {-1, -1, -1};   // what fltab was made for
-	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, dd, sswjobs, c2rslab;
+	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, gctx, dd, sswjobs, c2rslab;
 	DevBuf small;          // counters[4] | out_cursor | task_cursor | region cursors
 	HostBuf hstage;        // pinned staging for bulk results
 	HostBuf pin;           // two pinned halves through which large host<->device copies are streamed
@@ -76,7 +76,7 @@ struct bsx_device {
 	char name[256];
 	int n_cu = 0;
 	DevIndex ix; bool has_index = false;
-	DevBuf bwt[2], sa[2], pac, ctg, seedtab[2];
+	DevBuf bwt[2], sa[2], pac, ctg, holes, seedtab[2];
 	Lane lane[BSX_LANES];   // scoring matrices and penalties are per lane (Lane::sc): chunks with different options may be in flight together
 	// Front halves of consecutive chunks are chained stage by stage (the seeding launch of chunk k+1 waits for that of chunk k, the
 	// region launches likewise): four chunks that share the device evenly all finish at the same moment, and the device then idles
@@ -173,11 +173,11 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 	(void)hipSetDevice(d->ordinal);
 	devbuf_drain(d->ordinal);   // the blocks this device's buffers left behind when they grew
 	for (int i = 0; i < 2; ++i) { d->bwt[i].release(); d->sa[i].release(); d->seedtab[i].release(); }
-	d->pac.release(); d->ctg.release();
+	d->pac.release(); d->ctg.release(); d->holes.release();
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
 		L.reads.release(); L.qpack.release(); L.gath.release(); L.jobs.release(); L.res.release(); L.scratch.release(); L.scratch2.release(); L.out.release(); L.aux.release(); L.pool.release();
-		L.small.release(); L.hstage.release(); L.regs.release(); L.regmeta.release(); L.slabs.release(); L.slabflags.release(); L.slabs3.release(); L.redo.release(); L.pin.release(); L.pos.release(); L.posoff.release(); L.xpool.release(); L.xmeta.release(); L.x4jobs.release(); L.fltab.release(); L.flt_key[0] = -1; L.tags.release(); L.mdpool.release(); L.dd.release(); L.c2rslab.release(); L.sswjobs.release(); L.msw_jobs.release(); L.msw_res.release(); L.msw_meta.release(); L.msw_roff.release();
+		L.small.release(); L.hstage.release(); L.regs.release(); L.regmeta.release(); L.slabs.release(); L.slabflags.release(); L.slabs3.release(); L.redo.release(); L.pin.release(); L.pos.release(); L.posoff.release(); L.xpool.release(); L.xmeta.release(); L.x4jobs.release(); L.fltab.release(); L.flt_key[0] = -1; L.tags.release(); L.mdpool.release(); L.gctx.release(); L.dd.release(); L.c2rslab.release(); L.sswjobs.release(); L.msw_jobs.release(); L.msw_res.release(); L.msw_meta.release(); L.msw_roff.release();
 		if (L.pev[0]) (void)hipEventDestroy(L.pev[0]);
 		if (L.pev[1]) (void)hipEventDestroy(L.pev[1]);
 		if (L.ev0) (void)hipEventDestroy(L.ev0);
@@ -227,6 +227,15 @@ static int upload_ref(bsx_device_t *d, const bsx_index_t *idx)
 		HIPCHK(hipMemcpy(d->ctg.p, off.data(), ((size_t)ns + 1) * 8, hipMemcpyHostToDevice));
 		HIPCHK(hipMemcpy((char*)d->ctg.p + ((size_t)ns + 1) * 8, alt.data(), (size_t)ns, hipMemcpyHostToDevice));
 		d->ix.ctg_off = (const int64_t*)d->ctg.p; d->ix.ctg_alt = (const uint8_t*)d->ctg.p + ((size_t)ns + 1) * 8; d->ix.n_seqs = ns;
+	}
+	{ // the N holes of the forward strand (.bis.amb, or the builder's list): starts, then ends, in the file's order (sorted by position)
+		const int nh = idx->ref.n_holes;
+		std::vector<int64_t> he((size_t)nh * 2 + 1);
+		for (int i = 0; i < nh; ++i) { he[i] = idx->ref.ambs[i].offset; he[(size_t)nh + i] = idx->ref.ambs[i].offset + idx->ref.ambs[i].len; }
+		for (int i = 1; i < nh; ++i) if (he[i] < he[(size_t)nh + i - 1]) { fprintf(stderr, "[bsx-hip] the index's N holes are not sorted\n"); return BSX_E_FORMAT; }
+		if ((rc = d->holes.reserve((size_t)nh * 16 + 16)) != BSX_OK) return rc;
+		if (nh) HIPCHK(hipMemcpy(d->holes.p, he.data(), (size_t)nh * 16, hipMemcpyHostToDevice));
+		d->ix.hole_off = (const int64_t*)d->holes.p; d->ix.hole_end = (const int64_t*)d->holes.p + nh; d->ix.n_holes = nh; d->ix.pad2_ = 0;
 	}
 	return BSX_OK;
 }
@@ -1693,7 +1702,8 @@ static int lane_msw_plan(bsx_device_t *d, int lane, const bsx_opt_t *opt, const 
 // K6
 // ------------------------------------------------------------------------------------------
 static int lane_global_batch(bsx_device_t *d, int lane, int64_t n, const bsx_glb_job_t *jobs, bsx_glb_res_t *res,
-                             uint32_t *cigar_pool, size_t cigar_pool_len, bsx_glb_tag_t *tags = nullptr, char **md = nullptr, int64_t *md_cap = nullptr)
+                             uint32_t *cigar_pool, size_t cigar_pool_len, bsx_glb_tag_t *tags = nullptr, char **md = nullptr, int64_t *md_cap = nullptr,
+                             bsx_glb_ctx_t *ctx = nullptr)   // ctx (with tags): the k_global_ctx form, counts by context for both strand hypotheses
 {
 	if (!d || !d->has_index) return BSX_E_NODEVICE;
 	Lane &L = d->lane[lane];
@@ -1758,6 +1768,10 @@ static int lane_global_batch(bsx_device_t *d, int lane, int64_t n, const bsx_glb
 		HIPCHK(hipMemsetAsync(md_cursor, 0, 8, L.st_hi));
 		HIPCHK(hipMemsetAsync(L.tags.p, 0xff, (size_t)n * sizeof(bsx_glb_tag_t), L.st_hi));   // l_md = -1: jobs that ask for no CIGAR
 	}
+	if (ctx) {
+		if ((rc = L.gctx.reserve((size_t)n * sizeof(bsx_glb_ctx_t))) != BSX_OK) return rc;
+		HIPCHK(hipMemsetAsync(L.gctx.p, 0, (size_t)n * sizeof(bsx_glb_ctx_t), L.st_hi));
+	}
 	H2D(L.st_hi, L.jobs.p, jobs, (size_t)n * sizeof(bsx_glb_job_t));
 	size_t off = 0;
 	for (int c = 0; c < 4; ++c) if (!order[c].empty()) {
@@ -1770,11 +1784,13 @@ static int lane_global_batch(bsx_device_t *d, int lane, int64_t n, const bsx_glb
 		if (c == 3)
 			launch_global_hbm(L.st_hi, d->ix, L.sc, (const uint8_t*)L.reads.p, (const bsx_glb_job_t*)L.jobs.p, (const int*)L.aux.p + off,
 			                  (long long)order[c].size(), (bsx_glb_res_t*)L.res.p, (uint32_t*)L.pool.p, (uint8_t*)L.scratch.p, zmax[c], hbm_qmax, blocks[c],
-			                  tags ? (bsx_glb_tag_t*)L.tags.p : nullptr, (char*)L.mdpool.p, (unsigned long long)md_bound, md_cursor, (char*)L.scratch.p + rows_off);
+			                  tags ? (bsx_glb_tag_t*)L.tags.p : nullptr, (char*)L.mdpool.p, (unsigned long long)md_bound, md_cursor, (char*)L.scratch.p + rows_off,
+			                  ctx ? (bsx_glb_ctx_t*)L.gctx.p : nullptr);
 		else
 		launch_global(L.st_hi, d->ix, L.sc, (const uint8_t*)L.reads.p, (const bsx_glb_job_t*)L.jobs.p, (const int*)L.aux.p + off,
 		              (long long)order[c].size(), (bsx_glb_res_t*)L.res.p, (uint32_t*)L.pool.p, (uint8_t*)L.scratch.p, zmax[c],
-		              QCAP[c], NCS[c], blocks[c], WPB[c], tags ? (bsx_glb_tag_t*)L.tags.p : nullptr, (char*)L.mdpool.p, (unsigned long long)md_bound, md_cursor, tags ? TCAP[c] : 0);
+		              QCAP[c], NCS[c], blocks[c], WPB[c], tags ? (bsx_glb_tag_t*)L.tags.p : nullptr, (char*)L.mdpool.p, (unsigned long long)md_bound, md_cursor, tags ? TCAP[c] : 0,
+		              ctx ? (bsx_glb_ctx_t*)L.gctx.p : nullptr);
 		off += order[c].size();
 	}
 	HIPCHK(hipEventRecord(L.ev1, L.st_hi));
@@ -1793,6 +1809,7 @@ static int lane_global_batch(bsx_device_t *d, int lane, int64_t n, const bsx_glb
 		}
 		D2H(L.st_hi, *md, L.mdpool.p, (size_t)used);
 	}
+	if (ctx) D2H(L.st_hi, ctx, L.gctx.p, (size_t)n * sizeof(bsx_glb_ctx_t));
 	return BSX_OK;
 }
 
@@ -1819,6 +1836,9 @@ extern "C" BSX_API int bsx_global_batch(bsx_device_t *d, int64_t n, const bsx_gl
 extern "C" BSX_API int bsx_global_batch_tags(bsx_device_t *d, int64_t n, const bsx_glb_job_t *jobs, bsx_glb_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_len,
                                              bsx_glb_tag_t *tags, char **md, int64_t *md_cap)
 { if (!tags || !md || !md_cap) return BSX_E_ARG; return lane_global_batch(d, 0, n, jobs, res, cigar_pool, cigar_pool_len, tags, md, md_cap); }
+extern "C" BSX_API int bsx_global_batch_tags_ctx(bsx_device_t *d, int64_t n, const bsx_glb_job_t *jobs, bsx_glb_res_t *res, uint32_t *cigar_pool, size_t cigar_pool_len,
+                                                 bsx_glb_tag_t *tags, char **md, int64_t *md_cap, bsx_glb_ctx_t *ctx)
+{ if (!tags || !md || !md_cap || !ctx) return BSX_E_ARG; return lane_global_batch(d, 0, n, jobs, res, cigar_pool, cigar_pool_len, tags, md, md_cap, ctx); }
 
 // the seams as one vtable for the host pipeline; ctx = (device, lane)
 #define LR(c) ((LaneRef*)(c))->d, ((LaneRef*)(c))->lane
@@ -1848,6 +1868,8 @@ static int be_dedup2(void *c, const bsx_opt_t *o, int64_t n_reads, int per_read,
 static int be_glb(void *c, int64_t n, const bsx_glb_job_t *j, bsx_glb_res_t *r, uint32_t *pool, size_t len) { return lane_global_batch(LR(c), n, j, r, pool, len); }
 static int be_glb_tags(void *c, int64_t n, const bsx_glb_job_t *j, bsx_glb_res_t *r, uint32_t *pool, size_t len, bsx_glb_tag_t *t, char **md, int64_t *cap)
 { return lane_global_batch(LR(c), n, j, r, pool, len, t, md, cap); }
+static int be_glb_tags_ctx(void *c, int64_t n, const bsx_glb_job_t *j, bsx_glb_res_t *r, uint32_t *pool, size_t len, bsx_glb_tag_t *t, char **md, int64_t *cap, bsx_glb_ctx_t *x)
+{ return lane_global_batch(LR(c), n, j, r, pool, len, t, md, cap, x); }
 
 static LaneRef g_lane_ref[8][BSX_LANES];   // ctx storage for the vtables (by device ordinal)
 
@@ -1860,7 +1882,7 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	memset(out, 0, sizeof(*out));
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
-	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags;
+	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx;
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

@@ -186,6 +186,10 @@ typedef struct bsx_backend {
 	 * applicable, plan on the host.  token: changes with the chunk (the reads' offsets roff[0 .. n_reads] are uploaded once per chunk) */
 	int (*msw_plan)(void *ctx, const bsx_opt_t *opt, const bsx_pestat_t *pes, int64_t token, int64_t n_reads, int per_read, const uint32_t *roff, int max_len,
 	                int p0, int p1, void *table, bsx_sw_res_t **res, int64_t *res_cap, int64_t *n_jobs);
+	/* optional (may be NULL; a backend that clears the struct has it NULL), with global_batch_tags: the same with the counts by cytosine
+	 * context of both bisulfite-strand hypotheses, see bsx_global_batch_tags_ctx.  Without it the host walks the record (sam.c). */
+	int (*global_batch_tags_ctx)(void *ctx, int64_t n, const bsx_glb_job_t *jobs, bsx_glb_res_t *res,
+	                             uint32_t *cigar_pool, size_t cigar_pool_len, bsx_glb_tag_t *tags, char **md, int64_t *md_cap, bsx_glb_ctx_t *cx);
 } bsx_backend_t;
 /* what msw_plan says about a pair: base = its first job in res (-1: the pair is left to the host's own plan), n_c[i] = candidates of read i it
  * looked at, mask[i] = which of them have a job (bit j: candidate j), in job order: read 0's, then read 1's */

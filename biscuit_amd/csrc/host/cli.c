@@ -59,6 +59,10 @@ static int usage(void)
 		"  scoring   : -A -B INT  -O -E -L INT[,INT]  -U INT\n"
 		"  I/O       : -1/-2 STR reads on the command line  -i -p -R STR -F -H STR/FILE -j -q -T INT -g INT[,INT]\n"
 		"              -a -C -V -Y -M -I FLOAT[,FLOAT[,INT[,INT]]] -v INT -h\n"
+		"  bsconv    : --bsconv  add ZN:Z:CA_R<r>C<c>,CC_..,CG_..,CT_.. (retention / conversion by cytosine context) to every mapped record\n"
+		"              --bsconv-max-cph INT  --bsconv-max-cpa INT  --bsconv-max-cpc INT  --bsconv-max-cpt INT  --bsconv-max-cpy INT\n"
+		"              --bsconv-max-cph-frac FLOAT  --bsconv-max-cpy-frac FLOAT  --bsconv-filter-u  --bsconv-show-filtered\n"
+		"              any of these: annotate, and keep or drop each record as `biscuit bsconv` -m -a -c -t -x -f -y -u -v would\n"
 		"  device    : $BSX_DEVICE selects the HIP device ordinal (default 0)\n\n");
 	return 1;
 }
@@ -308,6 +312,20 @@ static void emit_chunk(bsx_read_t *seqs, int n, int64_t chunk_idx, int ok)
 	free(seqs);
 }
 
+/* what `biscuit bsconv` says when it is done (src/bsconv.c:257-259), and the eight totals it hands to `biscuit qc` */
+static void bsconv_print(const uint64_t t[8], uint64_t n, uint64_t nf)
+{
+	fprintf(stderr, "[M::bsconv] processed %llu, %llu remain\n", (unsigned long long)n, (unsigned long long)(n - nf));
+	fprintf(stderr, "[M::bsconv] CpA_R %llu CpA_C %llu CpC_R %llu CpC_C %llu CpG_R %llu CpG_C %llu CpT_R %llu CpT_C %llu\n", (unsigned long long)t[0], (unsigned long long)t[1],
+	        (unsigned long long)t[2], (unsigned long long)t[3], (unsigned long long)t[4], (unsigned long long)t[5], (unsigned long long)t[6], (unsigned long long)t[7]);
+}
+static void bsconv_report(void)
+{
+	uint64_t t[8], n, nf;
+	bsx_process_bsconv_totals(t, &n, &nf, 0);
+	bsconv_print(t, n, nf);
+}
+
 BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void *ud, int (*open_device)(int ordinal, const bsx_index_t *idx, void **ud))
 {
 	bsx_opt_t opt_, opt0, *opt = &opt_;
@@ -320,6 +338,17 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	int64_t n_processed = 0;
 	const uint8_t *nt4 = bsx_nt4_table();
 
+	/* long options only for what the reference's command line does not have (the short option string below is the reference's) */
+	static const struct option long_opts[] = {
+		{"bsconv", no_argument, 0, 1000}, {"bsconv-max-cph", required_argument, 0, 1001}, {"bsconv-max-cpa", required_argument, 0, 1002},
+		{"bsconv-max-cpc", required_argument, 0, 1003}, {"bsconv-max-cpt", required_argument, 0, 1004}, {"bsconv-max-cpy", required_argument, 0, 1005},
+		{"bsconv-max-cph-frac", required_argument, 0, 1006}, {"bsconv-max-cpy-frac", required_argument, 0, 1007},
+		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {0, 0, 0, 0}
+	};
+	bsx_bsconv_conf_t bsconv;
+	int bsconv_on = 0;
+
+	bsx_bsconv_conf_init(&bsconv);
 	g_write_error = 0;   /* per call: a failed write of an earlier call in this process must not fail this one */
 	if (getenv("BSX_DEVICE")) device = atoi(getenv("BSX_DEVICE"));
 	bsx_opt_init(opt);
@@ -327,7 +356,20 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	memset(&opt0, 0, sizeof(opt0));
 	if (argc < 2) return usage();
 	optind = 1;
-	while ((c = getopt(argc, argv, ":@:1:2:3:5:9ab:c:d:ef:g:hijk:m:pqr:s:v:w:x:y:z:A:B:CD:E:FG:H:I:J:K:L:MN:O:PQ:R:ST:U:VW:X:Y")) >= 0) {
+	while ((c = getopt_long(argc, argv, ":@:1:2:3:5:9ab:c:d:ef:g:hijk:m:pqr:s:v:w:x:y:z:A:B:CD:E:FG:H:I:J:K:L:MN:O:PQ:R:ST:U:VW:X:Y", long_opts, 0)) >= 0) {
+		if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
+			bsconv_on = 1;
+			if (c == 1000) bsconv.annotate = 1;
+			else if (c == 1001) bsconv.max_cph = atoi(optarg);
+			else if (c == 1002) bsconv.max_cpa = atoi(optarg);
+			else if (c == 1003) bsconv.max_cpc = atoi(optarg);
+			else if (c == 1004) bsconv.max_cpt = atoi(optarg);
+			else if (c == 1005) bsconv.max_cpy = atoi(optarg);
+			else if (c == 1006) bsconv.max_cph_frac = (float)atof(optarg);
+			else if (c == 1007) bsconv.max_cpy_frac = (float)atof(optarg);
+			else if (c == 1008) bsconv.filter_u = 1;
+			else if (c == 1009) bsconv.show_filtered = 1;
+		} else
 		if (c == 'k') opt->min_seed_len = atoi(optarg), opt0.min_seed_len = 1;
 		else if (c == '1') seq1 = strdup(optarg);
 		else if (c == '2') seq2 = strdup(optarg);
@@ -418,8 +460,8 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 			if (bsx_verbose >= 3)
 				fprintf(stderr, "[M::%s] mean insert size: %.3f, stddev: %.3f, max: %d, min: %d\n", "main_align", pes0->avg, pes0->std, pes0->high, pes0->low);
 		} else if (c == 'h') return usage();
-		else if (c == ':') { usage(); fprintf(stderr, "Option needs an argument: -%c\n", optopt); return 1; }
-		else if (c == '?') { usage(); fprintf(stderr, "Unrecognized option: -%c\n", optopt); return 1; }
+		else if (c == ':') { usage(); if (optopt >= 1000) fprintf(stderr, "Option needs an argument: %s\n", argv[optind - 1]); else fprintf(stderr, "Option needs an argument: -%c\n", optopt); return 1; }
+		else if (c == '?') { usage(); if (!optopt) fprintf(stderr, "Unrecognized option: %s\n", argv[optind - 1]); else fprintf(stderr, "Unrecognized option: -%c\n", optopt); return 1; }
 		else return usage();
 	}
 	if (rg_line) { hdr_line = insert_header(rg_line, hdr_line); free(rg_line); }
@@ -460,6 +502,8 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		} else { fprintf(stderr, "[E::%s] unknown read type '%s'\n", "main_align", mode); return 1; }
 	} else update_a(opt, &opt0);
 	bsx_opt_fill_matrices(opt);
+	if (bsconv_on) bsconv.annotate = 1;   /* a filter implies the annotation */
+	bsx_process_set_bsconv(bsconv_on ? &bsconv : 0);   /* every chunk of this call, through a stream or not; totals from zero */
 	if (optind >= argc) { usage(); fprintf(stderr, "Missing fai-index base\n"); return 1; }
 	if ((rc = bsx_index_load(argv[optind], &idx)) != BSX_OK) { fprintf(stderr, "[E::%s] fail to locate the index files (%s)\n", "main_align", bsx_strerror(rc)); return 1; }
 	if (auto_alt) infer_alt(&idx->ref);
@@ -659,7 +703,9 @@ loop_done:
 	if (bsx_fq_error(f1) || bsx_fq_error(f2)) { fprintf(stderr, "[E::%s] damaged or truncated compressed input: the SAM is incomplete\n", "main_align"); rc = 1; }
 	if (fflush(stdout) != 0 || ferror(stdout)) g_write_error = 1;
 	if (g_write_error) { fprintf(stderr, "[E::%s] failed to write the output: the SAM is incomplete\n", "main_align"); rc = 1; }
+	if (bsconv_on && bsx_shard_world <= 1) bsconv_report();   /* (several ranks: rank 0 reports the sum, bsx_align_main_ranks_with) */
 cleanup:
+	if (bsconv_on && bsx_shard_world <= 1) bsx_process_set_bsconv(0);
 	if (open_device && ud && g_close_device) g_close_device(ud);   /* the device this call opened: index replica, lanes, streams */
 	free(hdr_line); free(opt->adaptor1); free(opt->adaptor2); free(pes0); free(seq1); free(seq2);
 	bsx_fq_close(f1); bsx_fq_close(f2);
@@ -754,6 +800,19 @@ BSX_API int bsx_align_main_ranks_with(int argc, char **argv, bsx_process_fn proc
 	if (pthread_create(&th, 0, ranks_aligner, &R) != 0) { (void)ranks_aligner(&R); }
 	rc = bsx_gather_run(R.G, &n_chunks);
 	pthread_join(th, 0);
+	{ /* conversion by context: every rank's totals added up (the transport's all-reduce; all zero when the option is off), rank 0 reports */
+		uint64_t t[8], n = 0, nf = 0;
+		int64_t v[11];
+		int k, on = 0;
+		for (k = 1; k < argc; ++k) if (strncmp(argv[k], "--bsconv", 8) == 0) on = 1;
+		bsx_process_bsconv_totals(t, &n, &nf, 1);
+		for (k = 0; k < 8; ++k) v[k] = (int64_t)t[k];
+		v[8] = (int64_t)n; v[9] = (int64_t)nf; v[10] = on;
+		if (R.tg.all_reduce_sum && R.tg.all_reduce_sum(R.tg.ctx, v, 11) == BSX_OK) {
+			if (rank == 0 && v[10] > 0) { for (k = 0; k < 8; ++k) t[k] = (uint64_t)v[k]; bsconv_print(t, (uint64_t)v[8], (uint64_t)v[9]); }
+		} else if (on) { R.failed = 1; fprintf(stderr, "[E::%s] adding the conversion totals over the ranks failed\n", "main_align"); }
+		bsx_process_set_bsconv(0);
+	}
 	bsx_emit_hook = 0; bsx_emit_ud = 0; bsx_pes_hist_hook = 0; bsx_pes_hist_ud = 0; bsx_shard_rank = 0; bsx_shard_world = 1; bsx_shard_mode = 0; g_ranks = 0;
 	if (R.out && R.out != stdout && fclose(R.out) != 0) R.failed = 1;
 	else if (R.out == stdout && fflush(stdout) != 0) R.failed = 1;

@@ -87,8 +87,43 @@ BSX_API void bsx_hook_clip_read(const bsx_opt_t *opt, int l_seq, uint8_t *seq, c
 }
 BSX_API int bsx_hook_pair_names_ok(const char *n1, const char *n2) { return pair_names_ok(n1, n2); }
 
+/* ------------------------------------------------------------------ conversion by context: setting and totals of a stream, or of the process */
+typedef struct { bsx_bsconv_conf_t conf; int on, filter; uint64_t tot[10]; } bsconv_state_t;   /* tot: the eight totals, records seen, records filtered */
+static bsconv_state_t g_bsconv;
+static int bsconv_state_set(bsconv_state_t *b, const bsx_bsconv_conf_t *conf)
+{
+	memset(b, 0, sizeof(*b));
+	if (!conf) return BSX_OK;
+	b->conf = *conf;
+	b->filter = bsx_bsconv_filters(conf);
+	b->on = conf->annotate || b->filter;
+	return BSX_OK;
+}
+static int bsconv_state_totals(const bsconv_state_t *b, uint64_t out[8], uint64_t *n, uint64_t *n_filtered)
+{
+	int i;
+	for (i = 0; i < 8; ++i) if (out) out[i] = __atomic_load_n(&b->tot[i], __ATOMIC_RELAXED);
+	if (n) *n = __atomic_load_n(&b->tot[8], __ATOMIC_RELAXED);
+	if (n_filtered) *n_filtered = __atomic_load_n(&b->tot[9], __ATOMIC_RELAXED);
+	return BSX_OK;
+}
+BSX_API void bsx_bsconv_conf_init(bsx_bsconv_conf_t *conf)
+{
+	memset(conf, 0, sizeof(*conf));
+	conf->max_cph = conf->max_cpa = conf->max_cpc = conf->max_cpt = conf->max_cpy = -1;   /* main_bsconv, src/bsconv.c:216-219 */
+	conf->max_cph_frac = conf->max_cpy_frac = 1.0f;
+}
+BSX_API int bsx_process_set_bsconv(const bsx_bsconv_conf_t *conf) { return bsconv_state_set(&g_bsconv, conf); }
+BSX_API int bsx_process_bsconv_totals(uint64_t out[8], uint64_t *n, uint64_t *n_filtered, int reset)
+{
+	bsconv_state_totals(&g_bsconv, out, n, n_filtered);
+	if (reset) memset(g_bsconv.tot, 0, sizeof(g_bsconv.tot));
+	return BSX_OK;
+}
+
 /* ------------------------------------------------------------------ chunk state */
 typedef struct {
+	bsconv_state_t *bs;  /* conversion by context for this chunk's records (NULL: off): its stream's setting, else the process's */
 	const bsx_backend_t *be;
 	const bsx_opt_t *opt;
 	const bsx_index_t *idx;
@@ -837,6 +872,7 @@ static void out_worker(void *data, long k_, int tid)
 typedef struct {
 	chunk_t *C; samctx_t *ctx; int per, u0; const int *todo, *jread, *jreg; const bsx_glb_job_t *sub; const bsx_glb_res_t *sres; const uint32_t *pool;
 	const bsx_glb_tag_t *tags; const char *md;   /* NM / MD / ZC / ZR from the backend, or NULL */
+	const bsx_glb_ctx_t *cx;                     /* counts by context from the backend, or NULL (then walked here when wanted) */
 } finish_par_t;
 static void finish_worker(void *data, long k, int tid)
 {
@@ -846,6 +882,11 @@ static void finish_worker(void *data, long k, int tid)
 	if (F->sres[k].n_cigar < 0) return;   /* did not fit: redone with more room */
 	bsx_setsam_finish(F->C->opt, F->C->idx, &F->C->reads[ri], &F->C->regs[ri].a[F->jreg[jj]], F->pool + F->sub[k].cigar_off, F->sres[k].n_cigar,
 	                  &F->ctx[ri / F->per - F->u0].table[ri % F->per][F->jreg[jj]], F->tags ? &F->tags[k] : 0, F->tags ? F->md + F->tags[k].md_off : 0);
+	if (F->C->bs) {
+		bsx_glb_ctx_t *zn = &F->ctx[ri / F->per - F->u0].zn[ri % F->per][F->jreg[jj]];
+		if (F->cx) *zn = F->cx[k];
+		else bsx_setsam_ctx_host(F->C->idx, &F->C->reads[ri], &F->C->regs[ri].a[F->jreg[jj]], F->pool + F->sub[k].cigar_off, F->sres[k].n_cigar, zn);
+	}
 }
 
 typedef struct { chunk_t *C; samctx_t *ctx; int per, u0; int *cnt; int64_t *off; bsx_glb_job_t *jobs; int *jread, *jreg, *todo; } plan_par_t;
@@ -868,6 +909,10 @@ static void plan_jobs_worker(void *data, long u, int tid)
 		reg_v *regs = &C->regs[ri];
 		Q->ctx[u].table[w] = (samrec_t*)bsx_crealloc(0, 0, sizeof(samrec_t) * (regs->n ? regs->n : 1));
 		memset(Q->ctx[u].table[w], 0, sizeof(samrec_t) * (regs->n ? regs->n : 1));
+		if (C->bs) {
+			Q->ctx[u].zn[w] = (bsx_glb_ctx_t*)bsx_crealloc(0, 0, sizeof(bsx_glb_ctx_t) * (regs->n ? regs->n : 1));
+			memset(Q->ctx[u].zn[w], 0, sizeof(bsx_glb_ctx_t) * (regs->n ? regs->n : 1));
+		}
 		for (k = 0; k < Q->ctx[u].want[w].n; ++k, ++at) {
 			int gi = Q->ctx[u].want[w].a[k];
 			bsx_setsam_job(C->opt, C->idx, &C->reads[ri], C->roff[ri], &regs->a[gi], &Q->jobs[at]);
@@ -886,7 +931,7 @@ static void plan_free_worker(void *data, long u, int tid)
 	for (w = 0; w < Q->per; ++w) {
 		reg_v *regs = &Q->C->regs[(Q->u0 + u) * Q->per + w];
 		if (Q->ctx[u].table[w]) for (k = 0; k < regs->n; ++k) bsx_cfree(Q->ctx[u].table[w][k].cigar);
-		bsx_cfree(Q->ctx[u].table[w]); bsx_cvec_free(Q->ctx[u].want[w]);
+		bsx_cfree(Q->ctx[u].table[w]); bsx_cvec_free(Q->ctx[u].want[w]); bsx_cfree(Q->ctx[u].zn[w]);
 	}
 }
 
@@ -925,13 +970,15 @@ static int emit_sam(chunk_t *C, int u0, int u1)   /* the units (pairs, or single
 		bsx_glb_job_t *sub = round == 0 ? Q.jobs : (bsx_glb_job_t*)malloc(sizeof(*sub) * todo.n);
 		bsx_glb_res_t *sres = (bsx_glb_res_t*)malloc(sizeof(*sres) * todo.n);
 		bsx_glb_tag_t *tags = C->be->global_batch_tags ? (bsx_glb_tag_t*)malloc(sizeof(*tags) * todo.n) : 0;
+		bsx_glb_ctx_t *cx = C->bs && tags && C->be->global_batch_tags_ctx ? (bsx_glb_ctx_t*)malloc(sizeof(*cx) * todo.n) : 0;
 		size_t off = 0, nt = 0;
 		if (round == 0) off = todo.n * 8;   /* (cigar_off set with the jobs) */
 		else for (k = 0; k < todo.n; ++k) { sub[k] = Q.jobs[todo.a[k]]; sub[k].cigar_off = (uint32_t)off; off += sub[k].cigar_cap; }
 		if (off > pool_len) { pool_len = off; pool = (uint32_t*)realloc(pool, pool_len * 4 + 4); }
 		{
 			double tb = now_s();
-			rc = tags ? C->be->global_batch_tags(C->be->ctx, (int64_t)todo.n, sub, sres, pool, off, tags, &md, &md_cap)
+			rc = cx ? C->be->global_batch_tags_ctx(C->be->ctx, (int64_t)todo.n, sub, sres, pool, off, tags, &md, &md_cap, cx)
+			   : tags ? C->be->global_batch_tags(C->be->ctx, (int64_t)todo.n, sub, sres, pool, off, tags, &md, &md_cap)
 			          : C->be->global_batch(C->be->ctx, (int64_t)todo.n, sub, sres, pool, off);
 			t_batch += now_s() - tb;
 		}
@@ -939,7 +986,7 @@ static int emit_sam(chunk_t *C, int u0, int u1)   /* the units (pairs, or single
 		if (rc == BSX_OK) {
 			finish_par_t F;
 			F.C = C; F.ctx = ctx; F.per = per; F.u0 = u0; F.todo = todo.a; F.jread = Q.jread; F.jreg = Q.jreg; F.sub = sub; F.sres = sres; F.pool = pool;
-			F.tags = tags; F.md = md;
+			F.tags = tags; F.md = md; F.cx = cx;
 			bsx_parallel_for(C->nt, finish_worker, &F, (long)todo.n);
 			for (k = 0; k < todo.n; ++k) {
 				int jj = todo.a[k];
@@ -948,12 +995,19 @@ static int emit_sam(chunk_t *C, int u0, int u1)   /* the units (pairs, or single
 		}
 		todo.n = nt;
 		if (round) free(sub);
-		free(sres); free(tags);
+		free(sres); free(tags); free(cx);
 	}
 	if (rc == BSX_OK && todo.n) rc = BSX_E_INTERNAL;
 	if (bsx_phases()) fprintf(stderr, "[M::cigar] %d rounds, %.3f s in the K6 batches, %.3f s on the host\n", round, t_batch, now_s() - t0 - t_batch);
 	stat_add(&C->st.t_cigar, now_s() - t0); t0 = now_s();
+	if (rc == BSX_OK && C->bs) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].bs = &C->bs->conf; ctx[k].bs_filter = C->bs->filter; }   /* (the planning pass writes no records) */
 	if (rc == BSX_OK) { P.final_pass = 1; bsx_parallel_for(C->nt, out_worker, &P, n_units); }
+	if (rc == BSX_OK && C->bs) {
+		uint64_t t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		int i;
+		for (k = 0; k < (size_t)n_units; ++k) for (i = 0; i < 10; ++i) t[i] += ctx[k].bs_tot[i];
+		for (i = 0; i < 10; ++i) __atomic_fetch_add(&C->bs->tot[i], t[i], __ATOMIC_RELAXED);
+	}
 	/* the records own the CIGAR buffers now; release what the reference frees in mem_alnreg_freeSAM */
 	if (C->arena_set < 0) bsx_parallel_for(C->nt, plan_free_worker, &Q, n_units);   /* arena memory is rewound with the chunk */
 	stat_add(&C->st.t_sam, now_s() - t0);
@@ -1061,6 +1115,7 @@ static chunk_t *chunk_new(const bsx_backend_t *be, const bsx_opt_t *opt, const b
 	C->be_copy = *be; C->be = &C->be_copy;
 	C->opt = opt; C->idx = idx; C->n = n; C->reads = reads; C->n_processed = n_processed; C->nt = bsx_host_threads(opt);
 	C->local0 = g_next_local0; g_next_local0 = 0;
+	C->bs = g_bsconv.on ? &g_bsconv : 0;
 	C->is_pe = (opt->flag & BSX_F_PE) ? 1 : 0;
 	if (pes0) { C->pes0_copy = *pes0; C->pes0 = &C->pes0_copy; }
 	C->arena_set = -1;
@@ -1478,6 +1533,7 @@ struct bsx_stream {
 	bsx_pestat_t pes0; int has_pes0;
 	chunk_t *q[STREAM_MAX_DEPTH]; int n_q;   /* in flight, oldest first */
 	int64_t n_pushed;
+	bsconv_state_t bs;        /* bsx_stream_set_bsconv: this stream's own setting and totals (off: the process's setting applies) */
 };
 
 static int g_whole_chunk_threads = -1;   /* $BSX_STREAM_WHOLE_CHUNK=N: the chunk's own thread runs its back half too, at most N back halves at a time (0: the pushing thread runs them, one by one) */
@@ -1547,6 +1603,16 @@ BSX_API int bsx_stream_open(bsx_device_t *dev, const bsx_opt_t *opt, const bsx_i
 	return bsx_stream_open_backends(depth, b, opt, idx, pes0, out);
 }
 BSX_API int bsx_stream_depth(const bsx_stream_t *s) { return s ? s->depth : 0; }
+BSX_API int bsx_stream_set_bsconv(bsx_stream_t *s, const bsx_bsconv_conf_t *conf)
+{
+	if (!s || s->n_pushed) return BSX_E_ARG;
+	return bsconv_state_set(&s->bs, conf);
+}
+BSX_API int bsx_stream_bsconv_totals(const bsx_stream_t *s, uint64_t out[8], uint64_t *n, uint64_t *n_filtered)
+{
+	if (!s) return BSX_E_ARG;
+	return bsconv_state_totals(s->bs.on ? &s->bs : &g_bsconv, out, n, n_filtered);
+}
 
 /* wait for the chunk's front half, run its back half (its reads get their SAM text), release it */
 static int chunk_finish(chunk_t *C)
@@ -1574,6 +1640,7 @@ BSX_API int bsx_stream_push(bsx_stream_t *s, int64_t n_processed, int n, bsx_rea
 	if (n > 0) {
 		chunk_t *C = chunk_new(&s->be[s->n_pushed % s->depth], s->opt, s->idx, n_processed, n, reads, s->has_pes0 ? &s->pes0 : 0);
 		++s->n_pushed;
+		if (s->bs.on) C->bs = &s->bs;
 		/* a ticket only for the chunks that take a turn: a chunk pushed while the histogram hook is set (or without $BSX_STREAM_WHOLE_CHUNK)
 		 * never advances g_back_next, so handing it a number would leave every later ordered chunk waiting for a turn that never comes */
 		C->ordered = g_whole_chunk_threads > 0 && !bsx_pes_hist_hook;

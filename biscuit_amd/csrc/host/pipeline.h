@@ -47,7 +47,15 @@ typedef struct {
 	 * list (-1: the unmapped stand-in), index of the mate's region (-1: unmapped stand-in, -2: none), flag and mapq of the region
 	 * at that moment, is_primary */
 	int (*trace)[6]; int n_trace, m_trace;
+	/* conversion by context (bsconv while aligning; NULL: off): the setting, per region the counts of both strand hypotheses (beside table[],
+	 * filled with it), and what the final pass counted over this unit's records: the eight totals, records seen, records filtered */
+	const bsx_bsconv_conf_t *bs;
+	int bs_filter;
+	bsx_glb_ctx_t *zn[2];
+	uint32_t bs_tot[10];
 } samctx_t;
+/* is the per-record rule of `biscuit bsconv` on (any member besides annotate off its default)? */
+int bsx_bsconv_filters(const bsx_bsconv_conf_t *c);
 
 void bsx_reg2sam_se(const bsx_opt_t *opt, const bsx_index_t *idx, bsx_read_t *s, reg_v *regs, samctx_t *ctx, const char *rg_id);
 void bsx_reg2sam_pe(const bsx_opt_t *opt, const bsx_index_t *idx, uint64_t id, bsx_read_t s[2], reg_v regs[2],
@@ -57,6 +65,9 @@ void bsx_setsam_job(const bsx_opt_t *opt, const bsx_index_t *idx, const bsx_read
 /* finish a region's SAM record from the device CIGAR: MD/NM/ZC/ZR, D-squeezing, clipping, position */
 void bsx_setsam_finish(const bsx_opt_t *opt, const bsx_index_t *idx, const bsx_read_t *s, const reg_t *reg,
                        const uint32_t *cg, int n_cigar, samrec_t *out, const bsx_glb_tag_t *tag, const char *tag_md);
+/* the counts by cytosine context of both strand hypotheses over the same CIGAR, walked on the host: for a backend without
+ * global_batch_tags_ctx (include/bsx.h has the rule) */
+void bsx_setsam_ctx_host(const bsx_index_t *idx, const bsx_read_t *s, const reg_t *reg, const uint32_t *cg, int n_cigar, bsx_glb_ctx_t *out);
 
 extern char bsx_rg_id[256];
 

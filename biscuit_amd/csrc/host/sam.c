@@ -171,6 +171,57 @@ void bsx_setsam_finish(const bsx_opt_t *opt, const bsx_index_t *idx, const bsx_r
 	out->valid = 1;
 }
 
+/* ------------------------------------------------------------------ conversion by context (src/bsconv.c:63-140) */
+/* forward base at forward coordinate f, 4 when f lies outside [cb, ce) (the record's contig) or in an N hole */
+static int fwd_base_or_n(const bsx_index_t *idx, int64_t cb, int64_t ce, int64_t f)
+{
+	const bsx_amb_t *h = idx->ref.ambs;
+	int lo = 0, hi = idx->ref.n_holes;   /* the last hole that starts at or before f */
+	if (f < cb || f >= ce) return 4;
+	while (lo < hi) { int mid = (lo + hi) >> 1; if (h[mid].offset <= f) lo = mid + 1; else hi = mid; }
+	if (lo > 0 && f < h[lo - 1].offset + h[lo - 1].len) return 4;
+	return bsx_pac_get(idx->pac, f);
+}
+void bsx_setsam_ctx_host(const bsx_index_t *idx, const bsx_read_t *s, const reg_t *reg, const uint32_t *cg, int n_cigar, bsx_glb_ctx_t *out)
+{
+	const int64_t l_pac = idx->ref.l_pac, cb = idx->ref.anns[reg->rid].offset, ce = cb + idx->ref.anns[reg->rid].len;
+	const int rev = reg->rb >= l_pac;
+	const int64_t f0 = rev ? (l_pac << 1) - reg->re : reg->rb;   /* the alignment's columns ascend from here on the forward strand */
+	int c[2][5][2], k, i, x = 0, a, b;
+	int64_t y = 0;
+	memset(c, 0, sizeof(c));
+	for (k = 0; k < n_cigar; ++k) {
+		const int op = cg[k] & 0xf, len = (int)(cg[k] >> 4);
+		if (op == 0) {
+			for (i = 0; i < len; ++i) {
+				const int r = fwd_base_or_n(idx, cb, ce, f0 + y + i);
+				int q, nb;
+				if (r != 1 && r != 2) continue;
+				q = rev ? s->seq[reg->qe - 1 - (x + i)] : s->seq[reg->qb + x + i];
+				if (rev) q = q < 4 ? 3 - q : 4;
+				if (r == 1) {
+					if (q != 1 && q != 3) continue;
+					nb = fwd_base_or_n(idx, cb, ce, f0 + y + i + 1);
+					++c[0][nb][q == 3];
+				} else {
+					if (q != 2 && q != 0) continue;
+					nb = fwd_base_or_n(idx, cb, ce, f0 + y + i - 1);
+					++c[1][nb < 4 ? 3 - nb : 4][q == 0];
+				}
+			}
+			x += len; y += len;
+		} else if (op == 2) y += len;
+		else if (op == 1) x += len;
+	}
+	for (k = 0; k < 2; ++k) for (a = 0; a < 5; ++a) for (b = 0; b < 2; ++b) out->n[k][a][b] = (uint16_t)(c[k][a][b] > 65535 ? 65535 : c[k][a][b]);
+}
+
+int bsx_bsconv_filters(const bsx_bsconv_conf_t *c)
+{
+	return c && (c->filter_u || c->show_filtered || c->max_cph >= 0 || c->max_cpa >= 0 || c->max_cpc >= 0 || c->max_cpt >= 0 || c->max_cpy >= 0 ||
+	             c->max_cph_frac < 1.0f || c->max_cpy_frac < 1.0f);
+}
+
 /* ------------------------------------------------------------------ "setSAM" inside the drivers */
 typedef struct {
 	const bsx_opt_t *opt; const bsx_index_t *idx; samctx_t *ctx; const char *rg_id;
@@ -285,6 +336,61 @@ static void put_cigar(sbuf_t *str, const bsx_opt_t *opt, const reg_t *p, int is_
 	}
 }
 
+/* bsconv_func (src/bsconv.c:30-190) on the record just written into str from rec0 on (everything but the newline): counts of the strand
+ * YD names -- known only now, the mate has had its say --, the filters in float as the tool has them, ZN as the last field.  Returns 1
+ * when the record is dropped (str is cut back to rec0).  Annotate-only (no filter set) is this project's own mode: mapped records gain ZN,
+ * everything else passes untouched. */
+static int bsconv_record(drv_t *D, int which, sbuf_t *str, size_t rec0, const reg_t *p, const reg_t *p0, const reg_v *regs0)
+{
+	const bsx_bsconv_conf_t *conf = D->ctx->bs;
+	const int filter = D->ctx->bs_filter;
+	const int flag = (p->flag & 0xffff) | (p->flag & 0x10000 ? 0x100 : 0);
+	const bsx_glb_ctx_t *zn = 0;
+	int retn[5] = {0, 0, 0, 0, 0}, conv[5] = {0, 0, 0, 0, 0}, tofilter = 0, i;
+	uint32_t *tot = D->ctx->bs_tot;
+	if (!(flag & 0x4) && p->n_cigar > 0 && regs0 && p0 >= regs0->a && p0 < regs0->a + regs0->n && D->ctx->zn[which]) zn = &D->ctx->zn[which][p0 - regs0->a];
+	++tot[8];
+	if (!filter && !zn) return 0;
+	if ((flag & 0x4) || (flag & 0x200) || !zn) tofilter = 1;
+	else if (p->bss_u && conf->filter_u) tofilter = 1;
+	else {
+		int st = p->bss;
+		if (p->bss_u) { /* infer_bsstrand, bisc_utils.c:163-206, minimum base quality 0 */
+			int nC2T = 0, nG2A = 0;
+			for (i = 0; i < 5; ++i) { nC2T += zn->n[0][i][1]; nG2A += zn->n[1][i][1]; }
+			st = nC2T >= nG2A ? 0 : 1;
+		}
+		for (i = 0; i < 5; ++i) { retn[i] = zn->n[st][i][0]; conv[i] = zn->n[st][i][1]; }
+		if (filter) { /* bsconv.c:111-140 */
+			if (conf->max_cpa >= 0 && retn[0] > conf->max_cpa) tofilter = 1;
+			if (conf->max_cpc >= 0 && retn[1] > conf->max_cpc) tofilter = 1;
+			if (conf->max_cpt >= 0 && retn[3] > conf->max_cpt) tofilter = 1;
+			if (conf->max_cph >= 0 && retn[0] + retn[1] + retn[3] > conf->max_cph) tofilter = 1;
+			if (conf->max_cpy >= 0 && retn[1] + retn[3] > conf->max_cpy) tofilter = 1;
+			if (conf->max_cph_frac < 1.0) {
+				int cph_retn = retn[0] + retn[1] + retn[3], cph_conv = conv[0] + conv[1] + conv[3];
+				if (cph_retn + cph_conv > 0 && (float)cph_retn / (cph_retn + cph_conv) > conf->max_cph_frac) tofilter = 1;
+			}
+			if (conf->max_cpy_frac < 1.0) {
+				int cph_retn = retn[1] + retn[3], cph_conv = conv[1] + conv[3];
+				if (cph_retn + cph_conv > 0 && (float)cph_retn / (cph_retn + cph_conv) > conf->max_cpy_frac) tofilter = 1;
+			}
+		}
+	}
+	if (filter) {
+		if (tofilter) ++tot[9];
+		if (conf->show_filtered) tofilter = !tofilter;
+		if (tofilter) { str->l = rec0; str->s[rec0] = 0; return 1; }
+	}
+	for (i = 0; i < 4; ++i) { tot[2 * i] += (uint32_t)retn[i]; tot[2 * i + 1] += (uint32_t)conv[i]; }
+	sb_putsn(str, "\tZN:Z:", 6);
+	for (i = 0; i < 4; ++i) {
+		if (i) sb_putc(str, ',');
+		sb_putc(str, 'C'); sb_putc(str, "ACGT"[i]); sb_putsn(str, "_R", 2); sb_putw(str, retn[i]); sb_putc(str, 'C'); sb_putw(str, conv[i]);
+	}
+	return 0;
+}
+
 /* mem_alnreg_formatSAM, mem_alnreg_format.c:237-436 */
 static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const reg_t *p0, const reg_t *m0,
                        reg_v *regs0, int is_primary, const bsx_pestat_t *pes)
@@ -304,6 +410,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 		if (regs0) tag_XAXB(D, which, s, p0, regs0, str);
 		return;
 	}
+	const size_t rec0 = str->l;   /* where this record starts: a record the filters drop is taken back */
 	memset(&m, 0, sizeof(m));
 	if (m0) m = *m0;
 	p.flag |= m0 ? 0x1 : 0;
@@ -397,6 +504,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 	sb_putsn(str, "\tYD:A:", 6);
 	if (p.bss_u) sb_putc(str, 'u');
 	else sb_putc(str, "fr"[p.bss]);
+	if (D->ctx->bs && bsconv_record(D, which, str, rec0, &p, p0, regs0)) return;
 	sb_putc(str, '\n');
 }
 

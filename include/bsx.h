@@ -300,6 +300,19 @@ typedef struct bsx_glb_tag {
 } bsx_glb_tag_t;
 int bsx_global_batch_tags(bsx_device_t *dev, int64_t n, const bsx_glb_job_t *jobs, bsx_glb_res_t *res,
                           uint32_t *cigar_pool, size_t cigar_pool_len, bsx_glb_tag_t *tags, char **md, int64_t *md_cap);
+/* ... and, from the same walk, what `biscuit bsconv` (src/bsconv.c:63-109) counts over the alignment: cytosine retention / conversion by
+ * the next base, for BOTH bisulfite-strand hypotheses (the strand of a record follows from YD, which depends on the mate: the host picks).
+ * Everything is in forward-genome terms whatever the job's view: s[0] = columns whose reference base is C, bucket = the reference base after
+ * it, retained = read C, converted = read T; s[1] = columns whose reference base is G, bucket = the complement of the reference base before
+ * it, retained = read G, converted = read A.  Bucket 4 ("N"): the neighbour lies outside the contig or in an N hole of the reference
+ * (.bis.amb).  A column whose own reference base lies in a hole is counted nowhere (ZC / ZR use the randomised base of pac there).  The
+ * counters saturate at 65535.  A job's target window lies on one strand: tpos >= l_pac means a complemented view.  ctx[i] of a job without
+ * a CIGAR is all zero. */
+typedef struct bsx_glb_ctx {
+	uint16_t n[2][5][2];   /* [strand hypothesis][A, C, G, T, N context][retained, converted] */
+} bsx_glb_ctx_t;
+int bsx_global_batch_tags_ctx(bsx_device_t *dev, int64_t n, const bsx_glb_job_t *jobs, bsx_glb_res_t *res,
+                              uint32_t *cigar_pool, size_t cigar_pool_len, bsx_glb_tag_t *tags, char **md, int64_t *md_cap, bsx_glb_ctx_t *ctx);
 
 /* Settings of the library that never change its output (launch shapes, table sizes, which of two equivalent paths runs: what the tests and
  * the A/B tools switch).  One registry (csrc/host/tune.c has the table of names): bsx_tune_set(name, value) between calls of the library
@@ -404,6 +417,30 @@ int  bsx_stream_depth(const bsx_stream_t *s);
 int  bsx_stream_push(bsx_stream_t *s, int64_t n_processed, int n, bsx_read_t *reads);
 int  bsx_stream_flush(bsx_stream_t *s);
 void bsx_stream_close(bsx_stream_t *s);
+
+/* Per-read conversion by context while aligning: what `biscuit bsconv` (src/bsconv.c) does to the aligner's output in a second pass.
+ * annotate: every mapped record gains ZN:Z:CA_R<r>C<c>,CC_..,CG_..,CT_.. as its last field, nothing is dropped.  The filters: bsconv's per-record
+ * rule on top of that (unmapped and QC-fail records, and YD:u records with filter_u, are filtered; the max_* bounds as in bsconv.c:111-140, -1 and
+ * 1.0 meaning none); show_filtered keeps the filtered records instead.  A record is dropped on its own, its mate's fields are not touched.
+ * One deliberate difference from the tool: hard-clipped bases are not in SEQ and are not walked (the tool indexes past SEQ there). */
+typedef struct bsx_bsconv_conf {
+	int annotate;
+	int filter_u;
+	int show_filtered;
+	int max_cph, max_cpa, max_cpc, max_cpt, max_cpy;
+	float max_cph_frac, max_cpy_frac;
+} bsx_bsconv_conf_t;
+void bsx_bsconv_conf_init(bsx_bsconv_conf_t *conf);   /* the tool's defaults: -1 / 1.0, nothing switched on */
+/* The per-record rule is on as soon as one of its members differs from the defaults (filter_u, show_filtered, a bound >= 0, a fraction < 1.0),
+ * and implies annotate.  conf == NULL, or nothing of it set: off (the default).  The stream keeps a copy.  Call before the first push. */
+int  bsx_stream_set_bsconv(bsx_stream_t *s, const bsx_bsconv_conf_t *conf);
+/* the tool's retn_conv_counts (CpA retained, CpA converted, CpC .., CpG .., CpT ..) summed over the records written, and its two counters:
+ * records seen and records filtered */
+int  bsx_stream_bsconv_totals(const bsx_stream_t *s, uint64_t out[8], uint64_t *n, uint64_t *n_filtered);
+/* the same for bsx_process_seqs (and for any chunk processed outside a stream that has its own setting): one setting and one set of totals
+ * per process; bsx_process_bsconv_totals with reset != 0 zeroes them */
+int  bsx_process_set_bsconv(const bsx_bsconv_conf_t *conf);
+int  bsx_process_bsconv_totals(uint64_t out[8], uint64_t *n, uint64_t *n_filtered, int reset);
 
 /* `biscuit align` command line: main_align (lib/aln/align.c:319-598).  SAM on `out` (stdout). */
 int bsx_align_main(int argc, char **argv);

@@ -18,6 +18,8 @@ ap.add_argument("--profile", type=int, default=0, help="0: the clean synthetic g
 ap.add_argument("--json", action="store_true", help="one JSON line (bench.py's cli_end_to_end sub-record)")
 ap.add_argument("--threads", type=int, default=16)
 ap.add_argument("--out", default=None, help="where the SAM goes (default: a file in the work directory; /dev/null isolates the aligner from the write)")
+ap.add_argument("--align-args", default="", help="further options for biscuit_align, space separated (e.g. --bsconv)")
+ap.add_argument("--wrap", default="", help="a command to run biscuit_align under, space separated, ending in -- where it wants one (e.g. a kernel trace of the run)")
 a = ap.parse_args()
 from biscuit_amd import _lib as B
 from biscuit_amd.api import Index, Device
@@ -61,7 +63,8 @@ for n_chunks in sorted(int(x) for x in a.chunks.split(",")):
     done_at, err_lines = [], []
     t0 = time.time()
     with open(outp, "wb") as sam:
-        pr = subprocess.Popen([os.path.join(ROOT, "biscuit_amd", "biscuit_align"), "-@", str(a.threads), base, fq1, fq2], stdout=sam, stderr=subprocess.PIPE, env=env)
+        pr = subprocess.Popen(a.wrap.split() + [os.path.join(ROOT, "biscuit_amd", "biscuit_align")] + a.align_args.split() + ["-@", str(a.threads), base, fq1, fq2],
+                              stdout=sam, stderr=subprocess.PIPE, env=env)
 
         def watch():   # when each chunk's SAM is complete: the command line says so on stderr ([M::bsx_process_seqs] Processed ...)
             for line in pr.stderr:
@@ -85,7 +88,7 @@ for n_chunks in sorted(int(x) for x in a.chunks.split(",")):
     runs.append(r)
 idx.close()
 res = {"metric": "reads/s through the command line: FASTQ text in -> SAM text out (biscuit_align -@ %d <index files> r1.fq r2.fq > %s)" % (a.threads, a.out or "file"),
-       "runs": runs, "genome_mbp": a.genome_mbp, "genome_profile": "hg38-like" if a.profile else "clean", "genome_and_index_files_s": t_build,
+       "align_args": a.align_args, "runs": runs, "genome_mbp": a.genome_mbp, "genome_profile": "hg38-like" if a.profile else "clean", "genome_and_index_files_s": t_build,
        "includes": "index files -> host -> HBM, dense SA sample and table of k-mer intervals rebuilt on the device, FASTQ parse, alignment, SAM text written",
        "steady_state_is": "the time from the first chunk's SAM being complete to the last one's, per chunk (the start-up -- index load and upload, pipeline fill -- is reported beside it)"}
 best = runs[-1]
