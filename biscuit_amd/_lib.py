@@ -88,11 +88,27 @@ class GlbTag(C.Structure):
 
 class Backend(C.Structure):  # bsx_backend_t (csrc/host/bsx_core.h)
     _fields_ = [("ctx", C.c_void_p), ("name", C.c_char_p)] + [(n, C.c_void_p) for n in
-                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p)]
+                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p)]
 
 
 class GlbCtx(C.Structure):  # bsx_glb_ctx_t: [strand hypothesis][A, C, G, T, N context][retained, converted]
     _fields_ = [("n", C.c_uint16 * 20)]
+
+
+class QcJob(C.Structure):  # bsx_qc_job_t
+    _fields_ = [("fpos", C.c_int64), ("roff", C.c_uint32), ("rskip", C.c_int32), ("rlen", C.c_uint32), ("cig_off", C.c_uint32), ("n_cigar", C.c_uint32), ("flags", C.c_uint32)]
+
+
+QC_REVERSE, QC_READ2, QC_STRAND, QC_CINREAD, QC_BSCONV, QC_READ_LEN = 0x1, 0x2, 0x10, 0x20, 0x40, 301
+
+
+class QcCounts(C.Structure):  # bsx_qc_counts_t: [CpG, CpH][read][position][converted, retained], the eight totals, confusion[tag * 4 + inferred]
+    _fields_ = [("readpos", C.c_uint64 * (2 * 2 * 301 * 2)), ("conv", C.c_uint64 * 8), ("confusion", C.c_uint64 * 16)]
+
+
+class QcTotals(C.Structure):  # bsx_qc_totals_t
+    _fields_ = [("dev", QcCounts), ("mapq", C.c_uint64 * 62), ("isize", C.c_uint64 * 1001), ("n_isize", C.c_uint64), ("all_tot", C.c_uint64), ("all_dup", C.c_uint64),
+                ("q40_tot", C.c_uint64), ("q40_dup", C.c_uint64), ("strandcnt", C.c_uint64 * 16)]
 
 
 class BsconvConf(C.Structure):  # bsx_bsconv_conf_t

@@ -227,6 +227,22 @@ class Device(Batches):
             _libc_free(md)
         return res, pool, tags, out, ctx
 
+    def qc_batch(self, jobs, pool):
+        """bsx_qc_batch: the BISCUITqc column counts of the jobs (array of _lib.QcJob's layout; pool: their CIGAR words) added to the device's table"""
+        jobs = np.ascontiguousarray(jobs, dtype=np.dtype(B.QcJob))
+        pool = np.ascontiguousarray(pool, dtype=np.uint32)
+        f = B.lib().bsx_qc_batch
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t]
+        B.check(f(self.h, len(jobs), _p(jobs), _p(pool), pool.size), "bsx_qc_batch")
+
+    def qc_read(self, reset=False):
+        """bsx_qc_read -> (readpos[2, 2, 301, 2], conv[8], confusion[16]) as int64 arrays"""
+        c = B.QcCounts()
+        f = B.lib().bsx_qc_read
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        B.check(f(self.h, C.byref(c), int(reset)), "bsx_qc_read")
+        return (np.array(c.readpos, dtype=np.int64).reshape(2, 2, 301, 2), np.array(c.conv, dtype=np.int64), np.array(c.confusion, dtype=np.int64))
+
     def counters(self, reset=False):
         c = (C.c_uint64 * 4)()
         B.check(B.lib().bsx_device_counters(self.h, c, int(reset)), "bsx_device_counters")

@@ -41,6 +41,9 @@ void launch_global(hipStream_t st, const DevIndex &ix, const DevScoring &sc, con
                    long long n, bsx_glb_res_t *res, uint32_t *pool, uint8_t *zscratch, size_t zstride, int qcap, int nc, int blocks, int wpb,
                    bsx_glb_tag_t *tags = nullptr, char *md_pool = nullptr, unsigned long long md_cap = 0, unsigned long long *md_cursor = nullptr, int tcap = 0,
                    bsx_glb_ctx_t *ctx = nullptr);   // ctx != nullptr (with tags): k_global_ctx, which also fills ctx[job] (bsx_global_batch_tags_ctx)
+// k_qc.hip: the column counts of `biscuit qc` over n records (bsx_qc_job_t), added to the device's table (bsx_qc_counts_t as 64-bit cells)
+void launch_qc(hipStream_t st, const DevIndex &ix, const uint8_t *reads, long long reads_len, const bsx_qc_job_t *jobs, long long n, const uint32_t *pool,
+               unsigned long long *table, int n_cu);
 // K4 four to a wavefront (k_ext4.hip): a row of 16 lanes per job, persistent rows taking jobs off *cursor (zero at launch).
 // launch_x4: the extensions of the best seed of every chain the tiers exported (records with has_ext), written into the records ahead of
 // launch_c2r; jobs = room for job_cap jobs of x4_job_bytes(), ctr32[0..3]: job counts and cursor (zeroed by the call).

@@ -38,7 +38,7 @@ struct Lane {
 	DevBuf qpack;            // the chunk's reads as base-3 digits for the seeding kernel (k_seedt.hip)
 	int64_t rb_tasks = 0;    // strand searches of the last regions batch (their regions, offsets and counts are still in regs / regmeta)
 	int flt_key[3] = {-1, -1, -1};   // what fltab was made for
-	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, gctx, dd, sswjobs, c2rslab;
+	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, gctx, qcjobs, qcpool, dd, sswjobs, c2rslab;
 	DevBuf small;          // counters[4] | out_cursor | task_cursor | region cursors
 	HostBuf hstage;        // pinned staging for bulk results
 	HostBuf pin;           // two pinned halves through which large host<->device copies are streamed
@@ -77,6 +77,8 @@ struct bsx_device {
 	int n_cu = 0;
 	DevIndex ix; bool has_index = false;
 	DevBuf bwt[2], sa[2], pac, ctg, holes, seedtab[2];
+	DevBuf qc;   // bsx_qc_counts_t: the BISCUITqc column counts of every lane's batches (k_qc.hip), zeroed when made and by bsx_qc_read(reset)
+	std::mutex qc_mu;
 	Lane lane[BSX_LANES];   // scoring matrices and penalties are per lane (Lane::sc): chunks with different options may be in flight together
 	// Front halves of consecutive chunks are chained stage by stage (the seeding launch of chunk k+1 waits for that of chunk k, the
 	// region launches likewise): four chunks that share the device evenly all finish at the same moment, and the device then idles
@@ -173,11 +175,11 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 	(void)hipSetDevice(d->ordinal);
 	devbuf_drain(d->ordinal);   // the blocks this device's buffers left behind when they grew
 	for (int i = 0; i < 2; ++i) { d->bwt[i].release(); d->sa[i].release(); d->seedtab[i].release(); }
-	d->pac.release(); d->ctg.release(); d->holes.release();
+	d->pac.release(); d->ctg.release(); d->holes.release(); d->qc.release();
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
 		L.reads.release(); L.qpack.release(); L.gath.release(); L.jobs.release(); L.res.release(); L.scratch.release(); L.scratch2.release(); L.out.release(); L.aux.release(); L.pool.release();
-		L.small.release(); L.hstage.release(); L.regs.release(); L.regmeta.release(); L.slabs.release(); L.slabflags.release(); L.slabs3.release(); L.redo.release(); L.pin.release(); L.pos.release(); L.posoff.release(); L.xpool.release(); L.xmeta.release(); L.x4jobs.release(); L.fltab.release(); L.flt_key[0] = -1; L.tags.release(); L.mdpool.release(); L.gctx.release(); L.dd.release(); L.c2rslab.release(); L.sswjobs.release(); L.msw_jobs.release(); L.msw_res.release(); L.msw_meta.release(); L.msw_roff.release();
+		L.small.release(); L.hstage.release(); L.regs.release(); L.regmeta.release(); L.slabs.release(); L.slabflags.release(); L.slabs3.release(); L.redo.release(); L.pin.release(); L.pos.release(); L.posoff.release(); L.xpool.release(); L.xmeta.release(); L.x4jobs.release(); L.fltab.release(); L.flt_key[0] = -1; L.tags.release(); L.mdpool.release(); L.gctx.release(); L.qcjobs.release(); L.qcpool.release(); L.dd.release(); L.c2rslab.release(); L.sswjobs.release(); L.msw_jobs.release(); L.msw_res.release(); L.msw_meta.release(); L.msw_roff.release();
 		if (L.pev[0]) (void)hipEventDestroy(L.pev[0]);
 		if (L.pev[1]) (void)hipEventDestroy(L.pev[1]);
 		if (L.ev0) (void)hipEventDestroy(L.ev0);
@@ -1840,6 +1842,63 @@ extern "C" BSX_API int bsx_global_batch_tags_ctx(bsx_device_t *d, int64_t n, con
                                                  bsx_glb_tag_t *tags, char **md, int64_t *md_cap, bsx_glb_ctx_t *ctx)
 { if (!tags || !md || !md_cap || !ctx) return BSX_E_ARG; return lane_global_batch(d, 0, n, jobs, res, cigar_pool, cigar_pool_len, tags, md, md_cap, ctx); }
 
+// ------------------------------------------------------------------------------------------
+// BISCUITqc column counts (k_qc.hip)
+// ------------------------------------------------------------------------------------------
+static int qc_table(bsx_device_t *d)   // the device's table, made on first use
+{
+	std::lock_guard<std::mutex> lock(d->qc_mu);
+	if (d->qc.p) return BSX_OK;
+	int rc;
+	if ((rc = d->qc.reserve(sizeof(bsx_qc_counts_t))) != BSX_OK) return rc;
+	HIPCHK(hipMemset(d->qc.p, 0, sizeof(bsx_qc_counts_t)));
+	return BSX_OK;
+}
+static int lane_qc_batch(bsx_device_t *d, int lane, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (n == 0) return BSX_OK;
+	if (n < 0 || !jobs || (!cigar_pool && cigar_pool_len)) return BSX_E_ARG;
+	Lane &L = d->lane[lane];
+	for (int64_t i = 0; i < n; ++i) { // what the kernel indexes with must lie inside what it is given (read bases are checked one by one there)
+		const bsx_qc_job_t &j = jobs[i];
+		if ((size_t)j.cig_off + j.n_cigar > cigar_pool_len || j.rlen > (1u << 30) || j.fpos < 0 || j.fpos >= d->ix.l_pac) {
+			fprintf(stderr, "[bsx-hip] qc job %lld: invalid\n", (long long)i); return BSX_E_ARG;
+		}
+		uint64_t span = 0;
+		for (uint32_t k = 0; k < j.n_cigar; ++k) { const uint32_t c = cigar_pool[j.cig_off + k]; if ((c & 0xf) > 4) return BSX_E_ARG; span += c >> 4; }
+		if (span > (1u << 30)) return BSX_E_ARG;
+	}
+	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc;
+	if ((rc = qc_table(d)) != BSX_OK) return rc;
+	if ((rc = L.qcjobs.reserve((size_t)n * sizeof(bsx_qc_job_t))) != BSX_OK) return rc;
+	if ((rc = L.qcpool.reserve(cigar_pool_len * 4 + 64)) != BSX_OK) return rc;
+	H2D(L.st_hi, L.qcjobs.p, jobs, (size_t)n * sizeof(bsx_qc_job_t));
+	H2D(L.st_hi, L.qcpool.p, cigar_pool, cigar_pool_len * 4);
+	launch_qc(L.st_hi, d->ix, (const uint8_t*)L.reads.p, (long long)L.n_reads, (const bsx_qc_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p,
+	          (unsigned long long*)d->qc.p, d->n_cu);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(L.st_hi));   // the lane's read buffer belongs to the next chunk once the caller is done with this one
+	return BSX_OK;
+}
+static int dev_qc_read(bsx_device_t *d, bsx_qc_counts_t *out, int reset)
+{
+	if (!d || !out) return BSX_E_ARG;
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc;
+	if ((rc = qc_table(d)) != BSX_OK) return rc;
+	std::lock_guard<std::mutex> lock(d->qc_mu);
+	HIPCHK(hipDeviceSynchronize());   // every lane's batches
+	HIPCHK(hipMemcpy(out, d->qc.p, sizeof(bsx_qc_counts_t), hipMemcpyDeviceToHost));
+	if (reset) HIPCHK(hipMemset(d->qc.p, 0, sizeof(bsx_qc_counts_t)));
+	return BSX_OK;
+}
+extern "C" BSX_API int bsx_qc_batch(bsx_device_t *d, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
+{ return lane_qc_batch(d, 0, n, jobs, cigar_pool, cigar_pool_len); }
+extern "C" BSX_API int bsx_qc_read(bsx_device_t *d, bsx_qc_counts_t *out, int reset) { return dev_qc_read(d, out, reset); }
+
 // the seams as one vtable for the host pipeline; ctx = (device, lane)
 #define LR(c) ((LaneRef*)(c))->d, ((LaneRef*)(c))->lane
 static int be_set_opt(void *c, const bsx_opt_t *o) { return lane_set_opt(LR(c), o); }
@@ -1871,6 +1930,13 @@ static int be_glb_tags(void *c, int64_t n, const bsx_glb_job_t *j, bsx_glb_res_t
 static int be_glb_tags_ctx(void *c, int64_t n, const bsx_glb_job_t *j, bsx_glb_res_t *r, uint32_t *pool, size_t len, bsx_glb_tag_t *t, char **md, int64_t *cap, bsx_glb_ctx_t *x)
 { return lane_global_batch(LR(c), n, j, r, pool, len, t, md, cap, x); }
 
+static int be_qc(void *c, int64_t n, const bsx_qc_job_t *j, const uint32_t *pool, size_t len, bsx_qc_counts_t *read_out, int reset)
+{
+	int rc = lane_qc_batch(LR(c), n, j, pool, len);
+	if (rc == BSX_OK && read_out) rc = dev_qc_read(((LaneRef*)c)->d, read_out, reset);
+	return rc;
+}
+
 static LaneRef g_lane_ref[8][BSX_LANES];   // ctx storage for the vtables (by device ordinal)
 
 extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *out)
@@ -1882,7 +1948,7 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	memset(out, 0, sizeof(*out));
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
-	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx;
+	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc;
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

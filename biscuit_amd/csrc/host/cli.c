@@ -63,6 +63,9 @@ static int usage(void)
 		"              --bsconv-max-cph INT  --bsconv-max-cpa INT  --bsconv-max-cpc INT  --bsconv-max-cpt INT  --bsconv-max-cpy INT\n"
 		"              --bsconv-max-cph-frac FLOAT  --bsconv-max-cpy-frac FLOAT  --bsconv-filter-u  --bsconv-show-filtered\n"
 		"              any of these: annotate, and keep or drop each record as `biscuit bsconv` -m -a -c -t -x -f -y -u -v would\n"
+		"  qc        : --qc PREFIX  write the BISCUITqc tables of the records written, as `biscuit qc <ref> <bam> PREFIX` would: PREFIX_mapq_table.txt,\n"
+		"              _dup_report.txt, _strand_table.txt, _totalReadConversionRate.txt, _CpGRetentionByReadPos.txt, _CpHRetentionByReadPos.txt and,\n"
+		"              for paired input, _isize_table.txt\n"
 		"  device    : $BSX_DEVICE selects the HIP device ordinal (default 0)\n\n");
 	return 1;
 }
@@ -326,6 +329,19 @@ static void bsconv_report(void)
 	bsconv_print(t, n, nf);
 }
 
+/* --qc: the tables of `biscuit qc` (src/qc.c) over this call's records; with several ranks rank 0 writes the sum (bsx_align_main_ranks_with) */
+static char g_qc_prefix[4096];
+static int g_qc_paired;
+static int qc_report(void)
+{
+	bsx_qc_totals_t *t = (bsx_qc_totals_t*)malloc(sizeof(*t));
+	int rc = bsx_process_qc_totals(t, 0);
+	if (rc == BSX_OK) rc = bsx_qc_write(g_qc_prefix, t, g_qc_paired);
+	if (rc != BSX_OK) fprintf(stderr, "[E::%s] writing the QC tables failed (%s)\n", "main_align", bsx_strerror(rc));
+	free(t);
+	return rc;
+}
+
 BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void *ud, int (*open_device)(int ordinal, const bsx_index_t *idx, void **ud))
 {
 	bsx_opt_t opt_, opt0, *opt = &opt_;
@@ -343,10 +359,10 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		{"bsconv", no_argument, 0, 1000}, {"bsconv-max-cph", required_argument, 0, 1001}, {"bsconv-max-cpa", required_argument, 0, 1002},
 		{"bsconv-max-cpc", required_argument, 0, 1003}, {"bsconv-max-cpt", required_argument, 0, 1004}, {"bsconv-max-cpy", required_argument, 0, 1005},
 		{"bsconv-max-cph-frac", required_argument, 0, 1006}, {"bsconv-max-cpy-frac", required_argument, 0, 1007},
-		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {0, 0, 0, 0}
+		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {"qc", required_argument, 0, 1010}, {0, 0, 0, 0}
 	};
 	bsx_bsconv_conf_t bsconv;
-	int bsconv_on = 0;
+	int bsconv_on = 0, qc_on = 0;
 
 	bsx_bsconv_conf_init(&bsconv);
 	g_write_error = 0;   /* per call: a failed write of an earlier call in this process must not fail this one */
@@ -357,7 +373,8 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	if (argc < 2) return usage();
 	optind = 1;
 	while ((c = getopt_long(argc, argv, ":@:1:2:3:5:9ab:c:d:ef:g:hijk:m:pqr:s:v:w:x:y:z:A:B:CD:E:FG:H:I:J:K:L:MN:O:PQ:R:ST:U:VW:X:Y", long_opts, 0)) >= 0) {
-		if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
+		if (c == 1010) { qc_on = 1; snprintf(g_qc_prefix, sizeof(g_qc_prefix), "%s", optarg); }
+		else if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
 			bsconv_on = 1;
 			if (c == 1000) bsconv.annotate = 1;
 			else if (c == 1001) bsconv.max_cph = atoi(optarg);
@@ -504,6 +521,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	bsx_opt_fill_matrices(opt);
 	if (bsconv_on) bsconv.annotate = 1;   /* a filter implies the annotation */
 	bsx_process_set_bsconv(bsconv_on ? &bsconv : 0);   /* every chunk of this call, through a stream or not; totals from zero */
+	bsx_process_set_qc(qc_on);
 	if (optind >= argc) { usage(); fprintf(stderr, "Missing fai-index base\n"); return 1; }
 	if ((rc = bsx_index_load(argv[optind], &idx)) != BSX_OK) { fprintf(stderr, "[E::%s] fail to locate the index files (%s)\n", "main_align", bsx_strerror(rc)); return 1; }
 	if (auto_alt) infer_alt(&idx->ref);
@@ -704,7 +722,13 @@ loop_done:
 	if (fflush(stdout) != 0 || ferror(stdout)) g_write_error = 1;
 	if (g_write_error) { fprintf(stderr, "[E::%s] failed to write the output: the SAM is incomplete\n", "main_align"); rc = 1; }
 	if (bsconv_on && bsx_shard_world <= 1) bsconv_report();   /* (several ranks: rank 0 reports the sum, bsx_align_main_ranks_with) */
+	if (qc_on) { /* the device's counts are read while it is open; several ranks: kept for the sum */
+		g_qc_paired = (opt->flag & BSX_F_PE) ? 1 : 0;
+		if (bsx_shard_world <= 1) { if (rc == 0 && qc_report() != BSX_OK) rc = 1; }
+		else if (bsx_process_qc_totals(0, 0) != BSX_OK) rc = 1;
+	}
 cleanup:
+	if (qc_on && bsx_shard_world <= 1) bsx_process_set_qc(0);
 	if (bsconv_on && bsx_shard_world <= 1) bsx_process_set_bsconv(0);
 	if (open_device && ud && g_close_device) g_close_device(ud);   /* the device this call opened: index replica, lanes, streams */
 	free(hdr_line); free(opt->adaptor1); free(opt->adaptor2); free(pes0); free(seq1); free(seq2);
@@ -812,6 +836,19 @@ BSX_API int bsx_align_main_ranks_with(int argc, char **argv, bsx_process_fn proc
 			if (rank == 0 && v[10] > 0) { for (k = 0; k < 8; ++k) t[k] = (uint64_t)v[k]; bsconv_print(t, (uint64_t)v[8], (uint64_t)v[9]); }
 		} else if (on) { R.failed = 1; fprintf(stderr, "[E::%s] adding the conversion totals over the ranks failed\n", "main_align"); }
 		bsx_process_set_bsconv(0);
+	}
+	{ /* --qc (the same command line on every rank): the counters added up, rank 0 writes the files */
+		int k, on = 0;
+		for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--qc") == 0 || strncmp(argv[k], "--qc=", 5) == 0) on = 1;
+		if (on) {
+			bsx_qc_totals_t *t = (bsx_qc_totals_t*)malloc(sizeof(*t));
+			bsx_process_qc_totals(t, 1);
+			if (R.tg.all_reduce_sum && R.tg.all_reduce_sum(R.tg.ctx, (int64_t*)t, (int)(sizeof(*t) / 8)) == BSX_OK) {
+				if (rank == 0 && R.rc == 0 && bsx_qc_write(g_qc_prefix, t, g_qc_paired) != BSX_OK) R.failed = 1;
+			} else { R.failed = 1; fprintf(stderr, "[E::%s] adding the QC counters over the ranks failed\n", "main_align"); }
+			free(t);
+			bsx_process_set_qc(0);
+		}
 	}
 	bsx_emit_hook = 0; bsx_emit_ud = 0; bsx_pes_hist_hook = 0; bsx_pes_hist_ud = 0; bsx_shard_rank = 0; bsx_shard_world = 1; bsx_shard_mode = 0; g_ranks = 0;
 	if (R.out && R.out != stdout && fclose(R.out) != 0) R.failed = 1;

@@ -22,6 +22,7 @@
 #include "align_types.h"
 #include "tune.h"
 #include "pipeline.h"
+#include "qc.h"
 
 static double now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.tv_sec + tv.tv_usec * 1e-6; }
 
@@ -121,8 +122,27 @@ BSX_API int bsx_process_bsconv_totals(uint64_t out[8], uint64_t *n, uint64_t *n_
 	return BSX_OK;
 }
 
+/* ------------------------------------------------------------------ BISCUITqc while aligning (qc.c): setting and totals of the process (a stream has its own) */
+static bsx_qc_state_t g_qc = {0, PTHREAD_MUTEX_INITIALIZER};
+static int qc_state_totals(bsx_qc_state_t *q, bsx_qc_totals_t *out)
+{
+	int rc = bsx_qc_collect(q);
+	pthread_mutex_lock(&q->mu);
+	if (out) *out = q->tot;
+	pthread_mutex_unlock(&q->mu);
+	return rc;
+}
+BSX_API int bsx_process_set_qc(int on) { bsx_qc_state_set(&g_qc, on); return BSX_OK; }
+BSX_API int bsx_process_qc_totals(bsx_qc_totals_t *out, int reset)
+{
+	int rc = qc_state_totals(&g_qc, out);
+	if (reset) { pthread_mutex_lock(&g_qc.mu); memset(&g_qc.tot, 0, sizeof(g_qc.tot)); pthread_mutex_unlock(&g_qc.mu); }
+	return rc;
+}
+
 /* ------------------------------------------------------------------ chunk state */
 typedef struct {
+	bsx_qc_state_t *qc;  /* BISCUITqc counting for this chunk's records (NULL: off): its stream's state, else the process's */
 	bsconv_state_t *bs;  /* conversion by context for this chunk's records (NULL: off): its stream's setting, else the process's */
 	const bsx_backend_t *be;
 	const bsx_opt_t *opt;
@@ -933,6 +953,7 @@ static void plan_free_worker(void *data, long u, int tid)
 		if (Q->ctx[u].table[w]) for (k = 0; k < regs->n; ++k) bsx_cfree(Q->ctx[u].table[w][k].cigar);
 		bsx_cfree(Q->ctx[u].table[w]); bsx_cvec_free(Q->ctx[u].want[w]); bsx_cfree(Q->ctx[u].zn[w]);
 	}
+	bsx_cvec_free(Q->ctx[u].qc_recs); bsx_cvec_free(Q->ctx[u].qc_cig);
 }
 
 static pthread_mutex_t g_stat_mu = PTHREAD_MUTEX_INITIALIZER;   /* a chunk's phase times, added to by the slices of its back half */
@@ -1001,7 +1022,9 @@ static int emit_sam(chunk_t *C, int u0, int u1)   /* the units (pairs, or single
 	if (bsx_phases()) fprintf(stderr, "[M::cigar] %d rounds, %.3f s in the K6 batches, %.3f s on the host\n", round, t_batch, now_s() - t0 - t_batch);
 	stat_add(&C->st.t_cigar, now_s() - t0); t0 = now_s();
 	if (rc == BSX_OK && C->bs) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].bs = &C->bs->conf; ctx[k].bs_filter = C->bs->filter; }   /* (the planning pass writes no records) */
+	if (rc == BSX_OK && C->qc) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].qc = 1; ctx[k].qc_roff[0] = C->roff[(u0 + k) * per]; ctx[k].qc_roff[1] = C->roff[(u0 + k) * per + per - 1]; }
 	if (rc == BSX_OK) { P.final_pass = 1; bsx_parallel_for(C->nt, out_worker, &P, n_units); }
+	if (rc == BSX_OK && C->qc) rc = bsx_qc_slice(C->qc, C->be, C->idx, C->buf, (size_t)C->roff[C->n], ctx, (size_t)n_units);
 	if (rc == BSX_OK && C->bs) {
 		uint64_t t[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 		int i;
@@ -1116,6 +1139,7 @@ static chunk_t *chunk_new(const bsx_backend_t *be, const bsx_opt_t *opt, const b
 	C->opt = opt; C->idx = idx; C->n = n; C->reads = reads; C->n_processed = n_processed; C->nt = bsx_host_threads(opt);
 	C->local0 = g_next_local0; g_next_local0 = 0;
 	C->bs = g_bsconv.on ? &g_bsconv : 0;
+	C->qc = g_qc.on ? &g_qc : 0;
 	C->is_pe = (opt->flag & BSX_F_PE) ? 1 : 0;
 	if (pes0) { C->pes0_copy = *pes0; C->pes0 = &C->pes0_copy; }
 	C->arena_set = -1;
@@ -1534,6 +1558,7 @@ struct bsx_stream {
 	chunk_t *q[STREAM_MAX_DEPTH]; int n_q;   /* in flight, oldest first */
 	int64_t n_pushed;
 	bsconv_state_t bs;        /* bsx_stream_set_bsconv: this stream's own setting and totals (off: the process's setting applies) */
+	bsx_qc_state_t qc;        /* bsx_stream_set_qc: likewise */
 };
 
 static int g_whole_chunk_threads = -1;   /* $BSX_STREAM_WHOLE_CHUNK=N: the chunk's own thread runs its back half too, at most N back halves at a time (0: the pushing thread runs them, one by one) */
@@ -1613,6 +1638,17 @@ BSX_API int bsx_stream_bsconv_totals(const bsx_stream_t *s, uint64_t out[8], uin
 	if (!s) return BSX_E_ARG;
 	return bsconv_state_totals(s->bs.on ? &s->bs : &g_bsconv, out, n, n_filtered);
 }
+BSX_API int bsx_stream_set_qc(bsx_stream_t *s, int on)
+{
+	if (!s || s->n_pushed) return BSX_E_ARG;
+	bsx_qc_state_set(&s->qc, on);
+	return BSX_OK;
+}
+BSX_API int bsx_stream_qc_totals(bsx_stream_t *s, bsx_qc_totals_t *out)
+{
+	if (!s || !out) return BSX_E_ARG;
+	return qc_state_totals(s->qc.on ? &s->qc : &g_qc, out);
+}
 
 /* wait for the chunk's front half, run its back half (its reads get their SAM text), release it */
 static int chunk_finish(chunk_t *C)
@@ -1641,6 +1677,7 @@ BSX_API int bsx_stream_push(bsx_stream_t *s, int64_t n_processed, int n, bsx_rea
 		chunk_t *C = chunk_new(&s->be[s->n_pushed % s->depth], s->opt, s->idx, n_processed, n, reads, s->has_pes0 ? &s->pes0 : 0);
 		++s->n_pushed;
 		if (s->bs.on) C->bs = &s->bs;
+		if (s->qc.on) C->qc = &s->qc;
 		/* a ticket only for the chunks that take a turn: a chunk pushed while the histogram hook is set (or without $BSX_STREAM_WHOLE_CHUNK)
 		 * never advances g_back_next, so handing it a number would leave every later ordered chunk waiting for a turn that never comes */
 		C->ordered = g_whole_chunk_threads > 0 && !bsx_pes_hist_hook;

@@ -38,6 +38,16 @@ typedef struct {
 	uint32_t *cigar;          /* ops + MD text, malloc'd */
 } samrec_t;
 
+/* one written record as the final pass notes it (BISCUITqc while aligning, qc.c): the fields the host counts, and the device's job when the record is mapped */
+typedef struct {
+	bsx_qc_job_t job;     /* cig_off: into the unit's own CIGAR words */
+	int32_t tlen;
+	uint16_t flag;
+	uint8_t mapq, mapped;
+} bsx_qc_rec_t;
+typedef BSX_VEC(bsx_qc_rec_t) bsx_qc_rec_v;
+typedef BSX_VEC(uint32_t) bsx_qc_cig_v;
+
 typedef struct {
 	/* plan mode: collect the regions whose CIGAR will be needed instead of formatting */
 	int plan;
@@ -53,6 +63,11 @@ typedef struct {
 	int bs_filter;
 	bsx_glb_ctx_t *zn[2];
 	uint32_t bs_tot[10];
+	/* BISCUITqc while aligning (0: off): where the unit's reads lie in the chunk's read buffer, and what the final pass wrote */
+	int qc;
+	uint32_t qc_roff[2];
+	bsx_qc_rec_v qc_recs;
+	bsx_qc_cig_v qc_cig;
 } samctx_t;
 /* is the per-record rule of `biscuit bsconv` on (any member besides annotate off its default)? */
 int bsx_bsconv_filters(const bsx_bsconv_conf_t *c);

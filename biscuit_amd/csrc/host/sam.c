@@ -391,6 +391,29 @@ static int bsconv_record(drv_t *D, int which, sbuf_t *str, size_t rec0, const re
 	return 0;
 }
 
+/* BISCUITqc while aligning: note the record just written for the slice's count (qc.c) -- the fields process_qc (src/qc.c:125-160) looks at and,
+ * for a mapped record, the job of the column counts: the read where the chunk's read buffer has it, the CIGAR as printed (S or H alike) */
+static void qc_record(drv_t *D, int which, const bsx_read_t *s, const reg_t *p, int64_t tlen)
+{
+	const int flag = (p->flag & 0xffff) | (p->flag & 0x10000 ? 0x100 : 0), mapq = p->rid >= 0 ? (int)p->mapq : 0;
+	bsx_qc_rec_t r;
+	int k;
+	memset(&r, 0, sizeof(r));
+	r.flag = (uint16_t)flag; r.mapq = (uint8_t)(mapq > 255 ? 255 : mapq < 0 ? 0 : mapq);
+	r.tlen = tlen > 0x7fffffff ? 0x7fffffff : tlen < -0x7fffffff ? -0x7fffffff : (int32_t)tlen;
+	r.mapped = !(flag & 0x4) && p->rid >= 0 && p->n_cigar > 0;
+	if (r.mapped) {
+		r.job.fpos = D->idx->ref.anns[p->rid].offset + p->pos;
+		r.job.roff = D->ctx->qc_roff[which]; r.job.rskip = s->clip5; r.job.rlen = (uint32_t)s->l_seq0;
+		r.job.cig_off = (uint32_t)D->ctx->qc_cig.n; r.job.n_cigar = (uint32_t)p->n_cigar;
+		r.job.flags = (flag & 0x10 ? BSX_QC_REVERSE : 0) | (flag & 0x80 ? BSX_QC_READ2 : 0) | (uint32_t)(p->bss_u ? 3 : p->bss ? 1 : 0) << 2 | BSX_QC_STRAND;
+		if (mapq >= 40 && !(flag & 0x100)) r.job.flags |= BSX_QC_CINREAD;
+		if (mapq >= 40 && !(flag & 0x100) && !(flag & 0x400) && !(flag & 0x200) && (flag & 0x1) && (flag & 0x2)) r.job.flags |= BSX_QC_BSCONV;
+		for (k = 0; k < p->n_cigar; ++k) bsx_cvec_push(D->ctx->qc_cig, p->cigar[k]);
+	}
+	bsx_cvec_push(D->ctx->qc_recs, r);
+}
+
 /* mem_alnreg_formatSAM, mem_alnreg_format.c:237-436 */
 static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const reg_t *p0, const reg_t *m0,
                        reg_v *regs0, int is_primary, const bsx_pestat_t *pes)
@@ -398,6 +421,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 	const bsx_opt_t *opt = D->opt;
 	const bsx_refmeta_t *ref = &D->idx->ref;
 	reg_t p = *p0, m;
+	int64_t tlen = 0;   /* as written */
 	int i;
 	if (D->ctx->plan) { /* planning only needs the side effects on CIGAR availability */
 		if (D->ctx->trace && D->ctx->n_trace < D->ctx->m_trace) {
@@ -442,7 +466,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 			int64_t q0 = -1, q1 = -1;
 			if (p.is_rev) q1 = p.pos + get_rlen(p.n_cigar, p.cigar) - 1; else q0 = p.pos;
 			if (m.is_rev) q1 = m.pos + get_rlen(m.n_cigar, m.cigar) - 1; else q0 = m.pos;
-			if (p.n_cigar > 0 && m.n_cigar > 0 && q0 >= 0 && q1 >= 0) sb_putl(str, q1 - q0 + 1);
+			if (p.n_cigar > 0 && m.n_cigar > 0 && q0 >= 0 && q1 >= 0) { tlen = q1 - q0 + 1; sb_putl(str, tlen); }
 			else sb_putc(str, '0');
 		} else sb_putc(str, '0');
 	} else sb_putsn(str, "*\t0\t0", 5);
@@ -505,6 +529,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 	if (p.bss_u) sb_putc(str, 'u');
 	else sb_putc(str, "fr"[p.bss]);
 	if (D->ctx->bs && bsconv_record(D, which, str, rec0, &p, p0, regs0)) return;
+	if (D->ctx->qc) qc_record(D, which, s, &p, tlen);
 	sb_putc(str, '\n');
 }
 

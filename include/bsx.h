@@ -314,6 +314,40 @@ typedef struct bsx_glb_ctx {
 int bsx_global_batch_tags_ctx(bsx_device_t *dev, int64_t n, const bsx_glb_job_t *jobs, bsx_glb_res_t *res,
                               uint32_t *cigar_pool, size_t cigar_pool_len, bsx_glb_tag_t *tags, char **md, int64_t *md_cap, bsx_glb_ctx_t *ctx);
 
+/* BISCUITqc counts over written records (k_qc.hip): what `biscuit qc` (src/qc.c:112-179) has bsstrand_func, cinread_func (targets CG and CH) and
+ * bsconv_func count column by column, one job per mapped record, accumulated in a table that stays on the device.
+ * A job is the record as the SAM has it: fpos = forward coordinate (concatenated contigs) of the first aligned column; the read as it lies in the
+ * resident read buffer (bsx_device_set_reads), in sequencing orientation: its first stored base at roff, rskip bases of the whole read before the
+ * stored ones (bases clipped off before alignment), rlen = the whole read's length; the record's final CIGAR, S and H included, in reference order,
+ * n_cigar words (len << 4 | op, op 0..4 = MIDSH) at cig_off of the pool.  A reverse record reads the complement of the read from its far end.
+ * Read positions are in whole-read coordinates (S and H both advance them): 0-based from the read's first base on a forward record, rlen - qpos
+ * on a reverse one; positions >= 301 are not counted.  Reference columns in an N hole count nowhere; a neighbour in a hole or beyond the contig
+ * end is "not G". */
+#define BSX_QC_REVERSE  0x1    /* flag 0x10 */
+#define BSX_QC_READ2    0x2    /* flag 0x80 */
+#define BSX_QC_TAG(f)   (((f) >> 2) & 3)   /* YD: 0 = f, 1 = r, 3 = u */
+#define BSX_QC_STRAND   0x10   /* count confusion[tag * 4 + inferred] (bsstrand.c:115-135; inferred: 0 f, 1 r, 2 conflict, 3 unknown) */
+#define BSX_QC_CINREAD  0x20   /* count both read-position tables (MAPQ >= 40, not secondary) */
+#define BSX_QC_BSCONV   0x40   /* count the eight conversion totals (not secondary, paired, proper, MAPQ >= 40) */
+#define BSX_QC_READ_LEN 301
+typedef struct bsx_qc_job {
+	int64_t fpos;
+	uint32_t roff;
+	int32_t rskip;
+	uint32_t rlen;
+	uint32_t cig_off, n_cigar;
+	uint32_t flags;
+} bsx_qc_job_t;
+typedef struct bsx_qc_counts {   /* the device's table, one POD */
+	uint64_t readpos[2][2][BSX_QC_READ_LEN][2];   /* [CpG, CpH][read 1, read 2][position][converted, retained] */
+	uint64_t conv[8];                             /* CpA retained, CpA converted, CpC .., CpG .., CpT .. (bsconv's retn_conv_counts) */
+	uint64_t confusion[16];                       /* [YD tag * 4 + inferred] */
+} bsx_qc_counts_t;
+/* adds the jobs' counts to the device's table (exact integer sums: the order of jobs and the split into batches do not matter) */
+int bsx_qc_batch(bsx_device_t *dev, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len);
+/* waits for the batches in flight and copies the table out; reset != 0 zeroes it */
+int bsx_qc_read(bsx_device_t *dev, bsx_qc_counts_t *out, int reset);
+
 /* Settings of the library that never change its output (launch shapes, table sizes, which of two equivalent paths runs: what the tests and
  * the A/B tools switch).  One registry (csrc/host/tune.c has the table of names): bsx_tune_set(name, value) between calls of the library
  * (value NULL: back to the default; BSX_E_ARG for an unknown name), or "$BSX_TUNE=name=value,name=value" for a whole process.  bsx_phases():
@@ -441,6 +475,30 @@ int  bsx_stream_bsconv_totals(const bsx_stream_t *s, uint64_t out[8], uint64_t *
  * per process; bsx_process_bsconv_totals with reset != 0 zeroes them */
 int  bsx_process_set_bsconv(const bsx_bsconv_conf_t *conf);
 int  bsx_process_bsconv_totals(uint64_t out[8], uint64_t *n, uint64_t *n_filtered, int reset);
+
+/* The BISCUITqc tables while aligning: what `biscuit qc <ref> <bam> PREFIX` (src/qc.c) would count over the SAM written, a record at a time
+ * as it is written (after bsconv's filters: a dropped record is not counted).  Record fields are counted on the host, columns on the device
+ * (bsx_qc_batch; a backend without it walks them on the host).  Differences from the tool: hard-clipped bases count towards the read position
+ * and are never indexed into SEQ; position 301 is dropped with those beyond it; 64-bit counters. */
+#define BSX_QC_N_MAPQ 61
+#define BSX_QC_ISIZE  1000
+typedef struct bsx_qc_totals {
+	bsx_qc_counts_t dev;                    /* the column counts */
+	uint64_t mapq[BSX_QC_N_MAPQ + 1];       /* non-secondary records by MAPQ; [61]: unmapped */
+	uint64_t isize[BSX_QC_ISIZE + 1];       /* proper pair, MAPQ >= 40, 0 <= TLEN <= 1000, non-secondary */
+	uint64_t n_isize;
+	uint64_t all_tot, all_dup, q40_tot, q40_dup;   /* the two duplicate counts stay 0: no record carries 0x400 */
+	uint64_t strandcnt[16];                 /* [(no 0x40) * 8 + reverse * 4 + YD tag] over mapped records */
+} bsx_qc_totals_t;
+/* on != 0: count from the next chunk on, totals from zero.  A stream's own setting takes its chunks out of the process's.  The device's table
+ * is one per device: one stream (or the process) at a time counts on a device.  Call before the first push. */
+int  bsx_stream_set_qc(bsx_stream_t *s, int on);
+int  bsx_stream_qc_totals(bsx_stream_t *s, bsx_qc_totals_t *out);   /* after bsx_stream_flush */
+int  bsx_process_set_qc(int on);
+int  bsx_process_qc_totals(bsx_qc_totals_t *out, int reset);        /* while the devices the chunks ran on are still open */
+/* PREFIX_mapq_table.txt, _dup_report.txt, _strand_table.txt, _totalReadConversionRate.txt, _CpGRetentionByReadPos.txt, _CpHRetentionByReadPos.txt
+ * and, with paired != 0, _isize_table.txt: the formatters of src/qc.c:29-110, byte for byte */
+int  bsx_qc_write(const char *prefix, const bsx_qc_totals_t *t, int paired);
 
 /* `biscuit align` command line: main_align (lib/aln/align.c:319-598).  SAM on `out` (stdout). */
 int bsx_align_main(int argc, char **argv);
