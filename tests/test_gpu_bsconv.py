@@ -68,6 +68,24 @@ def test_kernel_counts_equal_the_model_job_by_job(data):
                 read = simdata.revcomp(simdata.mutate(simdata.bisulfite(simdata.revcomp(src), r, cpg_ret=0.6, other_ret=0.05), r, 0.02, 0.0))
             seqs.append(read.astype(np.uint8))
             meta.append((ci, s, L, back))
+        # three reads of 16 400 - 17 000 bases behind them (a stream of their own, so that the jobs above stay what they were): the DP rows of
+        # these live in HBM (launch_global_hbm, its ctx form).  Both strands, one of them walked against the forward direction
+        LONG = [(False, False), (True, False), (False, True)]      # (from the reverse strand, reversed view)
+        n_short = len(seqs)
+        r2 = np.random.default_rng(7717)
+        for back, _ in LONG:
+            while True:
+                ci = int(r2.integers(0, len(contigs)))
+                g = contigs[ci][1]
+                L = int(r2.integers(16400, 17001))
+                s = int(r2.integers(0, len(g) - L))
+                if (g[s:s + L] == 4).sum() < 30:                   # short N runs only
+                    break
+            f = g[s:s + L].copy()
+            src = simdata.revcomp(f) if back else f
+            read = simdata.mutate(simdata.bisulfite(src, r2, cpg_ret=0.6, other_ret=0.05), r2, 0.02, 0.002)
+            seqs.append(read.astype(np.uint8))
+            meta.append((ci, s, L, back))
         buf, offs = simdata.read_buffer(seqs)
         opt = default_opt()
         dev.set_opt(opt)
@@ -78,20 +96,22 @@ def test_kernel_counts_equal_the_model_job_by_job(data):
             q = len(seqs[k])
             fs = int(offs_c[ci]) + s                              # forward coordinate of the window's first base
             flip = bool(r.random() < 0.25)                        # the view walks the window against the forward direction
+            if k >= n_short:
+                flip = LONG[k - n_short][1]
             if not back:
                 tpos, tdir, qoff, qdir = (fs, 1, offs[k], 1) if not flip else (fs + L - 1, -1, offs[k] + q - 1, -1)
             else:                                                 # the reverse strand's coordinates: [2 l_pac - (fs + L), 2 l_pac - fs)
                 rb, re = 2 * l_pac - (fs + L), 2 * l_pac - fs
                 tpos, tdir, qoff, qdir = (re - 1, -1, offs[k] + q - 1, -1) if not flip else (rb, 1, offs[k], 1)
             cap = 64 + q // 8
-            jobs[k] = (tpos, qoff, q, L, 60, 400, 0, 1, at, cap, qdir, tdir, int(r.integers(0, 2)), 1)
+            jobs[k] = (tpos, qoff, q, L, 60 if k < n_short else max(100, abs(L - q) + 3), 400, 0, 1, at, cap, qdir, tdir, int(r.integers(0, 2)), 1)
             at += cap
         res, pool, tags, md, ctx = dev.global_tags_ctx(jobs, at)
         res2, pool2, tags2, md2 = dev.global_tags(jobs, at)
         assert (res == res2).all() and (pool == pool2).all() and md == md2
         for name in ("NM", "ZC", "ZR", "l_md", "bss_u"):
             assert (tags[name] == tags2[name]).all(), name
-        n_checked = n_special = n_onelane = n_indel = 0
+        n_checked = n_special = n_onelane = n_indel = n_hbm = 0
         seen = np.zeros((2, 5, 2), np.int64)
         for k, (ci, s, L, back) in enumerate(meta):
             n_c = int(res[k]["n_cigar"])
@@ -113,8 +133,12 @@ def test_kernel_counts_equal_the_model_job_by_job(data):
             g = contigs[ci][1]
             n_special += int(s == 0 or s + L == len(g) or (g[max(0, s - 1):s + L + 1] == 4).any())
             n_onelane += int(q > 1024)
+            n_hbm += int(q > 16384)
             n_indel += int(any(o[1] in "ID" for o in ops))
         assert n_checked >= 2000 and n_special > 300 and n_onelane >= 20
+        assert n_hbm == 3 and n_checked == n_short + 3 and all(16400 <= len(x) <= 17000 for x in seqs[n_short:])
+        long_jobs = jobs[n_short:]
+        assert {int(j["tpos"]) >= l_pac for j in long_jobs} == {False, True} and (long_jobs["tdir"] < 0).any() and (long_jobs["tdir"] > 0).any()
         assert (seen[:, :4] > 50).all() and (seen[:, 4] > 0).all()      # every bucket of both strands is exercised, the N bucket too
         assert len({(int(j["qdir"]), int(j["tpos"]) >= l_pac) for j in jobs}) == 4      # both directions on both strands
         assert n_indel > 200

@@ -360,6 +360,63 @@ def test_sw_matches_oracle(small_index, port, device):
     assert (pr["score"] > 60).sum() > 100 and (pr["score2"] > 0).sum() > 5 and (pr["qb"] >= 0).sum() > 100
 
 
+def _check_tags(small_index, buf, jobs, dr, dp, tags, mds):
+    """the second half of bis_bwa_gen_cigar2 (lib/aln/bwa.c:342-418) restated: NM, MD, ZC, ZR and bss_u of every job from its CIGAR (dr, dp), against
+    what the device returned (tags, mds).  Returns (jobs checked, conversions seen, deletions written into an MD)."""
+    l_pac = small_index.l_pac
+    pac = np.fromfile(small_index.base + ".bis.pac", dtype=np.uint8)
+    ii = np.arange(l_pac)
+    fwd = ((pac[ii >> 2] >> ((~ii & 3) << 1)) & 3).astype(np.uint8)
+    both = np.concatenate([fwd, 3 - fwd[::-1]])      # the forward-reverse coordinate space
+    n_checked = n_conv = n_del = 0
+    for k in range(len(jobs)):
+        J = jobs[k]
+        n = int(dr[k]["n_cigar"])
+        if not J["want_cigar"] or n <= 0:
+            assert mds[k] is None
+            continue
+        o = int(J["cigar_off"])
+        q = buf[int(J["qoff"]) + int(J["qdir"]) * np.arange(int(J["qlen"]))].tolist()
+        t = both[int(J["tpos"]) + int(J["tdir"]) * np.arange(int(J["tlen"]))].tolist()
+        int2base = "TGCAN" if J["tdir"] < 0 else "ACGTN"     # bwa.c:345: the forward-strand base of a reversed alignment
+        parent = int(J["use_ct"])
+        x = y = u = n_mm = n_gap = zc = zr = 0
+        md = []
+        for c in range(n):
+            op, ln = int(dp[o + c]) & 0xf, int(dp[o + c]) >> 4
+            if op == 0:
+                for i in range(ln):
+                    a, b = q[x + i], t[y + i]
+                    if a == b:
+                        zr += (a == 1) if parent else (a == 2)
+                        u += 1
+                    else:
+                        md.append("%d%s" % (u, int2base[b]))
+                        u = 0
+                        if (parent and a == 3 and b == 1) or (not parent and a == 0 and b == 2):
+                            zc += 1
+                        else:
+                            n_mm += 1
+                x += ln
+                y += ln
+            elif op == 2:
+                if 0 < c < n - 1:
+                    md.append("%d^%s" % (u, "".join(int2base[b] for b in t[y:y + ln])))
+                    u = 0
+                    n_gap += ln
+                    n_del += 1
+                y += ln
+            elif op == 1:
+                x += ln
+                n_gap += ln
+        md.append("%d" % u)
+        assert mds[k] == "".join(md).encode() + b"\0", (k, mds[k][:200], "".join(md)[:200])
+        assert (int(tags[k]["NM"]), int(tags[k]["ZC"]), int(tags[k]["ZR"]), int(tags[k]["bss_u"])) == (n_mm + n_gap, zc, zr, int(zc == 0)), k
+        n_checked += 1
+        n_conv += zc
+    return n_checked, n_conv, n_del
+
+
 def test_global_matches_oracle(small_index, port, device):
     from biscuit_amd.api import GLB_DT
     opt = default_opt()
@@ -409,59 +466,7 @@ def test_global_matches_oracle(small_index, port, device):
     # restatement of that loop written here (the CIGARs were just shown to be the checker's)
     tr, tp, tags, mds = device.global_tags(jobs, cig_off)
     assert (tr == dr).all() and (tp == dp).all()
-    pac = np.fromfile(small_index.base + ".bis.pac", dtype=np.uint8)
-
-    def ref_base(p):
-        if p >= l_pac:
-            p = 2 * l_pac - 1 - p
-            return 3 - int((pac[p >> 2] >> ((~p & 3) << 1)) & 3)
-        return int((pac[p >> 2] >> ((~p & 3) << 1)) & 3)
-    n_checked = n_conv = n_del = 0
-    for k in range(len(jobs)):
-        J = jobs[k]
-        n = int(dr[k]["n_cigar"])
-        if not J["want_cigar"] or n <= 0:
-            assert mds[k] is None
-            continue
-        o = int(J["cigar_off"])
-        q = [int(buf[int(J["qoff"]) + i * int(J["qdir"])]) for i in range(int(J["qlen"]))]
-        t = [ref_base(int(J["tpos"]) + i * int(J["tdir"])) for i in range(int(J["tlen"]))]
-        int2base = "TGCAN" if J["tdir"] < 0 else "ACGTN"     # bwa.c:345: the forward-strand base of a reversed alignment
-        parent = int(J["use_ct"])
-        x = y = u = n_mm = n_gap = zc = zr = 0
-        md = ""
-        for c in range(n):
-            op, ln = int(dp[o + c]) & 0xf, int(dp[o + c]) >> 4
-            if op == 0:
-                for i in range(ln):
-                    a, b = q[x + i], t[y + i]
-                    if a == b:
-                        zr += (a == 1) if parent else (a == 2)
-                        u += 1
-                    else:
-                        md += "%d%s" % (u, int2base[b])
-                        u = 0
-                        if (parent and a == 3 and b == 1) or (not parent and a == 0 and b == 2):
-                            zc += 1
-                        else:
-                            n_mm += 1
-                x += ln
-                y += ln
-            elif op == 2:
-                if 0 < c < n - 1:
-                    md += "%d^%s" % (u, "".join(int2base[b] for b in t[y:y + ln]))
-                    u = 0
-                    n_gap += ln
-                    n_del += 1
-                y += ln
-            elif op == 1:
-                x += ln
-                n_gap += ln
-        md += "%d" % u
-        assert mds[k] == md.encode() + b"\0", (k, mds[k], md)
-        assert (int(tags[k]["NM"]), int(tags[k]["ZC"]), int(tags[k]["ZR"]), int(tags[k]["bss_u"])) == (n_mm + n_gap, zc, zr, int(zc == 0)), k
-        n_checked += 1
-        n_conv += zc
+    n_checked, n_conv, n_del = _check_tags(small_index, buf, jobs, dr, dp, tags, mds)
     assert n_checked > 250 and n_conv > 1000 and n_del > 5
 
 
@@ -528,6 +533,9 @@ def test_oversize_jobs_take_the_large_classes(small_index, port, device):
         assert n > 0 and (pp[o:o + n] == tp[o:o + n]).all(), k
     dr, dp = device.global_(gj, cig_off)
     assert (dr == pr).all()
+    # NM, MD, ZC, ZR, bss_u of the same jobs -- the ones with their rows in HBM walk their MD from HBM as well -- against the restated loop
+    n_checked, n_conv, n_del = _check_tags(small_index, buf, gj, tr, tp, tags, mds)
+    assert n_checked == len(gj) and n_conv > 1000 and n_del > 5, (n_checked, n_conv, n_del)
     # ---- local alignment: queries of 2500 bases (mate rescue of long paired reads)
     sj = []
     for r in range(len(big), len(big) + len(mid)):

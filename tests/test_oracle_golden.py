@@ -105,31 +105,48 @@ def test_btree_lookup_and_order(V):
         L.bsx_bt_free(t)
 
 
-def test_extend_sw_global_vs_reference_vectors(V, PL):
-    qo, to = V["ext_qoff"], V["ext_toff"]
-    for i, (par, want) in enumerate(zip(V["ext_par"], V["ext_out"])):
+def _dp_vs_recorded(V, F, PL, p=""):
+    """oracle_extend1 / oracle_sw1 / oracle_global1 over every recorded vector of F (key prefix p), exact; returns the three counts"""
+    qo, to = F[p + "ext_qoff"], F[p + "ext_toff"]
+    for i, (par, want) in enumerate(zip(F[p + "ext_par"], F[p + "ext_out"])):
         a, b, which, od, ed, oi, ei, w, eb, zd, h0 = [int(x) for x in par]
-        q = np.ascontiguousarray(V["ext_q"][qo[i]:qo[i + 1]]); t = np.ascontiguousarray(V["ext_t"][to[i]:to[i + 1]])
+        q = np.ascontiguousarray(F[p + "ext_q"][qo[i]:qo[i + 1]]); t = np.ascontiguousarray(F[p + "ext_t"][to[i]:to[i + 1]])
         M = _mat(V, a, b, which)
         o = (C.c_int * 6)()
         PL.oracle_extend1(len(q), P(q, u8p), len(t), P(t, u8p), P(M, i8p), od, ed, oi, ei, w, eb, zd, h0, o)
-        assert list(o) == list(want), i
-    qo, to = V["sw_qoff"], V["sw_toff"]
-    for i, (par, want) in enumerate(zip(V["sw_par"], V["sw_out"])):
+        assert list(o) == list(want), (i, list(par))
+    qo, to = F[p + "sw_qoff"], F[p + "sw_toff"]
+    for i, (par, want) in enumerate(zip(F[p + "sw_par"], F[p + "sw_out"])):
         a, b, which, od, ed, oi, ei, xtra = [int(x) for x in par]
-        q = V["sw_q"][qo[i]:qo[i + 1]].copy(); t = V["sw_t"][to[i]:to[i + 1]].copy()
+        q = F[p + "sw_q"][qo[i]:qo[i + 1]].copy(); t = F[p + "sw_t"][to[i]:to[i + 1]].copy()
         M = _mat(V, a, b, which)
         o = (C.c_int * 7)()
         PL.oracle_sw1(len(q), P(q, u8p), len(t), P(t, u8p), P(M, i8p), od, ed, oi, ei, xtra, o)
         assert list(o) == list(want), (i, hex(xtra))
-    qo, to, co = V["gl_qoff"], V["gl_toff"], V["gl_coff"]
-    for i, par in enumerate(V["gl_par"]):
+    qo, to, co = F[p + "gl_qoff"], F[p + "gl_toff"], F[p + "gl_coff"]
+    cap = int(np.diff(co).max()) + 2048
+    for i, par in enumerate(F[p + "gl_par"]):
         a, b, which, od, ed, oi, ei, w, wc = [int(x) for x in par]
-        q = np.ascontiguousarray(V["gl_q"][qo[i]:qo[i + 1]]); t = np.ascontiguousarray(V["gl_t"][to[i]:to[i + 1]])
+        q = np.ascontiguousarray(F[p + "gl_q"][qo[i]:qo[i + 1]]); t = np.ascontiguousarray(F[p + "gl_t"][to[i]:to[i + 1]])
         M = _mat(V, a, b, which)
-        cg = (C.c_uint32 * 2048)(); n = C.c_int()
-        s = PL.oracle_global1(len(q), P(q, u8p), len(t), P(t, u8p), P(M, i8p), od, ed, oi, ei, w, wc, C.byref(n), cg, 2048)
-        assert s == int(V["gl_score"][i]) and list(cg[:n.value]) == list(V["gl_cigar"][co[i]:co[i + 1]]), i
+        cg = (C.c_uint32 * cap)(); n = C.c_int()
+        s = PL.oracle_global1(len(q), P(q, u8p), len(t), P(t, u8p), P(M, i8p), od, ed, oi, ei, w, wc, C.byref(n), cg, cap)
+        assert s == int(F[p + "gl_score"][i]) and list(cg[:n.value]) == list(F[p + "gl_cigar"][co[i]:co[i + 1]]), i
+    return len(F[p + "ext_par"]), len(F[p + "sw_par"]), len(F[p + "gl_par"])
+
+
+def test_extend_sw_global_vs_reference_vectors(V, PL):
+    _dp_vs_recorded(V, V, PL)
+
+
+def test_extend_sw_global_vs_long_reference_vectors(V, PL):
+    """the checker at the shapes of ref_vectors_long.npz (tests/golden/make_vectors_long.py): queries of up to 17 kb, bands of up to 2001
+    columns, byte-mode local alignment that reaches 255.  Every vector, exact: what pins port.c -- and with it the port-based GPU tests --
+    to the reference's ksw.c at the lengths where the device changes kernel."""
+    VL = np.load(os.path.join(HERE, "golden", "ref_vectors_long.npz"))
+    assert _dp_vs_recorded(V, VL, PL, "l") == (403, 118, 114)
+    sat = VL["lsw_out"][:, 0] == 255
+    assert sat.sum() == 10 and (VL["lsw_par"][sat, 7] & 0x10000).all()      # byte mode that saturated: recorded as the reference answers it
 
 
 @pytest.fixture(scope="module")
