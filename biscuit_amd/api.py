@@ -186,6 +186,41 @@ class Device(Batches):
                 _libc_free(ptr)
         return regs, off[:n], cnt[:n]
 
+    def put_regions(self, regs, off, cnt):
+        """bsx_hook_regions_put (tests): regions, offsets and counts of strand searches put where a regions batch leaves its own"""
+        regs = np.ascontiguousarray(regs, dtype=np.dtype(B.Region))
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        cnt = np.ascontiguousarray(cnt, dtype=np.int32)
+        assert len(off) == len(cnt)
+        f = B.lib().bsx_hook_regions_put
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        B.check(f(self.h, len(cnt), _p(regs), len(regs), _p(off), _p(cnt)), "bsx_hook_regions_put")
+
+    def dedup(self, opt, n_reads, per_read):
+        """bsx_regions_dedup -> (out_n[n_reads], out_idx[n_reads, bsx_regions_dedup_cap()])"""
+        L = B.lib()
+        cap = L.bsx_regions_dedup_cap()
+        out_n = np.zeros(max(1, n_reads), dtype=np.int32)
+        out_idx = np.zeros((max(1, n_reads), cap), dtype=np.uint8)
+        L.bsx_regions_dedup.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+        B.check(L.bsx_regions_dedup(self.h, C.byref(opt), n_reads, per_read, _p(out_n), _p(out_idx)), "bsx_regions_dedup")
+        return out_n[:n_reads], out_idx[:n_reads]
+
+    def dedup2(self, opt, n_reads, per_read):
+        """bsx_regions_dedup2 -> (out_n, out_idx, long_off[n_reads], pool of 16-bit indices the offsets point into)"""
+        L = B.lib()
+        cap = L.bsx_regions_dedup_cap()
+        out_n = np.zeros(max(1, n_reads), dtype=np.int32)
+        out_idx = np.zeros((max(1, n_reads), cap), dtype=np.uint8)
+        long_off = np.zeros(max(1, n_reads), dtype=np.int64)
+        pool, pool_cap = C.c_void_p(), C.c_int64(0)
+        L.bsx_regions_dedup2.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+        B.check(L.bsx_regions_dedup2(self.h, C.byref(opt), n_reads, per_read, _p(out_n), _p(out_idx), _p(long_off), C.byref(pool), C.byref(pool_cap)), "bsx_regions_dedup2")
+        arr = np.frombuffer(C.string_at(pool.value, pool_cap.value * 2), dtype=np.uint16).copy() if pool.value and pool_cap.value else np.zeros(0, dtype=np.uint16)
+        if pool.value:
+            _libc_free(pool)
+        return out_n[:n_reads], out_idx[:n_reads], long_off[:n_reads], arr
+
     def global_tags(self, jobs, pool_len):
         """bsx_global_batch_tags: K6 plus NM / MD / ZC / ZR of every job with a CIGAR -> (res, pool, tags, [md bytes or None])"""
         jobs = np.ascontiguousarray(jobs, dtype=GLB_DT)

@@ -1830,6 +1830,30 @@ extern "C" BSX_API int bsx_regions_dedup_long_cap(void) { return dedup_long_cap(
 extern "C" BSX_API int bsx_regions_dedup2(bsx_device_t *d, const bsx_opt_t *opt, int64_t n_reads, int per_read, int32_t *out_n, uint8_t *out_idx,
                                           int64_t *long_off, uint16_t **long_idx, int64_t *long_cap)
 { return lane_regions_dedup(d, 0, opt, n_reads, per_read, out_n, out_idx, long_off, long_idx, long_cap); }
+// test hook (like the bsx_hook_* entries of csrc/host/hooks.c; not in include/bsx.h): the caller's regions, offsets and counts put into lane 0
+// where lane_regions_batch leaves its own, so that bsx_regions_dedup* can be given lists made for it.  cnt[t] = -1: a strand search the
+// device did not finish.
+extern "C" BSX_API int bsx_hook_regions_put(bsx_device_t *d, int64_t n_tasks, const bsx_region_t *regs, int64_t n_regs, const int64_t *off, const int32_t *cnt)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (!regs || !off || !cnt || n_tasks < 0 || n_tasks > 0x7fffffff || n_regs < 0) return BSX_E_ARG;
+	Lane &L = d->lane[0];
+	if (L.rs.active) return BSX_E_ARG;
+	for (int64_t t = 0; t < n_tasks; ++t)
+		if (cnt[t] >= 0 && (off[t] < 0 || off[t] > n_regs || (int64_t)cnt[t] > n_regs - off[t])) return BSX_E_ARG;
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc;
+	const size_t n = (size_t)n_tasks;
+	if ((rc = L.regs.reserve(((size_t)n_regs + 1) * sizeof(bsx_region_t))) != BSX_OK) return rc;
+	if ((rc = L.regmeta.reserve(n * 49 + 64)) != BSX_OK) return rc;
+	H2D(L.st, L.regs.p, regs, (size_t)n_regs * sizeof(bsx_region_t));
+	H2D(L.st, L.regmeta.p, off, n * 8);
+	H2D(L.st, (char*)L.regmeta.p + n * 8, cnt, n * 4);
+	L.rb_tasks = n_tasks;
+	L.rs.used_main = (unsigned long long)n_regs;
+	L.ddl.valid = false;
+	return BSX_OK;
+}
 extern "C" BSX_API int bsx_sa_batch(bsx_device_t *d, int64_t n, const bsx_sa_job_t *jobs, uint64_t *pos) { return lane_sa_batch(d, 0, n, jobs, pos); }
 extern "C" BSX_API int bsx_extend_batch(bsx_device_t *d, int64_t n, const bsx_ext_job_t *jobs, bsx_ext_res_t *res) { return lane_extend_batch(d, 0, n, jobs, res); }
 extern "C" BSX_API int bsx_sw_batch(bsx_device_t *d, int64_t n, const bsx_sw_job_t *jobs, bsx_sw_res_t *res) { return lane_sw_batch(d, 0, n, jobs, res); }

@@ -429,6 +429,9 @@ def test_dedup_kernel_against_host_function(tmp_path):
         cat = np.concatenate([regs[roff[2 * i]:roff[2 * i] + rn[2 * i]], regs[roff[2 * i + 1]:roff[2 * i + 1] + rn[2 * i + 1]]])
         if out_n[i] < 0:
             left += 1   # more regions than the kernel holds, or a pair of regions to test for concatenation: the host's rounds
+            if len(cat) <= cap:   # the kernel held them all: then the host function, too, must have needed a concatenation score
+                keep = np.zeros(max(1, len(cat)), dtype=np.int32)
+                assert L.bsx_hook_regs_sort_dedup(C.byref(opt), idx.h, cat.ctypes.data_as(C.c_void_p), len(cat), keep.ctypes.data_as(C.c_void_p)) == -1, (i, len(cat))
             continue
         keep = np.zeros(max(1, len(cat)), dtype=np.int32)
         m = L.bsx_hook_regs_sort_dedup(C.byref(opt), idx.h, cat.ctypes.data_as(C.c_void_p), len(cat), keep.ctypes.data_as(C.c_void_p))

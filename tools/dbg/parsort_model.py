@@ -102,25 +102,33 @@ def par_partition(a, s, t):
     wp = a[t][0]
     L = [p for p in range(s + 1, t + 1) if a[p][0] <= wp]          # where `do ++i while (a[i] < rp)` can stop
     R = [p for p in range(t - 1, s, -1) if a[p][0] >= wp]          # where `do --j while (rp < a[j])` can stop, from the right
-    setL, setR = set(L), set(R)
+    # (counts by one sweep each way instead of a sum per position: the kernel sorts up to 1024 keys)
+    is_l, is_r = [False] * (t + 2), [False] * (t + 2)
+    for p in L:
+        is_l[p] = True
+    for p in R:
+        is_r[p] = True
+    r_ge = [0] * (t + 3)              # R stops at or above p
+    for p in range(t, s, -1):
+        r_ge[p] = r_ge[p + 1] + is_r[p]
     partL, partR = {}, {}
+    l_le = 0                          # L stops at or below p
     for p in range(s + 1, t + 1):
-        if p in setL:
-            kL = sum(1 for q in L if q <= p)
-            above = sum(1 for q in R if q > p)
-            if above >= kL:
-                partL[kL] = p
-        if p in setR:
-            kR = sum(1 for q in R if q >= p)
-            below = sum(1 for q in L if q < p)
-            if below >= kR:
+        if is_l[p]:
+            l_le += 1
+            if r_ge[p + 1] >= l_le:   # L stop number kL takes part iff at least kL R stops lie above it
+                partL[l_le] = p
+        if is_r[p]:
+            kR = r_ge[p]
+            if l_le - is_l[p] >= kR:  # R stop number kR (from the right) iff at least kR L stops lie below it
                 partR[kR] = p
     assert len(partL) == len(partR)
     K = len(partL)
     vals = list(a)
     for k in range(1, K + 1):
         a[partL[k]], a[partR[k]] = vals[partR[k]], vals[partL[k]]
-    first_free = min(p for p in L if p not in partL.values())
+    taking = set(partL.values())
+    first_free = min(p for p in L if p not in taking)
     i = min(first_free, partR[K]) if K else first_free
     a[i], a[t] = a[t], a[i]
     return i
@@ -171,12 +179,8 @@ def par_introsort(a, comb=False):
             if not stack:
                 break
             s, t, d = stack.pop()
-    # insertion pass = stable order by weight
-    rank = [sum(1 for q in range(n) if a[q][0] > a[p][0] or (a[q][0] == a[p][0] and q < p)) for p in range(n)]
-    out = [None] * n
-    for p in range(n):
-        out[rank[p]] = a[p]
-    a[:] = out
+    # insertion pass = stable order by weight (heavier first, earlier position first)
+    a.sort(key=lambda x: -x[0])
     return True
 
 
