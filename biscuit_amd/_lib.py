@@ -88,7 +88,7 @@ class GlbTag(C.Structure):
 
 class Backend(C.Structure):  # bsx_backend_t (csrc/host/bsx_core.h)
     _fields_ = [("ctx", C.c_void_p), ("name", C.c_char_p)] + [(n, C.c_void_p) for n in
-                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p)]
+                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p)]
 
 
 class GlbCtx(C.Structure):  # bsx_glb_ctx_t: [strand hypothesis][A, C, G, T, N context][retained, converted]
@@ -109,6 +109,17 @@ class QcCounts(C.Structure):  # bsx_qc_counts_t: [CpG, CpH][read][position][conv
 class QcTotals(C.Structure):  # bsx_qc_totals_t
     _fields_ = [("dev", QcCounts), ("mapq", C.c_uint64 * 62), ("isize", C.c_uint64 * 1001), ("n_isize", C.c_uint64), ("all_tot", C.c_uint64), ("all_dup", C.c_uint64),
                 ("q40_tot", C.c_uint64), ("q40_dup", C.c_uint64), ("strandcnt", C.c_uint64 * 16)]
+
+
+class MarkdupKey(C.Structure):  # bsx_markdup_key_t: w[0] = read 1 (or the single read), w[1] = read 2 (MD_SINGLE: a single read has none); an end: placed << 63 | reverse << 62 | YD is r << 61 | contig << 33 | u5 + 2^32
+    _fields_ = [("w", C.c_uint64 * 2)]
+
+
+MD_PLACED, MD_REVERSE, MD_YD, MD_U5_BIAS, MD_SINGLE = 1 << 63, 1 << 62, 1 << 61, 1 << 32, 1
+
+
+class MarkdupTotals(C.Structure):  # bsx_markdup_totals_t
+    _fields_ = [("n_templates", C.c_uint64), ("n_keyed", C.c_uint64), ("n_dup", C.c_uint64)]
 
 
 class BsconvConf(C.Structure):  # bsx_bsconv_conf_t

@@ -278,6 +278,30 @@ class Device(Batches):
         B.check(f(self.h, C.byref(c), int(reset)), "bsx_qc_read")
         return (np.array(c.readpos, dtype=np.int64).reshape(2, 2, 301, 2), np.array(c.conv, dtype=np.int64), np.array(c.confusion, dtype=np.int64))
 
+    def markdup_batch(self, keys, first_ordinal):
+        """bsx_markdup_batch: keys = uint64[n, 2] (_lib.MarkdupKey's layout; both words all ones: skipped), the template with ordinal
+        first_ordinal + i at keys[i] -> uint8[n], 1 where an equal key with a lower ordinal is in the device's table or earlier in the batch"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1, 2)
+        out = np.zeros(len(keys), np.uint8)
+        f = B.lib().bsx_markdup_batch
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_uint64, C.c_void_p]
+        B.check(f(self.h, len(keys), _p(keys), int(first_ordinal), _p(out)), "bsx_markdup_batch")
+        return out
+
+    def markdup_reset(self):
+        """bsx_markdup_reset: the device's table of template keys emptied"""
+        f = B.lib().bsx_markdup_reset
+        f.argtypes = [C.c_void_p]
+        B.check(f(self.h), "bsx_markdup_reset")
+
+    def markdup_table(self):
+        """bsx_markdup_table_info (tests, diagnostics) -> (slots, slots taken)"""
+        n, u = C.c_uint64(), C.c_uint64()
+        f = B.lib().bsx_markdup_table_info
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        B.check(f(self.h, C.byref(n), C.byref(u)), "bsx_markdup_table_info")
+        return n.value, u.value
+
     def counters(self, reset=False):
         c = (C.c_uint64 * 4)()
         B.check(B.lib().bsx_device_counters(self.h, c, int(reset)), "bsx_device_counters")

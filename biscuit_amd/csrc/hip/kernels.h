@@ -44,6 +44,15 @@ void launch_global(hipStream_t st, const DevIndex &ix, const DevScoring &sc, con
 // k_qc.hip: the column counts of `biscuit qc` over n records (bsx_qc_job_t), added to the device's table (bsx_qc_counts_t as 64-bit cells)
 void launch_qc(hipStream_t st, const DevIndex &ix, const uint8_t *reads, long long reads_len, const bsx_qc_job_t *jobs, long long n, const uint32_t *pool,
                unsigned long long *table, int n_cu);
+// k_markdup.hip: the device's table of template keys (bsx_markdup_batch).  A slot: claim word (0: empty), lowest ordinal, the key (all ones: none yet)
+struct MdSlot { unsigned long long claim, ord, k0, k1; };
+enum { MD_RES_FIRST = 0, MD_RES_DUP = 1, MD_RES_OPEN = 2, MD_RES_SKIP = 3, MD_RES_FULL = 4 };   // a key's state in res[] (OPEN: to be looked up in this round)
+void launch_md_init(hipStream_t st, MdSlot *T, unsigned long long n_slots);
+// one round over the keys still OPEN: k_md_claim, k_md_publish, k_md_decide; ctr[0] += slots taken, ctr[1] += keys left OPEN (another key has their claim word)
+void launch_md_round(hipStream_t st, MdSlot *T, unsigned long long n_slots, const bsx_markdup_key_t *keys, long long n, unsigned long long first,
+                     unsigned salt, int bits, uint8_t *res, unsigned long long *slot, unsigned long long *ctr);
+// every taken slot of `old` into T (initialised, at least twice the slots); ctr[2] += slots that found no room (none)
+void launch_md_rehash(hipStream_t st, const MdSlot *old, unsigned long long n_old, MdSlot *T, unsigned long long n_slots, unsigned long long *ctr);
 // K4 four to a wavefront (k_ext4.hip): a row of 16 lanes per job, persistent rows taking jobs off *cursor (zero at launch).
 // launch_x4: the extensions of the best seed of every chain the tiers exported (records with has_ext), written into the records ahead of
 // launch_c2r; jobs = room for job_cap jobs of x4_job_bytes(), ctr32[0..3]: job counts and cursor (zeroed by the call).

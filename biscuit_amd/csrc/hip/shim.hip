@@ -38,7 +38,7 @@ struct Lane {
 	DevBuf qpack;            // the chunk's reads as base-3 digits for the seeding kernel (k_seedt.hip)
 	int64_t rb_tasks = 0;    // strand searches of the last regions batch (their regions, offsets and counts are still in regs / regmeta)
 	int flt_key[3] = {-1, -1, -1};   // what fltab was made for
-	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, gctx, qcjobs, qcpool, dd, sswjobs, c2rslab;
+	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, gctx, qcjobs, qcpool, mdkeys, mdres, mdslot, dd, sswjobs, c2rslab;
 	DevBuf small;          // counters[4] | out_cursor | task_cursor | region cursors
 	HostBuf hstage;        // pinned staging for bulk results
 	HostBuf pin;           // two pinned halves through which large host<->device copies are streamed
@@ -79,6 +79,9 @@ struct bsx_device {
 	DevBuf bwt[2], sa[2], pac, ctg, holes, seedtab[2];
 	DevBuf qc;   // bsx_qc_counts_t: the BISCUITqc column counts of every lane's batches (k_qc.hip), zeroed when made and by bsx_qc_read(reset)
 	std::mutex qc_mu;
+	// the table of template keys (k_markdup.hip): made by the first bsx_markdup_batch, doubled as it fills, kept until bsx_markdup_reset / close
+	MdSlot *md = nullptr; uint64_t md_slots = 0, md_used = 0;
+	std::mutex md_mu;
 	Lane lane[BSX_LANES];   // scoring matrices and penalties are per lane (Lane::sc): chunks with different options may be in flight together
 	// Front halves of consecutive chunks are chained stage by stage (the seeding launch of chunk k+1 waits for that of chunk k, the
 	// region launches likewise): four chunks that share the device evenly all finish at the same moment, and the device then idles
@@ -176,10 +179,11 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 	devbuf_drain(d->ordinal);   // the blocks this device's buffers left behind when they grew
 	for (int i = 0; i < 2; ++i) { d->bwt[i].release(); d->sa[i].release(); d->seedtab[i].release(); }
 	d->pac.release(); d->ctg.release(); d->holes.release(); d->qc.release();
+	if (d->md) { (void)hipFree(d->md); d->md = nullptr; d->md_slots = d->md_used = 0; }
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
 		L.reads.release(); L.qpack.release(); L.gath.release(); L.jobs.release(); L.res.release(); L.scratch.release(); L.scratch2.release(); L.out.release(); L.aux.release(); L.pool.release();
-		L.small.release(); L.hstage.release(); L.regs.release(); L.regmeta.release(); L.slabs.release(); L.slabflags.release(); L.slabs3.release(); L.redo.release(); L.pin.release(); L.pos.release(); L.posoff.release(); L.xpool.release(); L.xmeta.release(); L.x4jobs.release(); L.fltab.release(); L.flt_key[0] = -1; L.tags.release(); L.mdpool.release(); L.gctx.release(); L.qcjobs.release(); L.qcpool.release(); L.dd.release(); L.c2rslab.release(); L.sswjobs.release(); L.msw_jobs.release(); L.msw_res.release(); L.msw_meta.release(); L.msw_roff.release();
+		L.small.release(); L.hstage.release(); L.regs.release(); L.regmeta.release(); L.slabs.release(); L.slabflags.release(); L.slabs3.release(); L.redo.release(); L.pin.release(); L.pos.release(); L.posoff.release(); L.xpool.release(); L.xmeta.release(); L.x4jobs.release(); L.fltab.release(); L.flt_key[0] = -1; L.tags.release(); L.mdpool.release(); L.gctx.release(); L.qcjobs.release(); L.qcpool.release(); L.mdkeys.release(); L.mdres.release(); L.mdslot.release(); L.dd.release(); L.c2rslab.release(); L.sswjobs.release(); L.msw_jobs.release(); L.msw_res.release(); L.msw_meta.release(); L.msw_roff.release();
 		if (L.pev[0]) (void)hipEventDestroy(L.pev[0]);
 		if (L.pev[1]) (void)hipEventDestroy(L.pev[1]);
 		if (L.ev0) (void)hipEventDestroy(L.ev0);
@@ -1923,6 +1927,111 @@ extern "C" BSX_API int bsx_qc_batch(bsx_device_t *d, int64_t n, const bsx_qc_job
 { return lane_qc_batch(d, 0, n, jobs, cigar_pool, cigar_pool_len); }
 extern "C" BSX_API int bsx_qc_read(bsx_device_t *d, bsx_qc_counts_t *out, int reset) { return dev_qc_read(d, out, reset); }
 
+// ------------------------------------------------------------------------------------------
+// duplicate templates (k_markdup.hip)
+// ------------------------------------------------------------------------------------------
+static int md_alloc(bsx_device_t *d, hipStream_t st, uint64_t n_slots, MdSlot **out)   // an empty table of n_slots
+{
+	if (hipMalloc((void**)out, n_slots * sizeof(MdSlot)) != hipSuccess) {
+		size_t fr = 0, tot = 0; (void)hipGetLastError(); (void)hipMemGetInfo(&fr, &tot);
+		fprintf(stderr, "[bsx-hip] markdup: no room for a table of %llu slots, %llu bytes (%zu of %zu bytes free; the table in use has %llu slots)\n",
+		        (unsigned long long)n_slots, (unsigned long long)(n_slots * sizeof(MdSlot)), fr, tot, (unsigned long long)d->md_slots);
+		*out = nullptr; return BSX_E_NOMEM;
+	}
+	launch_md_init(st, *out, n_slots);
+	HIPCHK(hipGetLastError());
+	return BSX_OK;
+}
+// room for `more` new keys at a load of one half or less: the first table, or one of twice (four times, ...) the slots with every slot moved over
+static int md_room(bsx_device_t *d, Lane &L, uint64_t more, unsigned long long *ctr)
+{
+	uint64_t want = d->md_slots;
+	if (!d->md) {
+		const long t = bsx_tune_long("markdup_slots", 0);
+		want = t > 0 ? (uint64_t)t : std::max<uint64_t>(65536, 32 * more);
+		while (want & (want - 1)) want += want & (~want + 1);   // up to a power of two
+		if (want < 2) want = 2;
+	}
+	while ((d->md_used + more) * 2 > want) want *= 2;
+	if (d->md && want == d->md_slots) return BSX_OK;
+	MdSlot *T = nullptr;
+	int rc;
+	if ((rc = md_alloc(d, L.st_hi, want, &T)) != BSX_OK) return rc;
+	if (d->md) {
+		unsigned long long lost = 0;
+		launch_md_rehash(L.st_hi, d->md, d->md_slots, T, want, ctr);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(&lost, ctr + 2, 8, hipMemcpyDeviceToHost, L.st_hi));
+		HIPCHK(hipStreamSynchronize(L.st_hi));
+		if (lost) { (void)hipFree(T); return BSX_E_INTERNAL; }
+		(void)hipFree(d->md);
+		if (bsx_phases()) fprintf(stderr, "[M::markdup] table grown from %llu to %llu slots (%llu taken)\n", (unsigned long long)d->md_slots, (unsigned long long)want, (unsigned long long)d->md_used);
+	}
+	d->md = T; d->md_slots = want;
+	return BSX_OK;
+}
+static int dev_markdup_reset(bsx_device_t *d)
+{
+	if (!d) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->md_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (d->md) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(d->md); }
+	d->md = nullptr; d->md_slots = d->md_used = 0;
+	return BSX_OK;
+}
+#define MD_MAX_SALTS 8
+static int lane_markdup_batch(bsx_device_t *d, int lane, int64_t n, const bsx_markdup_key_t *keys, uint64_t first_ordinal, uint8_t *dup_out)
+{
+	if (!d) return BSX_E_NODEVICE;
+	if (n < 0) return dev_markdup_reset(d);
+	if (n == 0) return BSX_OK;
+	if (!keys || !dup_out || first_ordinal + (uint64_t)n < first_ordinal || first_ordinal + (uint64_t)n == ~0ull) return BSX_E_ARG;
+	Lane &L = d->lane[lane];
+	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
+	std::lock_guard<std::mutex> lock(d->md_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	const int bits = (int)bsx_tune_long("markdup_hash_bits", 64);
+	const size_t res_bytes = ((size_t)n + 7) & ~(size_t)7, tail = 4 * 8;   // res[n], then ctr[4]: slots taken, keys left open, slots lost in a rehash
+	int rc;
+	if ((rc = L.mdkeys.reserve((size_t)n * sizeof(bsx_markdup_key_t))) != BSX_OK) return rc;
+	if ((rc = L.mdres.reserve(res_bytes + tail)) != BSX_OK) return rc;
+	if ((rc = L.mdslot.reserve((size_t)n * 8)) != BSX_OK) return rc;
+	uint8_t *res = (uint8_t*)L.mdres.p;
+	unsigned long long *ctr = (unsigned long long*)(res + res_bytes);
+	std::vector<uint8_t> host(res_bytes + tail);
+	HIPCHK(hipMemsetAsync(res, MD_RES_OPEN, res_bytes, L.st_hi));
+	HIPCHK(hipMemsetAsync(ctr, 0, tail, L.st_hi));
+	H2D(L.st_hi, L.mdkeys.p, keys, (size_t)n * sizeof(bsx_markdup_key_t));
+	uint64_t open = (uint64_t)n;
+	for (unsigned salt = 0; open; ++salt) {
+		if (salt == MD_MAX_SALTS) { fprintf(stderr, "[bsx-hip] markdup: %llu keys met other keys with their claim word at %d salts\n", (unsigned long long)open, MD_MAX_SALTS); return BSX_E_INTERNAL; }
+		if ((rc = md_room(d, L, open, ctr)) != BSX_OK) return rc;
+		HIPCHK(hipMemsetAsync(ctr, 0, tail, L.st_hi));
+		launch_md_round(L.st_hi, d->md, d->md_slots, (const bsx_markdup_key_t*)L.mdkeys.p, (long long)n, first_ordinal, salt, bits, res, (unsigned long long*)L.mdslot.p, ctr);
+		HIPCHK(hipGetLastError());
+		D2H(L.st_hi, host.data(), res, res_bytes + tail);
+		const unsigned long long *c = (const unsigned long long*)(host.data() + res_bytes);
+		d->md_used += c[0];
+		open = c[1];
+	}
+	for (int64_t i = 0; i < n; ++i) {
+		if (host[(size_t)i] == MD_RES_FULL || host[(size_t)i] == MD_RES_OPEN) return BSX_E_INTERNAL;
+		dup_out[i] = host[(size_t)i] == MD_RES_DUP;
+	}
+	return BSX_OK;
+}
+extern "C" BSX_API int bsx_markdup_batch(bsx_device_t *d, int64_t n, const bsx_markdup_key_t *keys, uint64_t first_ordinal, uint8_t *dup_out)
+{ if (n < 0) return BSX_E_ARG; return lane_markdup_batch(d, 0, n, keys, first_ordinal, dup_out); }
+extern "C" BSX_API int bsx_markdup_reset(bsx_device_t *d) { return dev_markdup_reset(d); }
+extern "C" BSX_API int bsx_markdup_table_info(bsx_device_t *d, uint64_t *n_slots, uint64_t *n_used)
+{
+	if (!d) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->md_mu);
+	if (n_slots) *n_slots = d->md_slots;
+	if (n_used) *n_used = d->md_used;
+	return BSX_OK;
+}
+
 // the seams as one vtable for the host pipeline; ctx = (device, lane)
 #define LR(c) ((LaneRef*)(c))->d, ((LaneRef*)(c))->lane
 static int be_set_opt(void *c, const bsx_opt_t *o) { return lane_set_opt(LR(c), o); }
@@ -1961,6 +2070,8 @@ static int be_qc(void *c, int64_t n, const bsx_qc_job_t *j, const uint32_t *pool
 	return rc;
 }
 
+static int be_markdup(void *c, int64_t n, const bsx_markdup_key_t *k, uint64_t first, uint8_t *out) { return lane_markdup_batch(LR(c), n, k, first, out); }
+
 static LaneRef g_lane_ref[8][BSX_LANES];   // ctx storage for the vtables (by device ordinal)
 
 extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *out)
@@ -1972,7 +2083,7 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	memset(out, 0, sizeof(*out));
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
-	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc;
+	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup;
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

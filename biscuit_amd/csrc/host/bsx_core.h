@@ -193,6 +193,9 @@ typedef struct bsx_backend {
 	/* optional (may be NULL): the BISCUITqc column counts of n written records added to the backend's table (bsx_qc_batch); with read_out != NULL
 	 * the table is then copied out (reset != 0: and zeroed) -- n == 0 only reads.  Without it the host walks the records (qc.c). */
 	int (*qc_batch)(void *ctx, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len, bsx_qc_counts_t *read_out, int reset);
+	/* optional (may be NULL): bsx_markdup_batch on the backend's table of template keys; n < 0 empties the table (bsx_markdup_reset).  Without it
+	 * the host keeps the table (markdup.c). */
+	int (*markdup_batch)(void *ctx, int64_t n, const bsx_markdup_key_t *keys, uint64_t first_ordinal, uint8_t *dup_out);
 } bsx_backend_t;
 /* what msw_plan says about a pair: base = its first job in res (-1: the pair is left to the host's own plan), n_c[i] = candidates of read i it
  * looked at, mask[i] = which of them have a job (bit j: candidate j), in job order: read 0's, then read 1's */

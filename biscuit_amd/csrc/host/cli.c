@@ -66,6 +66,8 @@ static int usage(void)
 		"  qc        : --qc PREFIX  write the BISCUITqc tables of the records written, as `biscuit qc <ref> <bam> PREFIX` would: PREFIX_mapq_table.txt,\n"
 		"              _dup_report.txt, _strand_table.txt, _totalReadConversionRate.txt, _CpGRetentionByReadPos.txt, _CpHRetentionByReadPos.txt and,\n"
 		"              for paired input, _isize_table.txt\n"
+		"  markdup   : --markdup  0x400 on every record of a template (a pair, or a single read) whose ends' unclipped 5' positions, strands and YD\n"
+		"              equal those of an earlier template of the input; one process only (refused with WORLD_SIZE > 1)\n"
 		"  device    : $BSX_DEVICE selects the HIP device ordinal (default 0)\n\n");
 	return 1;
 }
@@ -329,6 +331,9 @@ static void bsconv_report(void)
 	bsconv_print(t, n, nf);
 }
 
+/* --markdup needs one table for the whole input: the tables of several devices would have to be one */
+#define MARKDUP_RANKS_MSG "--markdup marks duplicates over the whole input in one table on one device: it cannot run with WORLD_SIZE > 1"
+
 /* --qc: the tables of `biscuit qc` (src/qc.c) over this call's records; with several ranks rank 0 writes the sum (bsx_align_main_ranks_with) */
 static char g_qc_prefix[4096];
 static int g_qc_paired;
@@ -359,10 +364,10 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		{"bsconv", no_argument, 0, 1000}, {"bsconv-max-cph", required_argument, 0, 1001}, {"bsconv-max-cpa", required_argument, 0, 1002},
 		{"bsconv-max-cpc", required_argument, 0, 1003}, {"bsconv-max-cpt", required_argument, 0, 1004}, {"bsconv-max-cpy", required_argument, 0, 1005},
 		{"bsconv-max-cph-frac", required_argument, 0, 1006}, {"bsconv-max-cpy-frac", required_argument, 0, 1007},
-		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {"qc", required_argument, 0, 1010}, {0, 0, 0, 0}
+		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {"qc", required_argument, 0, 1010}, {"markdup", no_argument, 0, 1011}, {0, 0, 0, 0}
 	};
 	bsx_bsconv_conf_t bsconv;
-	int bsconv_on = 0, qc_on = 0;
+	int bsconv_on = 0, qc_on = 0, markdup_on = 0;
 
 	bsx_bsconv_conf_init(&bsconv);
 	g_write_error = 0;   /* per call: a failed write of an earlier call in this process must not fail this one */
@@ -374,6 +379,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	optind = 1;
 	while ((c = getopt_long(argc, argv, ":@:1:2:3:5:9ab:c:d:ef:g:hijk:m:pqr:s:v:w:x:y:z:A:B:CD:E:FG:H:I:J:K:L:MN:O:PQ:R:ST:U:VW:X:Y", long_opts, 0)) >= 0) {
 		if (c == 1010) { qc_on = 1; snprintf(g_qc_prefix, sizeof(g_qc_prefix), "%s", optarg); }
+		else if (c == 1011) markdup_on = 1;
 		else if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
 			bsconv_on = 1;
 			if (c == 1000) bsconv.annotate = 1;
@@ -522,6 +528,8 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	if (bsconv_on) bsconv.annotate = 1;   /* a filter implies the annotation */
 	bsx_process_set_bsconv(bsconv_on ? &bsconv : 0);   /* every chunk of this call, through a stream or not; totals from zero */
 	bsx_process_set_qc(qc_on);
+	if (markdup_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; }
+	bsx_process_set_markdup(markdup_on);
 	if (optind >= argc) { usage(); fprintf(stderr, "Missing fai-index base\n"); return 1; }
 	if ((rc = bsx_index_load(argv[optind], &idx)) != BSX_OK) { fprintf(stderr, "[E::%s] fail to locate the index files (%s)\n", "main_align", bsx_strerror(rc)); return 1; }
 	if (auto_alt) infer_alt(&idx->ref);
@@ -727,7 +735,14 @@ loop_done:
 		if (bsx_shard_world <= 1) { if (rc == 0 && qc_report() != BSX_OK) rc = 1; }
 		else if (bsx_process_qc_totals(0, 0) != BSX_OK) rc = 1;
 	}
+	if (markdup_on && bsx_verbose >= 3) {
+		bsx_markdup_totals_t t;
+		bsx_process_markdup_totals(&t, 0);
+		fprintf(stderr, "[M::%s] markdup: %llu templates, %llu with a placed end, %llu duplicates\n", "main_align", (unsigned long long)t.n_templates,
+		        (unsigned long long)t.n_keyed, (unsigned long long)t.n_dup);
+	}
 cleanup:
+	if (markdup_on) bsx_process_set_markdup(0);
 	if (qc_on && bsx_shard_world <= 1) bsx_process_set_qc(0);
 	if (bsconv_on && bsx_shard_world <= 1) bsx_process_set_bsconv(0);
 	if (open_device && ud && g_close_device) g_close_device(ud);   /* the device this call opened: index replica, lanes, streams */
@@ -800,6 +815,7 @@ BSX_API int bsx_align_main_ranks_with(int argc, char **argv, bsx_process_fn proc
 	int64_t n_chunks = 0, mine, *all;
 	if (world <= 1 || bsx_emit_hook) return bsx_align_main_with(argc, argv, process, ud, open_device);   /* (a launcher with its own hook: multi_gpu.py) */
 	if (rank < 0 || rank >= world) { fprintf(stderr, "[E::%s] RANK %d of WORLD_SIZE %d\n", "main_align", rank, world); return 1; }
+	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 3 && strncmp("--markdup", argv[k], strlen(argv[k])) == 0) { /* (any abbreviation getopt_long takes: no other long option begins with --m) */ fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; } }   /* (before any transport is opened) */
 	memset(&R, 0, sizeof(R));
 	if (id_env && *id_env) snprintf(id_path, sizeof(id_path), "%s", id_env);
 	else if (out_path && *out_path) snprintf(id_path, sizeof(id_path), "%s.ranks", out_path);

@@ -23,6 +23,7 @@
 #include "tune.h"
 #include "pipeline.h"
 #include "qc.h"
+#include "markdup.h"
 
 static double now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.tv_sec + tv.tv_usec * 1e-6; }
 
@@ -140,8 +141,29 @@ BSX_API int bsx_process_qc_totals(bsx_qc_totals_t *out, int reset)
 	return rc;
 }
 
+/* ------------------------------------------------------------------ duplicate marking while aligning (markdup.c): setting and totals of the process (a stream has its own) */
+static bsx_md_state_t g_md = BSX_MD_STATE_INIT;
+static int md_state_totals(bsx_md_state_t *q, bsx_markdup_totals_t *out)
+{
+	pthread_mutex_lock(&q->mu);
+	*out = q->tot;
+	pthread_mutex_unlock(&q->mu);
+	return BSX_OK;
+}
+BSX_API int bsx_process_set_markdup(int on) { bsx_md_state_set(&g_md, on); return BSX_OK; }
+BSX_API int bsx_process_markdup_totals(bsx_markdup_totals_t *out, int reset)
+{
+	if (!out) return BSX_E_ARG;
+	md_state_totals(&g_md, out);
+	if (reset) { pthread_mutex_lock(&g_md.mu); memset(&g_md.tot, 0, sizeof(g_md.tot)); pthread_mutex_unlock(&g_md.mu); }
+	return BSX_OK;
+}
+
 /* ------------------------------------------------------------------ chunk state */
 typedef struct {
+	/* duplicate marking for this chunk's templates (NULL: off): its stream's state, else the process's; the chunk's place in that state's input
+	 * (taken when the chunk is pushed), the slices its back half runs in (0: not begun) and how many of them have handed their keys over */
+	bsx_md_state_t *md; int64_t md_seq; uint64_t md_ord0; int md_nsl, md_passed;
 	bsx_qc_state_t *qc;  /* BISCUITqc counting for this chunk's records (NULL: off): its stream's state, else the process's */
 	bsconv_state_t *bs;  /* conversion by context for this chunk's records (NULL: off): its stream's setting, else the process's */
 	const bsx_backend_t *be;
@@ -959,7 +981,32 @@ static void plan_free_worker(void *data, long u, int tid)
 static pthread_mutex_t g_stat_mu = PTHREAD_MUTEX_INITIALIZER;   /* a chunk's phase times, added to by the slices of its back half */
 static void stat_add(double *dst, double v) { pthread_mutex_lock(&g_stat_mu); *dst += v; pthread_mutex_unlock(&g_stat_mu); }
 
-static int emit_sam(chunk_t *C, int u0, int u1)   /* the units (pairs, or single reads) [u0, u1) */
+/* duplicate marking: a unit's key from the primary records of its ends, once their CIGARs and positions are final (finish_worker) */
+typedef struct { chunk_t *C; samctx_t *ctx; int per, u0; bsx_markdup_key_t *keys; } md_par_t;
+static void md_key_worker(void *data, long k, int tid)
+{
+	md_par_t *M = (md_par_t*)data;
+	const samctx_t *x = &M->ctx[k];
+	uint64_t w[2] = {0, 0};
+	int i, u[2] = {0, 0};
+	(void)tid;
+	for (i = 0; i < M->per; ++i) u[i] = x->md_pri[i] >= 0 && x->table[i][x->md_pri[i]].valid && x->table[i][x->md_pri[i]].bss_u;
+	for (i = 0; i < M->per; ++i) {
+		const int gi = x->md_pri[i];
+		const reg_t *r;
+		const samrec_t *t;
+		if (gi < 0) continue;   /* not placed */
+		r = &M->C->regs[(M->u0 + k) * M->per + i].a[gi];
+		t = &x->table[i][gi];
+		/* YD as written: u when the record's own walk says so and, in a pair, the mate's does too (format_sam) */
+		w[i] = bsx_md_end_key(r->rid, t->pos, (int)t->is_rev, (u[i] && (M->per == 1 || u[!i])) ? 0 : r->bss, t->valid ? t->n_cigar : 0, t->cigar);
+	}
+	if (!w[0] && !w[1]) w[0] = w[1] = ~(uint64_t)0;   /* no placed end */
+	else if (M->per == 1) w[1] = BSX_MD_SINGLE;
+	M->keys[k].w[0] = w[0]; M->keys[k].w[1] = w[1];
+}
+
+static int emit_sam(chunk_t *C, int u0, int u1, int sl, int n_sl)   /* the units (pairs, or single reads) [u0, u1): slice sl of n_sl of the chunk */
 {
 	int n_units = u1 - u0, per = C->is_pe ? 2 : 1, rc = BSX_OK, round;
 	samctx_t *ctx = (samctx_t*)bsx_par_calloc(C->nt, (size_t)n_units, sizeof(samctx_t));
@@ -974,6 +1021,7 @@ static int emit_sam(chunk_t *C, int u0, int u1)   /* the units (pairs, or single
 	double t0 = now_s(), t_batch = 0;
 	bsx_vec_init(todo);
 	P.C = C; P.ctx = ctx; P.final_pass = 0; P.u0 = u0;
+	if (C->md) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].md = 1; ctx[k].md_pri[0] = ctx[k].md_pri[1] = -2; }
 	bsx_parallel_for(C->nt, out_worker, &P, n_units);
 	stat_add(&C->st.t_primary, now_s() - t0); t0 = now_s();
 	Q.C = C; Q.ctx = ctx; Q.per = per; Q.u0 = u0;
@@ -1021,6 +1069,20 @@ static int emit_sam(chunk_t *C, int u0, int u1)   /* the units (pairs, or single
 	if (rc == BSX_OK && todo.n) rc = BSX_E_INTERNAL;
 	if (bsx_phases()) fprintf(stderr, "[M::cigar] %d rounds, %.3f s in the K6 batches, %.3f s on the host\n", round, t_batch, now_s() - t0 - t_batch);
 	stat_add(&C->st.t_cigar, now_s() - t0); t0 = now_s();
+	if (C->md) { /* the slice's keys to the table, in its turn; a slice that failed on its way lets the others go */
+		if (rc == BSX_OK) {
+			md_par_t M;
+			uint8_t *dup = (uint8_t*)malloc((size_t)n_units);
+			M.C = C; M.ctx = ctx; M.per = per; M.u0 = u0; M.keys = (bsx_markdup_key_t*)malloc(sizeof(bsx_markdup_key_t) * (size_t)n_units);
+			bsx_parallel_for(C->nt, md_key_worker, &M, n_units);
+			rc = bsx_md_slice(C->md, C->be, C->md_seq, sl, n_sl, n_units, M.keys, C->md_ord0 + (uint64_t)u0, dup);
+			if (rc == BSX_OK) for (k = 0; k < (size_t)n_units; ++k) ctx[k].md_dup = dup[k];
+			free(M.keys); free(dup);
+		}
+		if (rc != BSX_OK) bsx_md_fail(C->md);
+		else __atomic_fetch_add(&C->md_passed, 1, __ATOMIC_RELAXED);
+		stat_add(&C->st.t_cigar, now_s() - t0); t0 = now_s();
+	}
 	if (rc == BSX_OK && C->bs) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].bs = &C->bs->conf; ctx[k].bs_filter = C->bs->filter; }   /* (the planning pass writes no records) */
 	if (rc == BSX_OK && C->qc) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].qc = 1; ctx[k].qc_roff[0] = C->roff[(u0 + k) * per]; ctx[k].qc_roff[1] = C->roff[(u0 + k) * per + per - 1]; }
 	if (rc == BSX_OK) { P.final_pass = 1; bsx_parallel_for(C->nt, out_worker, &P, n_units); }
@@ -1407,17 +1469,17 @@ static int finish_pending(chunk_t *C)
  * next slice.  Every pair is still processed by the same code in the same order of stages: the SAM cannot change ("back_slices": 1 = the
  * stages over the whole chunk, as before). */
 typedef struct { chunk_t *C; int first, step, n_sl, n_units, helper, rc; } slice_run_t;
-static int one_slice(chunk_t *C, int u0, int u1)
+static int one_slice(chunk_t *C, int u0, int u1, int sl, int n_sl)
 {
 	int rc = BSX_OK;
-	if (u1 <= u0) return BSX_OK;
+	if (u1 <= u0) { if (C->md) { bsx_md_slice_skip(C->md, C->md_seq, sl, n_sl); __atomic_fetch_add(&C->md_passed, 1, __ATOMIC_RELAXED); } return BSX_OK; }
 	if (C->is_pe && !(C->opt->flag & BSX_F_NO_RESCUE)) {
 		double t0 = now_s();
 		rc = mate_rescue(C, u0, u1);
 		stat_add(&C->st.t_matesw, now_s() - t0);
-		if (rc != BSX_OK) return rc;
+		if (rc != BSX_OK) { if (C->md) bsx_md_fail(C->md); return rc; }
 	}
-	return emit_sam(C, u0, u1);
+	return emit_sam(C, u0, u1, sl, n_sl);
 }
 static void *slice_thread(void *arg)
 {
@@ -1427,7 +1489,7 @@ static void *slice_thread(void *arg)
 	if (R->helper) bsx_arenas_bind_extra(C->arena_set, R->helper - 1);   /* its own arena beside the chunk's: the caller of a parallel loop allocates too */
 	for (k = R->first; k < R->n_sl && R->rc == BSX_OK; k += R->step) {
 		const int u0 = (int)((int64_t)R->n_units * k / R->n_sl), u1 = (int)((int64_t)R->n_units * (k + 1) / R->n_sl);
-		R->rc = one_slice(C, u0, u1);
+		R->rc = one_slice(C, u0, u1, k, R->n_sl);
 	}
 	if (R->helper) bsx_arenas_bind(-1);
 	return 0;
@@ -1444,9 +1506,10 @@ static int back_slices(chunk_t *C)
 	if (n_thr > 4) n_thr = 4;
 	if (n_thr > n_sl) n_thr = n_sl;
 	if (n_thr < 1 || C->arena_set < 0) n_thr = 1;
+	C->md_nsl = n_sl;
 	for (j = 0; j < n_thr; ++j) { R[j].C = C; R[j].first = j; R[j].step = n_thr; R[j].n_sl = n_sl; R[j].n_units = n_units; R[j].helper = j; R[j].rc = BSX_OK; }
 	for (j = 1; j < n_thr; ++j) live[j] = pthread_create(&th[j], 0, slice_thread, &R[j]) == 0;
-	for (j = 1; j < n_thr; ++j) if (!live[j]) { R[j].helper = 0; }   /* (no thread: its slices run here, below) */
+	for (j = 1; j < n_thr; ++j) if (!live[j]) { R[j].helper = 0; if (C->md) { bsx_md_fail(C->md); R[j].rc = BSX_E_NOMEM; } }   /* (no thread: its slices run here, below -- too late for the order duplicate marking needs) */
 	(void)slice_thread(&R[0]);
 	for (j = 1; j < n_thr; ++j) { if (live[j]) pthread_join(th[j], 0); else (void)slice_thread(&R[j]); }
 	for (j = 0; j < n_thr; ++j) if (rc == BSX_OK) rc = R[j].rc;
@@ -1492,6 +1555,7 @@ static void chunk_free(chunk_t *C)
 {
 	int nt = C->nt;
 	double t0 = now_s();
+	if (C->md && (C->md_nsl == 0 || C->md_passed < C->md_nsl)) bsx_md_fail(C->md);   /* batches that will never come: later chunks must not wait for them */
 	bsx_arenas_bind(C->arena_set);
 	if (C->tasks) {
 		if (C->arena_set < 0) bsx_parallel_for(nt, release_worker, C, C->n_tasks);   /* arena memory is rewound, not freed */
@@ -1519,6 +1583,15 @@ static void chunk_free(chunk_t *C)
 	free(C);
 }
 
+static void chunk_set_md(chunk_t *C, bsx_md_state_t *q)
+{
+	if (!q || !q->on) return;
+	C->md = q;
+	bsx_md_chunk_begin(q, C->is_pe ? C->n >> 1 : C->n, &C->md_seq, &C->md_ord0);
+	/* the first chunk of a state that starts from zero: the backend's table starts empty too (no batch of this state can be in flight yet) */
+	if (C->md_seq == 0 && C->be->markdup_batch && C->be->markdup_batch(C->be->ctx, -1, 0, 0, 0) != BSX_OK) bsx_md_fail(q);
+}
+
 /* ------------------------------------------------------------------ the chunk, synchronously (mem_process_seqs) */
 BSX_API int bsx_process_seqs_backend(const bsx_backend_t *be, const bsx_opt_t *opt, const bsx_index_t *idx,
                                      int64_t n_processed, int n, bsx_read_t *reads, const bsx_pestat_t *pes0)
@@ -1529,6 +1602,7 @@ BSX_API int bsx_process_seqs_backend(const bsx_backend_t *be, const bsx_opt_t *o
 	if (n == 0) return BSX_OK;
 	if ((opt->flag & BSX_F_PE) && (n & 1)) return BSX_E_ARG;
 	C = chunk_new(be, opt, idx, n_processed, n, reads, pes0);
+	chunk_set_md(C, &g_md);
 	rc = chunk_front(C);
 	if (rc == BSX_OK) rc = chunk_back(C);
 	chunk_free(C);
@@ -1559,6 +1633,7 @@ struct bsx_stream {
 	int64_t n_pushed;
 	bsconv_state_t bs;        /* bsx_stream_set_bsconv: this stream's own setting and totals (off: the process's setting applies) */
 	bsx_qc_state_t qc;        /* bsx_stream_set_qc: likewise */
+	bsx_md_state_t md;        /* bsx_stream_set_markdup: likewise */
 };
 
 static int g_whole_chunk_threads = -1;   /* $BSX_STREAM_WHOLE_CHUNK=N: the chunk's own thread runs its back half too, at most N back halves at a time (0: the pushing thread runs them, one by one) */
@@ -1609,6 +1684,7 @@ BSX_API int bsx_stream_open_backends(int depth, const bsx_backend_t *be, const b
 	s = (bsx_stream_t*)calloc(1, sizeof(*s));
 	for (i = 0; i < depth; ++i) s->be[i] = be[i];
 	s->depth = depth; s->opt = opt; s->idx = idx;
+	bsx_md_state_set(&s->md, 0);
 	if (pes0) { s->pes0 = *pes0; s->has_pes0 = 1; }
 	*out = s;
 	return BSX_OK;
@@ -1650,6 +1726,18 @@ BSX_API int bsx_stream_qc_totals(bsx_stream_t *s, bsx_qc_totals_t *out)
 	return qc_state_totals(s->qc.on ? &s->qc : &g_qc, out);
 }
 
+BSX_API int bsx_stream_set_markdup(bsx_stream_t *s, int on)
+{
+	if (!s || s->n_pushed) return BSX_E_ARG;
+	bsx_md_state_set(&s->md, on);   /* (its first chunk empties the backend's table) */
+	return BSX_OK;
+}
+BSX_API int bsx_stream_markdup_totals(bsx_stream_t *s, bsx_markdup_totals_t *out)
+{
+	if (!s || !out) return BSX_E_ARG;
+	return md_state_totals(s->md.on ? &s->md : &g_md, out);
+}
+
 /* wait for the chunk's front half, run its back half (its reads get their SAM text), release it */
 static int chunk_finish(chunk_t *C)
 {
@@ -1678,6 +1766,7 @@ BSX_API int bsx_stream_push(bsx_stream_t *s, int64_t n_processed, int n, bsx_rea
 		++s->n_pushed;
 		if (s->bs.on) C->bs = &s->bs;
 		if (s->qc.on) C->qc = &s->qc;
+		chunk_set_md(C, s->md.on ? &s->md : &g_md);
 		/* a ticket only for the chunks that take a turn: a chunk pushed while the histogram hook is set (or without $BSX_STREAM_WHOLE_CHUNK)
 		 * never advances g_back_next, so handing it a number would leave every later ordered chunk waiting for a turn that never comes */
 		C->ordered = g_whole_chunk_threads > 0 && !bsx_pes_hist_hook;
@@ -1713,5 +1802,6 @@ BSX_API void bsx_stream_close(bsx_stream_t *s)
 {
 	if (!s) return;
 	(void)stream_drain(s);
+	bsx_md_state_end(&s->md);
 	free(s);
 }

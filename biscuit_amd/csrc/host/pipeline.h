@@ -68,6 +68,10 @@ typedef struct {
 	uint32_t qc_roff[2];
 	bsx_qc_rec_v qc_recs;
 	bsx_qc_cig_v qc_cig;
+	/* duplicate marking while aligning (md 0: off): the planning pass notes each end's primary record -- index of its region, -1: the unplaced
+	 * stand-in, -2: none yet / no such end; md_dup: the template is a duplicate, the final pass writes 0x400 into every record */
+	int md, md_dup;
+	int md_pri[2];
 } samctx_t;
 /* is the per-record rule of `biscuit bsconv` on (any member besides annotate off its default)? */
 int bsx_bsconv_filters(const bsx_bsconv_conf_t *c);

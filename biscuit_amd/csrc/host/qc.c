@@ -93,7 +93,8 @@ int bsx_qc_slice(bsx_qc_state_t *q, const bsx_backend_t *be, const bsx_index_t *
 		for (k = 0; k < ctx[u].qc_recs.n; ++k) { /* process_qc, src/qc.c:125-160 */
 			const bsx_qc_rec_t *r = &ctx[u].qc_recs.a[k];
 			++t->all_tot;
-			if (r->mapq >= 40) ++t->q40_tot;
+			if (r->flag & 0x400) ++t->all_dup;   /* (only --markdup sets it) */
+			if (r->mapq >= 40) { ++t->q40_tot; if (r->flag & 0x400) ++t->q40_dup; }
 			if (!(r->flag & 0x100)) {
 				if (r->flag & 0x4) ++t->mapq[BSX_QC_N_MAPQ];
 				else if (r->mapq <= BSX_QC_N_MAPQ) ++t->mapq[r->mapq];
@@ -116,7 +117,7 @@ int bsx_qc_slice(bsx_qc_state_t *q, const bsx_backend_t *be, const bsx_index_t *
 		for (i = 0; i <= BSX_QC_N_MAPQ; ++i) q->tot.mapq[i] += t->mapq[i];
 		for (i = 0; i <= BSX_QC_ISIZE; ++i) q->tot.isize[i] += t->isize[i];
 		for (i = 0; i < 16; ++i) q->tot.strandcnt[i] += t->strandcnt[i];
-		q->tot.n_isize += t->n_isize; q->tot.all_tot += t->all_tot; q->tot.q40_tot += t->q40_tot;
+		q->tot.n_isize += t->n_isize; q->tot.all_tot += t->all_tot; q->tot.q40_tot += t->q40_tot; q->tot.all_dup += t->all_dup; q->tot.q40_dup += t->q40_dup;
 		if (nj && be->qc_batch) { /* this backend's table has counts of ours now */
 			for (i = 0; i < q->n_be; ++i) if (q->be[i].ctx == be->ctx && q->be[i].fn == be->qc_batch) break;
 			if (i == q->n_be && q->n_be < BSX_QC_MAX_BE) { q->be[i].fn = be->qc_batch; q->be[i].ctx = be->ctx; ++q->n_be; }

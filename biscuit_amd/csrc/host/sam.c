@@ -432,6 +432,9 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 			t[3] = p0->flag; t[4] = (int)p0->mapq; t[5] = is_primary;
 		}
 		if (regs0) tag_XAXB(D, which, s, p0, regs0, str);
+		/* duplicate marking: the end's primary record is the first one planned without 0x100 / 0x800 -- its region, or -1 for the unplaced stand-in */
+		if (D->ctx->md && D->ctx->md_pri[which] == -2 && !(p0->flag & (0x100 | 0x800 | 0x10000)))
+			D->ctx->md_pri[which] = regs0 && p0 >= regs0->a && p0 < regs0->a + regs0->n ? (int)(p0 - regs0->a) : -1;
 		return;
 	}
 	const size_t rec0 = str->l;   /* where this record starts: a record the filters drop is taken back */
@@ -444,6 +447,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 	if (p.rid < 0 && m0 && m.rid >= 0) { p.rid = m.rid; p.pos = m.pos; p.is_rev = m.is_rev; p.n_cigar = 0; }
 	if (m0 && m.rid < 0 && p.rid >= 0) { m.rid = p.rid; m.pos = p.pos; m.is_rev = p.is_rev; m.n_cigar = 0; }
 	p.flag |= m0 && m.is_rev ? 0x20 : 0;
+	if (D->ctx->md_dup) p.flag |= 0x400;   /* every record of a duplicate template (markdup.c) */
 
 	sb_puts(str, s->name);
 	if (s->comment) { sb_putc(str, '_'); sb_puts(str, s->comment); }

@@ -50,6 +50,8 @@ static knob_t g_knobs[] = {
 	{"tier2_export", "[0] the first HBM tier of the region kernels in steps -- chains exported, seeds extended ahead (k_extl / k_ext4; 1: every chain's best seed, 2: every seed of every main list), the seed loop by a chains -> regions launch with its regions in HBM -- instead of its monolithic form (same SAM; measured no faster, DESIGN.md section 4)", 0},
 	{"msw_plan", "[0] 1: mate rescue's plan pass (which candidates need an alignment, over which window) by k_msw_plan over the lists on the device, its K5 batch run from device memory, instead of by the host's first replay pass (same SAM; measured slower, DESIGN.md section 4)", 0},
 	{"long_dedup", "[1] 0: reads with more than 32 regions are de-duplicated on the host (A/B against k_dedup_long)", 0},
+	{"markdup_slots", "[32 per key of the first batch, at least 65536] slots of the first table of template keys (--markdup), a power of two; it doubles before a batch would load it beyond one half", 0},
+	{"markdup_hash_bits", "[64] tests: low bits kept of a template key's claim word (different keys then meet in one slot and take the next salt)", 0},
 };
 #define N_KNOBS ((int)(sizeof(g_knobs) / sizeof(g_knobs[0])))
 static pthread_mutex_t g_mu = PTHREAD_MUTEX_INITIALIZER;

@@ -348,6 +348,42 @@ int bsx_qc_batch(bsx_device_t *dev, int64_t n, const bsx_qc_job_t *jobs, const u
 /* waits for the batches in flight and copies the table out; reset != 0 zeroes it */
 int bsx_qc_read(bsx_device_t *dev, bsx_qc_counts_t *out, int reset);
 
+/* Duplicate templates (k_markdup.hip): a table of template keys that stays on the device until bsx_markdup_reset or bsx_device_close.
+ * A key is the ordered pair of the template's ends, w[0] = read 1 (or the single read), w[1] = read 2; an end that is not placed (its primary
+ * record has 0x4) is 0, the second end of a single read is BSX_MD_SINGLE: a single read never equals a pair, not even one whose read 2 is not
+ * placed.  A placed end is BSX_MD_END(contig, u5, reverse, yd):
+ *   bit 63      placed
+ *   bit 62      0x10 of the end's primary record
+ *   bit 61      1 when the record's YD tag is r (f and u: 0)
+ *   bits 33-60  index of the contig (below 2^28)
+ *   bits 0-32   u5 + BSX_MD_U5_BIAS, u5 = the unclipped 5' coordinate, 1-based like POS: POS - (leading S + leading H) on a forward record,
+ *               POS + reflen - 1 + (trailing S + trailing H) on a reverse one (reflen: the M, D, N, =, X operations); it may be 0, negative
+ *               or beyond the contig's end
+ * The key with both words all ones means "no placed end": bsx_markdup_batch skips it and it never enters the table. */
+typedef struct bsx_markdup_key { uint64_t w[2]; } bsx_markdup_key_t;
+#define BSX_MD_PLACED   (1ull << 63)
+#define BSX_MD_REVERSE  (1ull << 62)
+#define BSX_MD_YD       (1ull << 61)
+#define BSX_MD_U5_BIAS  ((int64_t)1 << 32)
+#define BSX_MD_SINGLE   1ull
+#define BSX_MD_END(contig, u5, reverse, yd) (BSX_MD_PLACED | ((reverse) ? BSX_MD_REVERSE : 0) | ((yd) ? BSX_MD_YD : 0) | \
+	((uint64_t)(contig) & 0xfffffffull) << 33 | ((uint64_t)((int64_t)(u5) + BSX_MD_U5_BIAS) & 0x1ffffffffull))
+/* keys[i] is the template with ordinal first_ordinal + i.  dup_out[i] = 1 when an equal key (all 128 bits) with a lower ordinal is in the
+ * table or earlier in this batch, else 0 (also for a skipped key); within a batch the lowest ordinal is the one that stays unmarked however
+ * the lanes interleave, between batches the order is the caller's: ordinals must not decrease from one batch to the next.  The table grows
+ * (twice the slots, every slot moved by k_md_rehash) before a batch would load it beyond one half; BSX_E_NOMEM when the larger table cannot
+ * be had, with the size in the message.  The table in use is kept; keys the batch inserted before it failed (in an earlier salt round) stay
+ * in it, so the batch is lost and so is the run's marking: reset before marking again.  "markdup_slots" (bsx_tune_set) is the first table's
+ * capacity (a power of two; default: 32 slots per key of the first batch, at least 65536).  The claim word of a key is bsx_markdup_hash(key,
+ * salt, bits): salt 0 first; a key that meets another key with its claim word tries salt + 1, eight salts at most (BSX_E_INTERNAL beyond);
+ * "markdup_hash_bits" (default 64) keeps only the low bits of the claim word, so that tests can make such meetings happen. */
+int bsx_markdup_batch(bsx_device_t *dev, int64_t n, const bsx_markdup_key_t *keys, uint64_t first_ordinal, uint8_t *dup_out);
+int bsx_markdup_reset(bsx_device_t *dev);   /* an empty table of the initial capacity */
+/* For tests and diagnostics, not part of the marking seam: slots of the device's table and how many are taken (0, 0 before the first batch);
+ * the claim word of a key (csrc/host/markdup_hash.h). */
+int bsx_markdup_table_info(bsx_device_t *dev, uint64_t *n_slots, uint64_t *n_used);
+uint64_t bsx_markdup_hash(const bsx_markdup_key_t *key, uint32_t salt, int bits);
+
 /* Settings of the library that never change its output (launch shapes, table sizes, which of two equivalent paths runs: what the tests and
  * the A/B tools switch).  One registry (csrc/host/tune.c has the table of names): bsx_tune_set(name, value) between calls of the library
  * (value NULL: back to the default; BSX_E_ARG for an unknown name), or "$BSX_TUNE=name=value,name=value" for a whole process.  bsx_phases():
@@ -487,7 +523,7 @@ typedef struct bsx_qc_totals {
 	uint64_t mapq[BSX_QC_N_MAPQ + 1];       /* non-secondary records by MAPQ; [61]: unmapped */
 	uint64_t isize[BSX_QC_ISIZE + 1];       /* proper pair, MAPQ >= 40, 0 <= TLEN <= 1000, non-secondary */
 	uint64_t n_isize;
-	uint64_t all_tot, all_dup, q40_tot, q40_dup;   /* the two duplicate counts stay 0: no record carries 0x400 */
+	uint64_t all_tot, all_dup, q40_tot, q40_dup;   /* the two duplicate counts: records written with 0x400 (only --markdup sets it: 0 without) */
 	uint64_t strandcnt[16];                 /* [(no 0x40) * 8 + reverse * 4 + YD tag] over mapped records */
 } bsx_qc_totals_t;
 /* on != 0: count from the next chunk on, totals from zero.  A stream's own setting takes its chunks out of the process's.  The device's table
@@ -499,6 +535,22 @@ int  bsx_process_qc_totals(bsx_qc_totals_t *out, int reset);        /* while the
 /* PREFIX_mapq_table.txt, _dup_report.txt, _strand_table.txt, _totalReadConversionRate.txt, _CpGRetentionByReadPos.txt, _CpHRetentionByReadPos.txt
  * and, with paired != 0, _isize_table.txt: the formatters of src/qc.c:29-110, byte for byte */
 int  bsx_qc_write(const char *prefix, const bsx_qc_totals_t *t, int paired);
+
+/* Duplicate marking while aligning (--markdup).  A template is one unit of the input, a pair or a single read; its ordinal is its 0-based index
+ * in the input of the stream (or of the process) over all chunks.  Each end's primary record is the one with neither 0x100 nor 0x800; the
+ * template's key is bsx_markdup_key_t over them.  A template with no placed end is never a duplicate and never enters the table.  A template
+ * is a duplicate when a template with a lower ordinal has an equal key: every record written for it -- primary, secondary, supplementary, an
+ * unplaced mate's -- gets 0x400, and nothing else in any record changes.  The decision is made once the CIGARs are final and before bsconv's
+ * filters: a template whose records are all dropped still holds its key.  Barcodes, read groups and optical distance are not part of the key,
+ * and single-end templates are never compared against pairs, whether both reads of the pair are placed or one (both unlike dupsifter).  Keys are looked up on the device (bsx_markdup_batch),
+ * one batch per slice of a chunk, in input order; a backend without markdup_batch uses a table on the host with the same rule.
+ * The device's table is one per device: one stream (or the process) at a time marks on a device.  A stream's or the process's first chunk
+ * after set_markdup(1) empties the backend's table, so a device kept open over two runs starts the second one with an empty table. */
+typedef struct bsx_markdup_totals { uint64_t n_templates, n_keyed, n_dup; } bsx_markdup_totals_t;   /* seen, with a placed end, marked */
+int  bsx_stream_set_markdup(bsx_stream_t *s, int on);                  /* before the first push */
+int  bsx_stream_markdup_totals(bsx_stream_t *s, bsx_markdup_totals_t *out);   /* after bsx_stream_flush */
+int  bsx_process_set_markdup(int on);                                  /* on != 0: from the next chunk on, ordinals and totals from zero */
+int  bsx_process_markdup_totals(bsx_markdup_totals_t *out, int reset);
 
 /* `biscuit align` command line: main_align (lib/aln/align.c:319-598).  SAM on `out` (stdout). */
 int bsx_align_main(int argc, char **argv);
