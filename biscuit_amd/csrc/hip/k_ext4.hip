@@ -506,9 +506,9 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 	}
 	if (prof) { // tracing: jobs, rows, trips (a trip advances up to four rows) and passes through the block between extensions
 		pf_rows = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_rows : 0); pf_jobs = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_jobs : 0);
-		if (lane == 0) { atomicAdd(&prof[0], (unsigned long long)pf_jobs); atomicAdd(&prof[1], (unsigned long long)pf_rows); atomicAdd(&prof[2], (unsigned long long)pf_trips); atomicAdd(&prof[3], (unsigned long long)pf_cold); atomicAdd(&prof[4], (unsigned long long)pf_slots); }
+		if (lane == 0) { atomicAdd(&prof[EXT4_JOBS], (unsigned long long)pf_jobs); atomicAdd(&prof[EXT4_ROWS], (unsigned long long)pf_rows); atomicAdd(&prof[EXT4_TRIPS], (unsigned long long)pf_trips); atomicAdd(&prof[EXT4_COLD], (unsigned long long)pf_cold); atomicAdd(&prof[EXT4_SLOTS], (unsigned long long)pf_slots); }
 		pf_nrows = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_nrows : 0);
-		if (lane == 0) atomicAdd(&prof[5], (unsigned long long)pf_nrows);
+		if (lane == 0) atomicAdd(&prof[EXT4_NARROW_ROWS], (unsigned long long)pf_nrows);
 	}
 }
 
@@ -528,10 +528,11 @@ void launch_ext4_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevSc
 }
 
 // The extensions of the chains the tiers exported (records with has_ext), ahead of launch_c2r: k_x4prep lists the jobs (ctr32[0], [2] = their
-// numbers, ctr32[1] = k_ext4's cursor: zeroed here), k_ext4 runs them.  n_tasks bounds the number of exported strand searches.
-void launch_x4(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, const bsx_seed_task_t *tasks,
-               long long n_tasks, const RgXPoolArg &XA, void *jobs, unsigned long long job_cap, unsigned int *ctr32, unsigned long long *prof)
+// numbers, ctr32[1] = k_ext4's cursor: zeroed here), k_ext4 runs them.  G.n_tasks bounds the number of exported strand searches.
+void launch_x4(hipStream_t st, int n_cu, const RgLaunch &G, const RgXPoolArg &XA, void *jobs, unsigned long long job_cap, unsigned int *ctr32, unsigned long long *prof)
 {
+	const DevIndex &ix = *G.ix; const DevScoring &sc = *G.sc; const RegParams &P = *G.P;
+	const uint8_t *reads = G.reads; const bsx_seed_task_t *tasks = G.tasks; const long long n_tasks = G.n_tasks;
 	RgXPool X = rgx_pool(&XA);
 	const unsigned int jcap = (unsigned int)std::min<unsigned long long>(job_cap, 0xfffffff0ull);
 	const int pgrid = (int)((n_tasks + 64 * X4P_WPB - 1) / (64 * X4P_WPB));

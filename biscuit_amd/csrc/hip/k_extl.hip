@@ -328,7 +328,7 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 	}
 	if (prof) {
 		const unsigned int r = (unsigned int)wave_sum_i32((int)pf_rows), jb = (unsigned int)wave_sum_i32((int)pf_jobs), bl = (unsigned int)wave_sum_i32((int)pf_bail);
-		if (lane == 0) { atomicAdd(&prof[6], (unsigned long long)jb); atomicAdd(&prof[7], (unsigned long long)r); atomicAdd(&prof[8], (unsigned long long)pf_trips); atomicAdd(&prof[9], (unsigned long long)pf_cold); atomicAdd(&prof[10], (unsigned long long)bl); }
+		if (lane == 0) { atomicAdd(&prof[EXTL_JOBS], (unsigned long long)jb); atomicAdd(&prof[EXTL_ROWS], (unsigned long long)r); atomicAdd(&prof[EXTL_TRIPS], (unsigned long long)pf_trips); atomicAdd(&prof[EXTL_COLD], (unsigned long long)pf_cold); atomicAdd(&prof[EXTL_SENT_ON], (unsigned long long)bl); }
 	}
 }
 

@@ -90,11 +90,11 @@ typedef RgStore<4096, 8192, 8192, 8192, 8192, unsigned short, short> RgHuge;   /
 // divergent region inside the stages.  Round 5: `if (P.prof) { ...; if (lane == 0) atomicAdd(&counters[..], ..); }` ahead of the (not inlined)
 // call of rg_export made the compiler place a copy of the lane index for the call AHEAD of the s_or_b64 that restores EXEC at the end of the
 // lane-0 region -- 63 lanes entered rg_export with a stale lane index and exported garbage (tools/dbg/exec_join_check.py looks for that shape
-// in the assembly; tests/test_isa_exec_join.py).  Flushed to counters[32 + k] once, when the wave leaves the kernel.
+// in the assembly; tests/test_isa_exec_join.py).  Flushed to counters[CTR_STAGE + k] once, when the wave leaves the kernel.
 #define RG_NPF 16            // 0-7 stage cycles, 8 extensions, 9 extension rows
 #define RG_PF_ZERO(D) do { if (P.prof) { (D).pf[lane & (RG_NPF - 1)] = 0; WAVE_SYNC(); } } while (0)
 #define RG_PF_ADD(D, k, v) do { const unsigned long long s_ = (D).pf[k] + (unsigned long long)(v); (D).pf[k] = s_; } while (0)
-#define RG_PF_FLUSH(D) do { if (P.prof) { WAVE_SYNC(); if (lane < RG_NPF) { const unsigned long long v_ = (D).pf[lane]; if (v_) atomicAdd(&counters[32 + lane], v_); } } } while (0)
+#define RG_PF_FLUSH(D) do { if (P.prof) { WAVE_SYNC(); if (lane < RG_NPF) { const unsigned long long v_ = (D).pf[lane]; if (v_) atomicAdd(&counters[CTR_STAGE + lane], v_); } } } while (0)
 struct RgDp {            // per-wave LDS scratch
 	static const int QCAP = RG_QCAP;
 	unsigned long long pf[RG_NPF];
@@ -602,7 +602,7 @@ __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc
 		}
 		// work counters of the algorithmic-bytes model: FM blocks touched by the LF walks, SA samples read
 		lf = (uint32_t)wave_sum_i32((int)lf);
-		if (lane == 0 && !posl) { atomicAdd(&counters[2], (unsigned long long)lf); atomicAdd(&counters[3], (unsigned long long)tot); }
+		if (lane == 0 && !posl) { atomicAdd(&counters[CTR_LF_STEPS], (unsigned long long)lf); atomicAdd(&counters[CTR_LF_CALLS], (unsigned long long)tot); }
 	}
 	WAVE_SYNC();
 	// asymmetric_flt_seed (memchain.c:138-149) for every seed at once, a lane per seed: a reference T under a read C or a reference A
@@ -1924,7 +1924,7 @@ k_seedsw_apply(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, co
 			}
 		}
 	}
-	if (P.prof && lane == 0 && n_sw) atomicAdd(&counters[42], (unsigned long long)n_sw);
+	if (P.prof && lane == 0 && n_sw) atomicAdd(&counters[CTR_STAGE_SEEDSW], (unsigned long long)n_sw);
 }
 
 #ifndef C2R_WPB
@@ -1991,7 +1991,7 @@ k_c2r(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const bsx_s
 			}
 			reg_off[t] = (long long)base;
 			reg_n[t] = status ? -status : nr;
-			if (next_list && (status == 2 || status == 6)) { next_list[atomicAdd(next_count, 1u)] = t; if (P.prof) atomicAdd(counters + 160 + status, 1ull); }
+			if (next_list && (status == 2 || status == 6)) { next_list[atomicAdd(next_count, 1u)] = t; if (P.prof) atomicAdd(counters + CTR_HANDON + status, 1ull); }
 		}
 		WAVE_SYNC();
 	}
@@ -2124,13 +2124,13 @@ k_regions_slab(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, co
 		}
 		if (P.prof && lane == 0) { // $BSX_PHASES: the longest strand search of the launch, their sum and number, the busiest wave
 			const unsigned long long dt = (unsigned long long)((long long)__builtin_readcyclecounter() - tk0);
-			unsigned long long *c = counters + (Store::SCAP > 1024 ? 114 : 110);
+			unsigned long long *c = counters + (Store::SCAP > 1024 ? CTR_TIER3_TIME : CTR_TIER2_TIME);
 			atomicMax(c, dt); atomicAdd(c + 1, dt); atomicAdd(c + 2, 1ull); wave_cyc += dt;
 			if (Store::SCAP > 1024) { // the last tier: its strand searches by duration (powers of two of 2^16 cycles), and what the longest one looked like
 				const unsigned long long b = dt >> 16;
-				atomicAdd(counters + 130 + (b ? 64 - __builtin_clzll(b) : 0), 1ull);
+				atomicAdd(counters + CTR_T3_HIST + (b ? 64 - __builtin_clzll(b) : 0), 1ull);
 				const unsigned long long nk_ = (unsigned long long)(S.n_chains < 0 ? 0 : S.n_chains > 16383 ? 16383 : S.n_chains), nr_ = (unsigned long long)(S.n_regs < 0 ? 0 : S.n_regs > 16383 ? 16383 : S.n_regs);
-				atomicMax(counters + 128, (dt >> 14) << 38 | (unsigned long long)(n_iv > 4095 ? 4095 : n_iv) << 26 | (nk_ & 8191) << 13 | (nr_ & 8191));
+				atomicMax(counters + CTR_T3_LONGEST, (dt >> 14) << 38 | (unsigned long long)(n_iv > 4095 ? 4095 : n_iv) << 26 | (nk_ & 8191) << 13 | (nr_ & 8191));
 			}
 		}
 		if (status == 11) continue;   // exported (XSPLIT: chunks with long reads, whose chains go through k_seedsw and k_c2r)
@@ -2138,7 +2138,7 @@ k_regions_slab(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, co
 		if (next_list && (status == 8 || status == 2 || status == 3 || status == 4 || status == 6) && lane == 0) next_list[atomicAdd(next_count, 1u)] = t;
 	}
 	RG_PF_FLUSH(D);
-	if (P.prof && lane == 0 && wave_cyc) atomicMax(counters + (Store::SCAP > 1024 ? 117 : 113), wave_cyc);
+	if (P.prof && lane == 0 && wave_cyc) atomicMax(counters + (Store::SCAP > 1024 ? CTR_TIER3_TIME : CTR_TIER2_TIME) + 3, wave_cyc);
 }
 
 // Between the first tier and the HBM tiers: the same tables four times larger, still in LDS (two waves per workgroup, three
@@ -2188,7 +2188,7 @@ k_regions_mid(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, con
 		status = rg_publish(S, t, status, out, out_cap, out_cursor, reg_off, reg_n, lane);
 		if ((status == 8 || status == 2 || status == 3 || status == 4 || status == 6 || status == 10) && lane == 0) {
 			next_list[atomicAdd(next_count, 1u)] = t;
-			if (P.prof) atomicAdd(counters + 160 + status, 1ull);   // ($BSX_PHASES=2: why this tier hands a strand search on)
+			if (P.prof) atomicAdd(counters + CTR_HANDON + status, 1ull);   // ($BSX_PHASES=2: why this tier hands a strand search on)
 		}
 	}
 	RG_PF_FLUSH(D);
@@ -2255,16 +2255,15 @@ k_occ(DevIndex ix, unsigned long long *desc, unsigned long long desc_cap, const 
 		++calls;
 	}
 	for (int off = 32; off > 0; off >>= 1) { lf += __shfl_down(lf, off); calls += __shfl_down(calls, off); }
-	if ((threadIdx.x & 63) == 0) { atomicAdd(&counters[2], (unsigned long long)lf); atomicAdd(&counters[3], (unsigned long long)calls); }
+	if ((threadIdx.x & 63) == 0) { atomicAdd(&counters[CTR_LF_STEPS], (unsigned long long)lf); atomicAdd(&counters[CTR_LF_CALLS], (unsigned long long)calls); }
 }
 
-void launch_occ(hipStream_t st, int n_cu, const DevIndex &ix, const bsx_seed_task_t *tasks, int n_tasks, const DevIntv *seeds_dense, const long long *task_off,
-                const int *task_n, int max_occ, unsigned long long *desc, unsigned long long desc_cap, unsigned long long *cursor, long long *pos_off,
-                unsigned long long *counters, unsigned char *cls, unsigned long long *start, int *early_list, unsigned int *early_count)
+void launch_occ(hipStream_t st, int n_cu, const RgLaunch &G, int max_occ, unsigned long long desc_cap, unsigned long long *cursor, unsigned char *cls,
+                unsigned long long *start, int *early_list, unsigned int *early_count)
 {
 	if (start) (void)hipMemcpyAsync(start, cursor, 8, hipMemcpyDeviceToDevice, st);   // a later launch over the same pool: only the ranks it adds
-	hipLaunchKernelGGL(k_occ_expand, dim3((n_tasks + 255) / 256), dim3(256), 0, st, tasks, n_tasks, seeds_dense, task_off, task_n, max_occ, desc, desc_cap, cursor, pos_off, cls, early_list, early_count);
-	hipLaunchKernelGGL(k_occ, dim3(n_cu * 32), dim3(256), 0, st, ix, desc, desc_cap, cursor, counters, (const unsigned long long*)start);
+	hipLaunchKernelGGL(k_occ_expand, dim3((G.n_tasks + 255) / 256), dim3(256), 0, st, G.tasks, G.n_tasks, G.seeds_dense, G.task_off, G.task_n, max_occ, G.pos, desc_cap, cursor, G.pos_off, cls, early_list, early_count);
+	hipLaunchKernelGGL(k_occ, dim3(n_cu * 32), dim3(256), 0, st, *G.ix, G.pos, desc_cap, cursor, G.counters, (const unsigned long long*)start);
 }
 
 // The index files sample the suffix array every 32nd rank (bwtindex.c:328,340), which makes bwt_sa a walk of 31 LF steps
@@ -2316,94 +2315,76 @@ void launch_order_list(hipStream_t st, int *list, const unsigned int *count, con
 }
 
 size_t regions_slab_bytes(int tier) { return tier == 2 ? sizeof(RgBig) : sizeof(RgHuge); }
-size_t c2r_hbm_slab_bytes(void) { return RgC2rH::slab_bytes() * C2R_WPB; }   // per workgroup of launch_c2r(.., long_reads = 3)
+size_t c2r_hbm_slab_bytes(void) { return RgC2rH::slab_bytes() * C2R_WPB; }   // per workgroup of launch_c2r(.., RG_C2R_H / RG_C2R_HL)
 
-void launch_regions(hipStream_t st, int grid, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads,
-                    const bsx_seed_task_t *tasks, int n_tasks, const DevIntv *seeds_dense, const long long *task_off, const int *task_n,
-                    bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
-                    unsigned int *task_cursor, int *retry_list, unsigned int *retry_count, int quota, unsigned long long *counters,
-                    const long long *pos_off, const unsigned long long *pos, const unsigned char *cls, const RgXPoolArg &XA, int long_reads)
+// the launchers unpack the common arguments (RgLaunch) into the kernels' parameter lists
+#define RG_COMMON_ *G.ix, *G.sc, *G.P, G.reads, G.tasks
+#define RG_LISTS_  G.seeds_dense, G.task_off, G.task_n
+#define RG_OUT_    G.out, G.out_cap, G.out_cursor, G.reg_off, G.reg_n
+#define RG_POS_    G.counters, (const long long*)G.pos_off, (const unsigned long long*)G.pos
+void launch_regions(hipStream_t st, int grid, const RgLaunch &G, unsigned int *task_cursor, int *retry_list, unsigned int *retry_count, int quota,
+                    const unsigned char *cls, const RgXPoolArg &XA, bool long_reads)
 {
 	RgXPool X = rgx_pool(&XA);
 	const int occ = (int)bsx_tune_long("regions_occ", 5);   // waves per SIMD the register allocation targets (the tables in LDS allow five workgroups per CU)
-	if (long_reads)
-		hipLaunchKernelGGL((k_regions<3, RgDpLiteL>), dim3(grid * (4 / RG_WPB)), dim3(64 * RG_WPB), 0, st, ix, sc, P, reads, tasks, n_tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, task_cursor, retry_list, retry_count, quota, counters, pos_off, pos, cls, X);
-	else if (occ >= 5)
-		hipLaunchKernelGGL((k_regions<5, RgDpLite>), dim3(grid * (4 / RG_WPB)), dim3(64 * RG_WPB), 0, st, ix, sc, P, reads, tasks, n_tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, task_cursor, retry_list, retry_count, quota, counters, pos_off, pos, cls, X);
-	else if (occ >= 4)
-		hipLaunchKernelGGL((k_regions<4, RgDpLite>), dim3(grid * (4 / RG_WPB)), dim3(64 * RG_WPB), 0, st, ix, sc, P, reads, tasks, n_tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, task_cursor, retry_list, retry_count, quota, counters, pos_off, pos, cls, X);
-	else
-		hipLaunchKernelGGL((k_regions<3, RgDpLite>), dim3(grid * (4 / RG_WPB)), dim3(64 * RG_WPB), 0, st, ix, sc, P, reads, tasks, n_tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, task_cursor, retry_list, retry_count, quota, counters, pos_off, pos, cls, X);
+#define RG_T1_(OCC, DP) hipLaunchKernelGGL((k_regions<OCC, DP>), dim3(grid * (4 / RG_WPB)), dim3(64 * RG_WPB), 0, st, RG_COMMON_, G.n_tasks, RG_LISTS_, \
+	                                   RG_OUT_, task_cursor, retry_list, retry_count, quota, RG_POS_, cls, X)
+	if (long_reads) RG_T1_(3, RgDpLiteL);
+	else if (occ >= 5) RG_T1_(5, RgDpLite);
+	else if (occ >= 4) RG_T1_(4, RgDpLite);
+	else RG_T1_(3, RgDpLite);
+#undef RG_T1_
 }
 
-void launch_regions_mid(hipStream_t st, int grid, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads,
-                        const bsx_seed_task_t *tasks, const DevIntv *seeds_dense, const long long *task_off, const int *task_n,
-                        bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
-                        const int *list, const unsigned int *count, unsigned int *cursor, int *next_list, unsigned int *next_count,
-                        unsigned long long *counters, const long long *pos_off, const unsigned long long *pos, const RgXPoolArg &XA, int quota, int long_reads)
+void launch_regions_mid(hipStream_t st, int grid, const RgLaunch &G, const int *list, const unsigned int *count, unsigned int *cursor,
+                        int *next_list, unsigned int *next_count, const RgXPoolArg &XA, int quota, RgMidForm form)
 {
 	RgXPool X = rgx_pool(&XA);
-	if (long_reads == 3)   // kilobase reads, the larger of the two table sizes
-		hipLaunchKernelGGL((k_regions_mid<RgLongB, RgDpLiteL, 1, 1>), dim3(grid * 2), dim3(64), 0, st, ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, next_list, next_count, counters, pos_off, pos, X, quota);
-	else if (long_reads == 4)   // reads of ordinary length: twice RgMid's tables, the tier behind it
-		hipLaunchKernelGGL((k_regions_mid<RgMid2, RgDpLite, 1, 2>), dim3(grid * 2), dim3(64), 0, st, ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, next_list, next_count, counters, pos_off, pos, X, quota);
-	else if (long_reads == 2)   // the larger tables for reads of ordinary length (the tier behind k_regions_mid<RgMid>)
-		hipLaunchKernelGGL((k_regions_mid<RgLongB, RgDpLite, 1, 1>), dim3(grid * 2), dim3(64), 0, st, ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, next_list, next_count, counters, pos_off, pos, X, quota);
-	else if (long_reads)   // tables for a kilobase read, one wave per workgroup
-		hipLaunchKernelGGL((k_regions_mid<RgLongS, RgDpLiteL, 1, 1>), dim3(grid * 2), dim3(64), 0, st, ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, next_list, next_count, counters, pos_off, pos, X, quota);
-	else
-	hipLaunchKernelGGL((k_regions_mid<RgMid, RgDpLite, MID_WPB, 2>), dim3(grid * (2 / MID_WPB)), dim3(64 * MID_WPB), 0, st, /* `grid` counts pairs of waves */ ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-	                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, next_list, next_count, counters, pos_off, pos, X, quota);
+	// `grid` counts pairs of waves
+#define RG_MID_(TAB, DP, WPB, OCC) hipLaunchKernelGGL((k_regions_mid<TAB, DP, WPB, OCC>), dim3(grid * (2 / WPB)), dim3(64 * WPB), 0, st, RG_COMMON_, RG_LISTS_, \
+	                                              RG_OUT_, list, count, cursor, next_list, next_count, RG_POS_, X, quota)
+	switch (form) {
+	case RG_MID_LONGB_L: RG_MID_(RgLongB, RgDpLiteL, 1, 1); break;
+	case RG_MID2:        RG_MID_(RgMid2, RgDpLite, 1, 2); break;
+	case RG_MID_LONGB:   RG_MID_(RgLongB, RgDpLite, 1, 1); break;
+	case RG_MID_LONGS:   RG_MID_(RgLongS, RgDpLiteL, 1, 1); break;
+	case RG_MID:         RG_MID_(RgMid, RgDpLite, MID_WPB, 2); break;
+	}
+#undef RG_MID_
 }
-void launch_c2r(hipStream_t st, int grid, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, const bsx_seed_task_t *tasks,
-                const RgXPoolArg &XA, bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
-                unsigned int *cursor, int *next_list, unsigned int *next_count, unsigned long long *counters, int quota, int long_reads, void *slab)
+void launch_c2r(hipStream_t st, int grid, const RgLaunch &G, const RgXPoolArg &XA, unsigned int *cursor, int *next_list, unsigned int *next_count,
+                int quota, RgC2rForm form, void *slab)
 {
 	RgXPool X = rgx_pool(&XA);
-	if (long_reads == 4)   // chunks with long reads: what k_c2r<RgC2rL> declines
-		hipLaunchKernelGGL((k_c2r<RgC2rHL, 1>), dim3(grid), dim3(64 * C2R_WPB), 0, st, ix, sc, P, reads, tasks, X, out, out_cap, out_cursor, reg_off, reg_n, cursor, next_list, next_count, counters, quota, (unsigned char*)slab);
-	else if (long_reads == 3)   // ... and what that one declines too: the large tables in HBM (`slab`: c2r_hbm_slab_bytes() per wave of the grid)
-		hipLaunchKernelGGL((k_c2r<RgC2rH, 2>), dim3(grid), dim3(64 * C2R_WPB), 0, st, ix, sc, P, reads, tasks, X, out, out_cap, out_cursor, reg_off, reg_n, cursor, next_list, next_count, counters, quota, (unsigned char*)slab);
-	else if (long_reads == 2)   // ordinary reads with many regions or long seed lists: the strand searches k_c2r<RgC2r> declined (X names them)
-		hipLaunchKernelGGL((k_c2r<RgC2rB, 2>), dim3(grid * (4 / C2R_WPB)), dim3(64 * C2R_WPB), 0, st, ix, sc, P, reads, tasks, X, out, out_cap, out_cursor, reg_off, reg_n, cursor, next_list, next_count, counters, quota, (unsigned char*)nullptr);
-	else if (long_reads)
-		hipLaunchKernelGGL((k_c2r<RgC2rL, 3>), dim3(grid * (4 / C2R_WPB)), dim3(64 * C2R_WPB), 0, st, ix, sc, P, reads, tasks, X, out, out_cap, out_cursor, reg_off, reg_n, cursor, next_list, next_count, counters, quota, (unsigned char*)nullptr);
-	else
-	hipLaunchKernelGGL((k_c2r<RgC2r, 4>), dim3(grid * (4 / C2R_WPB)), dim3(64 * C2R_WPB), 0, st, /* `grid` counts groups of four waves */ ix, sc, P, reads, tasks, X, out, out_cap, out_cursor, reg_off, reg_n, cursor, next_list, next_count, counters, quota, (unsigned char*)nullptr);
+	// the forms with their tables in LDS: `grid` counts groups of four waves; in HBM: workgroups, with c2r_hbm_slab_bytes() of `slab` each
+#define RG_C2R_(TAB, OCC, GRID, SLAB) hipLaunchKernelGGL((k_c2r<TAB, OCC>), dim3(GRID), dim3(64 * C2R_WPB), 0, st, RG_COMMON_, X, RG_OUT_, cursor, next_list, next_count, G.counters, quota, (unsigned char*)(SLAB))
+	switch (form) {
+	case RG_C2R_HL: RG_C2R_(RgC2rHL, 1, grid, slab); break;
+	case RG_C2R_H:  RG_C2R_(RgC2rH, 2, grid, slab); break;
+	case RG_C2R_B:  RG_C2R_(RgC2rB, 2, grid * (4 / C2R_WPB), nullptr); break;
+	case RG_C2R_L:  RG_C2R_(RgC2rL, 3, grid * (4 / C2R_WPB), nullptr); break;
+	case RG_C2R:    RG_C2R_(RgC2r, 4, grid * (4 / C2R_WPB), nullptr); break;
+	}
+#undef RG_C2R_
 }
-void launch_regions_slab(hipStream_t st, int tier, int grid, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads,
-                         const bsx_seed_task_t *tasks, const DevIntv *seeds_dense, const long long *task_off, const int *task_n,
-                         bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
-                         const int *list, const unsigned int *count, unsigned int *cursor, void *slabs, int *next_list, unsigned int *next_count,
-                         unsigned long long *counters, const long long *pos_off, const unsigned long long *pos, const RgXPoolArg *XA)
+void launch_regions_slab(hipStream_t st, int tier, int grid, const RgLaunch &G, const int *list, const unsigned int *count, unsigned int *cursor,
+                         void *slabs, int *next_list, unsigned int *next_count, const RgXPoolArg *XA)
 {
 	RgXPool X = rgx_pool(XA);
 	// XA given: the tier stops after the chain filter and exports (chunks with long reads or an active seed-SW filter)
-	if (tier == 2 && XA)
-		hipLaunchKernelGGL((k_regions_slab<RgBig, true, RgDpLiteL>), dim3(grid), dim3(256), 0, st, ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, (RgBig*)slabs, next_list, next_count, counters, pos_off, pos, X);
-	else if (tier == 2)
-		hipLaunchKernelGGL((k_regions_slab<RgBig, false, RgDp>), dim3(grid), dim3(256), 0, st, ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, (RgBig*)slabs, next_list, next_count, counters, pos_off, pos, X);
-	else if (XA)
-		hipLaunchKernelGGL((k_regions_slab<RgHuge, true, RgDpLiteL>), dim3(grid), dim3(256), 0, st, ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, (RgHuge*)slabs, next_list, next_count, counters, pos_off, pos, X);
-	else
-		hipLaunchKernelGGL((k_regions_slab<RgHuge, false, RgDp>), dim3(grid), dim3(256), 0, st, ix, sc, P, reads, tasks, seeds_dense, task_off, task_n,
-		                   out, out_cap, out_cursor, reg_off, reg_n, list, count, cursor, (RgHuge*)slabs, next_list, next_count, counters, pos_off, pos, X);
+#define RG_SLAB_(TAB, EXPORTS, DP) hipLaunchKernelGGL((k_regions_slab<TAB, EXPORTS, DP>), dim3(grid), dim3(256), 0, st, RG_COMMON_, RG_LISTS_, \
+	                                              RG_OUT_, list, count, cursor, (TAB*)slabs, next_list, next_count, RG_POS_, X)
+	if (tier == 2 && XA) RG_SLAB_(RgBig, true, RgDpLiteL);
+	else if (tier == 2) RG_SLAB_(RgBig, false, RgDp);
+	else if (XA) RG_SLAB_(RgHuge, true, RgDpLiteL);
+	else RG_SLAB_(RgHuge, false, RgDp);
+#undef RG_SLAB_
 }
 size_t seedsw_job_bytes(void) { return sizeof(SswJob) + sizeof(int); }   // a job and its score
-void launch_seedsw(hipStream_t st, int grid, int n_cu, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, const bsx_seed_task_t *tasks,
-                   const RgXPoolArg &XA, unsigned int *cursor, unsigned int *count_cursor, void *jobs, unsigned int job_cap, unsigned long long *counters)
+void launch_seedsw(hipStream_t st, int grid, int n_cu, const RgLaunch &G, const RgXPoolArg &XA, unsigned int *cursor, unsigned int *count_cursor,
+                   void *jobs, unsigned int job_cap)
 {   // cursor: k_seedsw_prep's; count_cursor: [0] the job count [1] k_seedsw_apply's cursor (zeroed by the caller)
+	const DevIndex &ix = *G.ix; const DevScoring &sc = *G.sc;
 	RgXPool X = rgx_pool(&XA);
 	SswJob *J = (SswJob*)jobs;
 	int *scores = (int*)(J + job_cap);
@@ -2419,9 +2400,13 @@ void launch_seedsw(hipStream_t st, int grid, int n_cu, const DevIndex &ix, const
 		const int oe = (sc.o_del + sc.e_del > sc.o_ins + sc.e_ins ? sc.o_del + sc.e_del : sc.o_ins + sc.e_ins), e = sc.e_del > sc.e_ins ? sc.e_del : sc.e_ins;
 		if (199LL * mx + 7LL * 25 * e + 2LL * oe + bias >= 32768 || mx + bias > 255 || oe >= 32768) job_cap = 0;
 	}
-	hipLaunchKernelGGL(k_seedsw_prep, dim3(grid), dim3(64), 0, st, ix, tasks, X, cursor, J, job_cap, count_cursor);
-	if (sc.o_del == sc.o_ins && sc.e_del == sc.e_ins) hipLaunchKernelGGL(k_swl16<true>, dim3(n_cu * 8), dim3(256), 0, st, ix, sc, reads, (const SswJob*)J, (const unsigned int*)count_cursor, job_cap, scores);
-	else hipLaunchKernelGGL(k_swl16<false>, dim3(n_cu * 8), dim3(256), 0, st, ix, sc, reads, (const SswJob*)J, (const unsigned int*)count_cursor, job_cap, scores);
-	hipLaunchKernelGGL(k_seedsw_apply, dim3(grid), dim3(64), 0, st, ix, sc, P, reads, tasks, X, count_cursor + 1, (const int*)scores, counters);
+	hipLaunchKernelGGL(k_seedsw_prep, dim3(grid), dim3(64), 0, st, ix, G.tasks, X, cursor, J, job_cap, count_cursor);
+	if (sc.o_del == sc.o_ins && sc.e_del == sc.e_ins) hipLaunchKernelGGL(k_swl16<true>, dim3(n_cu * 8), dim3(256), 0, st, ix, sc, G.reads, (const SswJob*)J, (const unsigned int*)count_cursor, job_cap, scores);
+	else hipLaunchKernelGGL(k_swl16<false>, dim3(n_cu * 8), dim3(256), 0, st, ix, sc, G.reads, (const SswJob*)J, (const unsigned int*)count_cursor, job_cap, scores);
+	hipLaunchKernelGGL(k_seedsw_apply, dim3(grid), dim3(64), 0, st, ix, sc, *G.P, G.reads, G.tasks, X, count_cursor + 1, (const int*)scores, G.counters);
 }
+#undef RG_COMMON_
+#undef RG_LISTS_
+#undef RG_OUT_
+#undef RG_POS_
 int regions_long_max_query(void) { return RG_QCAP_LONG; }

@@ -243,13 +243,13 @@ k_seed(DevIndex ix, const uint8_t *reads, const bsx_seed_task_t *tasks, int n_ta
 		long long pub = pc_pub;
 		for (int off = 32; off > 0; off >>= 1) { long long o = __shfl_down(pub, off); pub = pub > o ? pub : o; }
 		if ((threadIdx.x & 63) == 0) {
-			atomicAdd(&counters[48], (unsigned long long)(clock64() - pc_t0)); atomicAdd(&counters[49], (unsigned long long)pc_cold);
-			atomicAdd(&counters[50], (unsigned long long)pub); atomicAdd(&counters[51], (unsigned long long)trip); atomicAdd(&counters[52], (unsigned long long)pc_cold_n);
+			atomicAdd(&counters[CTR_SEED_CYC], (unsigned long long)(clock64() - pc_t0)); atomicAdd(&counters[CTR_SEED_COLD], (unsigned long long)pc_cold);
+			atomicAdd(&counters[CTR_SEED_PUB], (unsigned long long)pub); atomicAdd(&counters[CTR_SEED_TRIPS], (unsigned long long)trip); atomicAdd(&counters[CTR_SEED_COLD_N], (unsigned long long)pc_cold_n);
 		}
 	}
 	if ((threadIdx.x & 63) == 0) {
-		atomicAdd(&counters[0], 2ull * tot_slow); atomicAdd(&counters[1], (unsigned long long)tot_fast);
-		if (tot_over) atomicAdd(&counters[119], (unsigned long long)tot_over);   // strand searches left with a negative count (k_seedt.hip)
+		atomicAdd(&counters[CTR_FM_SLOW], 2ull * tot_slow); atomicAdd(&counters[CTR_FM_FAST], (unsigned long long)tot_fast);
+		if (tot_over) atomicAdd(&counters[CTR_OVERFLOW], (unsigned long long)tot_over);   // strand searches left with a negative count (k_seedt.hip)
 		__threadfence();
 		atomicExch(&slab_busy[slab], 0u);
 	}
@@ -280,7 +280,7 @@ k_sa(DevIndex ix, const bsx_sa_job_t *jobs, long long n, uint64_t *pos, unsigned
 		++calls;
 	}
 	for (int off = 32; off > 0; off >>= 1) { steps += __shfl_down(steps, off); calls += __shfl_down(calls, off); }
-	if ((threadIdx.x & 63) == 0) { atomicAdd(&counters[2], (unsigned long long)steps); atomicAdd(&counters[3], (unsigned long long)calls); }
+	if ((threadIdx.x & 63) == 0) { atomicAdd(&counters[CTR_LF_STEPS], (unsigned long long)steps); atomicAdd(&counters[CTR_LF_CALLS], (unsigned long long)calls); }
 }
 
 void launch_seed(hipStream_t st, int grid, const DevIndex &ix, const uint8_t *reads, const bsx_seed_task_t *tasks, int n_tasks, const SeedParams &P,

@@ -183,7 +183,7 @@ k_seedt(DevIndex ix, const uint8_t *reads, const bsx_seed_task_t *tasks, int n_t
 				task_off[task] = (long long)base;
 				task_n[task] = L.overflow ? -n - 1 : n;   // any negative count: seed this strand search again
 				tot_over += L.overflow ? 1u : 0u;
-				if (hist) atomicAdd(&counters[60 + (trips > 0 ? 32 - __clz(trips) : 0)], 1ull);   // ($BSX_PHASES: requests per strand search of the second pass, by power of two)
+				if (hist) atomicAdd(&counters[CTR_SEED_HIST + (trips > 0 ? 32 - __clz(trips) : 0)], 1ull);   // ($BSX_PHASES: requests per strand search of the second pass, by power of two)
 				tot_slow += L.n_slow; tot_fast += L.n_fast; tot_look += L.n_look;
 				task = -1;
 			}
@@ -238,13 +238,13 @@ k_seedt(DevIndex ix, const uint8_t *reads, const bsx_seed_task_t *tasks, int n_t
 	for (int off = 32; off > 0; off >>= 1) { tot_slow += __shfl_down(tot_slow, off); tot_fast += __shfl_down(tot_fast, off); tot_look += __shfl_down(tot_look, off); tot_over += __shfl_down(tot_over, off); }
 	if ((threadIdx.x & 63) == 0) {
 		if (prof) {
-			atomicAdd(&counters[48], (unsigned long long)(clock64() - pc_t0)); atomicAdd(&counters[49], (unsigned long long)pc_cold);
-			atomicAdd(&counters[51], (unsigned long long)trip); atomicAdd(&counters[52], (unsigned long long)pc_cold_n);
-			atomicAdd(&counters[121], (unsigned long long)pc_hot); atomicAdd(&counters[122], (unsigned long long)pc_fetch); atomicAdd(&counters[123], (unsigned long long)pc_post);
-			atomicAdd(&counters[124], pc_req);
+			atomicAdd(&counters[CTR_SEED_CYC], (unsigned long long)(clock64() - pc_t0)); atomicAdd(&counters[CTR_SEED_COLD], (unsigned long long)pc_cold);
+			atomicAdd(&counters[CTR_SEED_TRIPS], (unsigned long long)trip); atomicAdd(&counters[CTR_SEED_COLD_N], (unsigned long long)pc_cold_n);
+			atomicAdd(&counters[CTR_SEEDT_HOT], (unsigned long long)pc_hot); atomicAdd(&counters[CTR_SEEDT_FETCH], (unsigned long long)pc_fetch); atomicAdd(&counters[CTR_SEEDT_POST], (unsigned long long)pc_post);
+			atomicAdd(&counters[CTR_SEEDT_REQ], pc_req);
 		}
-		atomicAdd(&counters[0], 2ull * tot_slow); atomicAdd(&counters[1], (unsigned long long)tot_fast); atomicAdd(&counters[120], (unsigned long long)tot_look);
-		if (tot_over) atomicAdd(&counters[119], (unsigned long long)tot_over);   // what the caller has to seed again: read back instead of every count
+		atomicAdd(&counters[CTR_FM_SLOW], 2ull * tot_slow); atomicAdd(&counters[CTR_FM_FAST], (unsigned long long)tot_fast); atomicAdd(&counters[CTR_TAB_LOOKUPS], (unsigned long long)tot_look);
+		if (tot_over) atomicAdd(&counters[CTR_OVERFLOW], (unsigned long long)tot_over);   // what the caller has to seed again: read back instead of every count
 		__threadfence();
 		atomicExch(&slab_busy[slab], 0u);
 	}

@@ -4,6 +4,7 @@
 #include "dev_common.hpp"
 #include "seed_core.hpp"
 #include "seed_tab.hpp"
+#include "ctr_layout.hpp"
 
 void launch_seed(hipStream_t st, int grid, const DevIndex &ix, const uint8_t *reads, const bsx_seed_task_t *tasks, int n_tasks, const SeedParams &P,
                  DevIntv *scratch, int list_cap, int mem_cap, DevIntv *out, unsigned long long out_cap, unsigned long long *out_cursor,
@@ -46,6 +47,7 @@ void launch_qc(hipStream_t st, const DevIndex &ix, const uint8_t *reads, long lo
                unsigned long long *table, int n_cu);
 // k_markdup.hip: the device's table of template keys (bsx_markdup_batch).  A slot: claim word (0: empty), lowest ordinal, the key (all ones: none yet)
 struct MdSlot { unsigned long long claim, ord, k0, k1; };
+enum { MD_CTR_TAKEN = 0, MD_CTR_OPEN = 1, MD_CTR_LOST = 2 };   // ctr[] of the two launchers below
 enum { MD_RES_FIRST = 0, MD_RES_DUP = 1, MD_RES_OPEN = 2, MD_RES_SKIP = 3, MD_RES_FULL = 4 };   // a key's state in res[] (OPEN: to be looked up in this round)
 void launch_md_init(hipStream_t st, MdSlot *T, unsigned long long n_slots);
 // one round over the keys still OPEN: k_md_claim, k_md_publish, k_md_decide; ctr[0] += slots taken, ctr[1] += keys left OPEN (another key has their claim word)
@@ -63,9 +65,8 @@ void launch_md_rehash(hipStream_t st, const MdSlot *old, unsigned long long n_ol
 void launch_extwin_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t *jobs, bsx_ext_res_t *res, long long n);
 int x4_max_query(int ncq);
 size_t x4_job_bytes(void);
-struct RgXPoolArg;
-void launch_x4(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, const bsx_seed_task_t *tasks,
-               long long n_tasks, const RgXPoolArg &X, void *jobs, unsigned long long job_cap, unsigned int *ctr32, unsigned long long *prof);
+struct RgXPoolArg; struct RgLaunch;
+void launch_x4(hipStream_t st, int n_cu, const RgLaunch &G, const RgXPoolArg &X, void *jobs, unsigned long long job_cap, unsigned int *ctr32, unsigned long long *prof);   // G.n_tasks bounds the number of exported strand searches
 // K4 a lane per job (k_extl.hip) for the narrow queue of launch_x4's pool; called by launch_x4
 void launch_extl(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, void *jobs, unsigned int jcap,
                  unsigned int *ctr32, unsigned char *xbase, long long n_upper, unsigned long long *prof);
@@ -81,39 +82,48 @@ size_t regions_slab_bytes(int tier);
 // the block of task t at xoff[t], and the list of tasks that have one
 struct RgXPoolArg { unsigned char *base; unsigned long long cap; unsigned long long *cursor; long long *xoff; int *xlist; unsigned int *xcount;
                     int ext; };   // ext: the records leave room for the extensions launch_x4 makes ahead of launch_c2r
-void launch_regions(hipStream_t st, int grid, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads,
-                    const bsx_seed_task_t *tasks, int n_tasks, const DevIntv *seeds_dense, const long long *task_off, const int *task_n,
-                    bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
-                    unsigned int *task_cursor, int *retry_list, unsigned int *retry_count, int quota, unsigned long long *counters,
-                    const long long *pos_off, const unsigned long long *pos, const unsigned char *cls, const RgXPoolArg &X, int long_reads = 0);   // cls[t] != 0: not for this tier (launch_occ)
-// the tier in between: LDS tables four times the first tier's; consumes the first tier's list, appends to the second tier's
-void launch_regions_mid(hipStream_t st, int grid, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads,
-                        const bsx_seed_task_t *tasks, const DevIntv *seeds_dense, const long long *task_off, const int *task_n,
-                        bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
-                        const int *list, const unsigned int *count, unsigned int *cursor, int *next_list, unsigned int *next_count,
-                        unsigned long long *counters, const long long *pos_off, const unsigned long long *pos, const RgXPoolArg &X, int quota, int long_reads = 0);   // quota: strand searches per wave; long_reads: the instantiation for reads up to regions_long_max_query()
-// chains -> regions for everything the two launches above exported; what does not fit its tables goes on next_list
-void launch_c2r(hipStream_t st, int grid, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, const bsx_seed_task_t *tasks,
-                const RgXPoolArg &X, bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
-                unsigned int *cursor, int *next_list, unsigned int *next_count, unsigned long long *counters, int quota, int long_reads = 0, void *slab = nullptr);   // next_list may be null (long reads: what outgrows the tables is left to the caller)   // long_reads 2: larger LDS tables (what the first launch declines); 3: the large tables in HBM, `slab` = grid x c2r_hbm_slab_bytes()
+// what every launch over one task list is given: the same at every call site of a tier sequence
+struct RgLaunch {
+	const DevIndex *ix; const DevScoring *sc; const RegParams *P;
+	const uint8_t *reads; const bsx_seed_task_t *tasks; int n_tasks;
+	const DevIntv *seeds_dense; const long long *task_off; const int *task_n;   // the dense interval lists
+	bsx_region_t *out; unsigned long long out_cap; unsigned long long *out_cursor;   // the region pool
+	long long *reg_off; int *reg_n;
+	unsigned long long *counters;            // the lane's counter block (ctr_layout.hpp)
+	long long *pos_off; unsigned long long *pos;   // launch_occ fills them, the region kernels read them
+};
+void launch_regions(hipStream_t st, int grid, const RgLaunch &G, unsigned int *task_cursor, int *retry_list, unsigned int *retry_count, int quota,
+                    const unsigned char *cls, const RgXPoolArg &X, bool long_reads = false);   // cls[t] != 0: not for this tier (launch_occ)
+// the tiers in between: larger LDS tables; each consumes the list of the tier before it and appends to the next one's.  The forms: tables, DP
+enum RgMidForm { RG_MID,          // RgMid, RgDpLite: four times the first tier's tables, behind it
+                 RG_MID_LONGS,    // RgLongS, RgDpLiteL: tables for a kilobase read, one wave per workgroup
+                 RG_MID_LONGB,    // RgLongB, RgDpLite: the larger tables for reads of ordinary length
+                 RG_MID_LONGB_L,  // RgLongB, RgDpLiteL: kilobase reads, the larger of the two table sizes
+                 RG_MID2 };       // RgMid2, RgDpLite: twice RgMid's tables, the tier behind it
+void launch_regions_mid(hipStream_t st, int grid, const RgLaunch &G, const int *list, const unsigned int *count, unsigned int *cursor,
+                        int *next_list, unsigned int *next_count, const RgXPoolArg &X, int quota, RgMidForm form);   // quota: strand searches per wave
+// chains -> regions for everything the launches above exported; what does not fit its tables goes on next_list (may be null: left to the caller)
+enum RgC2rForm { RG_C2R,      // RgC2r: ordinary chunks
+                 RG_C2R_L,    // RgC2rL: chunks with long reads or the seed filter
+                 RG_C2R_B,    // RgC2rB: larger LDS tables, for what RG_C2R declines
+                 RG_C2R_H,    // RgC2rH: the large tables in HBM (`slab` = grid x c2r_hbm_slab_bytes()), for what RG_C2R_B declines
+                 RG_C2R_HL }; // RgC2rHL: the same for what RG_C2R_L declines
+void launch_c2r(hipStream_t st, int grid, const RgLaunch &G, const RgXPoolArg &X, unsigned int *cursor, int *next_list, unsigned int *next_count,
+                int quota, RgC2rForm form = RG_C2R, void *slab = nullptr);
 size_t c2r_hbm_slab_bytes(void);
 // C3 between the tiers and launch_c2r: the seed-SW filter of the exported strand searches it applies to (mem_flt_chained_seeds, memchain.c:537-568)
-void launch_seedsw(hipStream_t st, int grid, int n_cu, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, const bsx_seed_task_t *tasks,
-                   const RgXPoolArg &XA, unsigned int *cursor, unsigned int *count_cursor, void *jobs, unsigned int job_cap, unsigned long long *counters);
+void launch_seedsw(hipStream_t st, int grid, int n_cu, const RgLaunch &G, const RgXPoolArg &XA, unsigned int *cursor, unsigned int *count_cursor,
+                   void *jobs, unsigned int job_cap);
 size_t seedsw_job_bytes(void);
 int regions_long_max_query(void);
-void launch_regions_slab(hipStream_t st, int tier, int grid, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads,
-                         const bsx_seed_task_t *tasks, const DevIntv *seeds_dense, const long long *task_off, const int *task_n,
-                         bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
-                         const int *list, const unsigned int *count, unsigned int *cursor, void *slabs, int *next_list, unsigned int *next_count,
-                         unsigned long long *counters, const long long *pos_off, const unsigned long long *pos, const RgXPoolArg *X = nullptr);   // X: export the chains (as the LDS tiers do) instead of making the regions
+void launch_regions_slab(hipStream_t st, int tier, int grid, const RgLaunch &G, const int *list, const unsigned int *count, unsigned int *cursor,
+                         void *slabs, int *next_list, unsigned int *next_count, const RgXPoolArg *X = nullptr);   // X: export the chains (as the LDS tiers do) instead of making the regions
 // a tier's list put in order of decreasing size (occurrences to visit), longest strand search first: what a launch that lasts as long as its longest one wants
 void launch_order_list(hipStream_t st, int *list, const unsigned int *count, const DevIntv *seeds_dense, const long long *task_off, const int *task_n, int max_occ);
 // K3 ahead of the region kernels: SA ranks of all occurrences of all strand searches listed into desc (pos_off[t] = where task
 // t's start, -1 = none listed), then turned into reference positions in place.  pos_off/pos feed launch_regions*.
-void launch_occ(hipStream_t st, int n_cu, const DevIndex &ix, const bsx_seed_task_t *tasks, int n_tasks, const DevIntv *seeds_dense, const long long *task_off,
-                const int *task_n, int max_occ, unsigned long long *desc, unsigned long long desc_cap, unsigned long long *cursor, long long *pos_off,
-                unsigned long long *counters, unsigned char *cls, unsigned long long *start = nullptr, int *early_list = nullptr, unsigned int *early_count = nullptr);   // early_list: the strand searches only the last HBM tier's tables hold are listed there (cls 3; the first tier then skips them)   // start: an 8-byte device slot; set = only the ranks this call adds to the pool are walked   // cls[t]: the first tier whose interval/occurrence tables hold task t
+void launch_occ(hipStream_t st, int n_cu, const RgLaunch &G, int max_occ, unsigned long long desc_cap, unsigned long long *cursor, unsigned char *cls,
+                unsigned long long *start = nullptr, int *early_list = nullptr, unsigned int *early_count = nullptr);   // desc = G.pos; early_list: the strand searches only the last HBM tier's tables hold are listed there (cls 3; the first tier then skips them)   // start: an 8-byte device slot; set = only the ranks this call adds to the pool are walked   // cls[t]: the first tier whose interval/occurrence tables hold task t
 // out[j] = SA[j * intv] for j < n, from the (sparser) samples ix currently holds: the denser suffix-array sample kept in HBM
 void launch_sa_dense(hipStream_t st, int n_cu, const DevIndex &ix, int parent, unsigned int intv, unsigned long long n, unsigned long long *out);
 // C5 (k_dedup.hip): mem_sort_deduplicate of every read over the regions of the chunk, a lane per read

@@ -21,11 +21,16 @@
 // One lane = one HIP stream with its own staging: a chunk is bound to a lane for its whole life, so the front half
 // (seeding .. regions) of one chunk and the back half (merge .. SAM) of the previous one can be in flight together.
 #define BSX_LANES 6
+// the slots of bsx_device_kernel_time: the chunk-wide seeding pass, the suffix-array lookups, the DP batches (extensions, local alignments,
+// global alignments), tier 1, the later tiers, seeding outside the chunk-wide launch (the batch form, the merged second pass)
+enum KTime { KT_SEED = 0, KT_K3 = 1, KT_EXTEND = 2, KT_SW = 3, KT_GLOBAL = 4, KT_TIER1 = 5, KT_TIERS_LATER = 6, KT_SEED_OTHER = 7, KT_N = 8 };
 struct Lane {
 	hipStream_t st = nullptr;      // front-half kernels (low priority)
 	hipEvent_t ev_seed_done = nullptr, ev_regions_done = nullptr;   // what the next chunk's launches of the same stage wait for
 	hipStream_t st_hi = nullptr;   // back-half kernels (K5, K6): high priority, so that they get compute units while another chunk's front half runs
-	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr, ev4 = nullptr, ev5 = nullptr, ev6 = nullptr;   // (ev5, ev6: around the second seeding pass inside the main sequence)
+	hipEvent_t ev_timed_begin = nullptr, ev_timed_end = nullptr;   // around the launch finish_timed times; in a regions batch: around the chunk-wide seeding pass
+	hipEvent_t ev_seed2_begin = nullptr, ev_seed2_end = nullptr;   // regions batch: around the second seeding pass inside the main sequence (recorded back to back when there is none)
+	hipEvent_t ev_occ_end = nullptr, ev_tier1_end = nullptr, ev_tiers_end = nullptr;   // ... behind the suffix-array lookups, behind tier 1, behind everything of the main sequence
 	hipEvent_t tier_ev[12] = {};   // $BSX_PHASES: between the region launches
 	hipStream_t st_cp = nullptr;   // unmasked: the front half's small copies (xfer)
 	hipEvent_t ev_cp = nullptr;
@@ -39,7 +44,7 @@ struct Lane {
 	int64_t rb_tasks = 0;    // strand searches of the last regions batch (their regions, offsets and counts are still in regs / regmeta)
 	int flt_key[3] = {-1, -1, -1};   // what fltab was made for
 	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, gctx, qcjobs, qcpool, mdkeys, mdres, mdslot, dd, sswjobs, c2rslab;
-	DevBuf small;          // counters[4] | out_cursor | task_cursor | region cursors
+	DevBuf small;          // the counter block: SMALL_BYTES laid out by ctr_layout.hpp
 	HostBuf hstage;        // pinned staging for bulk results
 	HostBuf pin;           // two pinned halves through which large host<->device copies are streamed
 	hipEvent_t pev[2] = {nullptr, nullptr};
@@ -54,22 +59,20 @@ struct Lane {
 		unsigned long long used_main = 0;      // regions the caller already holds
 		unsigned long long regs_cap = 0;       // size of the device's region pool for this chunk
 	} rs;
-	double k_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-	int64_t k_launch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+	double k_ms[KT_N] = {0, 0, 0, 0, 0, 0, 0, 0};   // by KTime
+	int64_t k_launch[KT_N] = {0, 0, 0, 0, 0, 0, 0, 0};
 	uint64_t work[5] = {0, 0, 0, 0, 0};   // the region kernels' work since the last reset: strand searches, SA intervals, occurrences, regions, read bases
 	// what the last de-duplication of this lane left in `dd` (k_msw.hip reads the reads' lists from there): layout and validity
 	struct { bool valid = false; int64_t n_reads = 0; int per_read = 0; size_t o_idx = 0, o_off = 0, o_pool = 0; bool with_long = false; } ddl;
 	DevBuf msw_jobs, msw_res, msw_meta, msw_roff; int64_t msw_token = -1;
 	std::mutex hi_mu;      // the back half's batches (K5, K6) of this lane, one at a time: the slices of a chunk's back half call them from two threads
 	long last_overflow = -1;   // strand searches the first seeding pass of this lane's last chunk left to the second (-1: no chunk yet)
-	double seed2_ms = 0; int64_t seed2_launches = 0; uint64_t seed2_tasks = 0;   // the second seeding pass inside the chunk's sequence (its own launch, its own counters: SEED2_CTR)
+	double seed2_ms = 0; int64_t seed2_launches = 0; uint64_t seed2_tasks = 0;   // the second seeding pass inside the chunk's sequence (its own launch, its own counters: CTR_SEED2)
 };
 // The seeding launches of a chunk count their FM blocks and table entries in blocks of their own, so that each pass's bytes can be put over
-// that pass's time (bsx_device_seed_passes): u64 slots [0], [1], [120] of the lane's counter block for the chunk-wide first pass (and the batch
-// form), the same three at SEED2_CTR for the second pass inside the sequence, at SEED3_CTR for the few seeded again on the side stream.
-#define SEED2_CTR 256
-#define SEED3_CTR 384
-#define SMALL_BYTES 4096
+// that pass's time (bsx_device_seed_passes): CTR_FM_SLOW, CTR_FM_FAST, CTR_TAB_LOOKUPS of the lane's counter block (ctr_layout.hpp) for the chunk-wide
+// first pass (and the batch form), the same three from CTR_SEED2 for the second pass inside the sequence, from CTR_SEED3 for the few seeded again
+// on the side stream.
 
 struct bsx_device {
 	int ordinal = 0;
@@ -97,6 +100,10 @@ static double bsx_now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return 
 // Measured at hg38 size, k_occ per chunk: 28 ms at every 4th (12.4 GB per index), 16.5 at every 2nd (24.8 GB), 8.9 with the whole array (49.6 GB)
 #define BSX_DEVICE_SA_INTV_DEFAULT 2
 static inline unsigned long long *dev_counters(Lane &L) { return (unsigned long long*)L.small.p; }
+static inline CtrShared *ctr_shared(Lane &L) { return (CtrShared*)(dev_counters(L) + CTR_SHARED); }   // (device memory: for the addresses of its fields)
+static inline TierCtr *ctr_tiers(Lane &L, bool main_seq) { return (TierCtr*)(dev_counters(L) + (main_seq ? CTR_MAIN : CTR_SIDE)); }
+// a lane's slab of a seeding pass: mem_cap SMEMs of 32 bytes, one list of list_cap 16-byte entries
+static inline size_t seed_lane_bytes(long long mem_cap, int list_cap) { return (size_t)mem_cap * 32 + (size_t)list_cap * 16; }
 
 extern "C" BSX_API int bsx_device_open(int ordinal, bsx_device_t **out)
 {
@@ -144,26 +151,20 @@ extern "C" BSX_API int bsx_device_open(int ordinal, bsx_device_t **out)
 			HIPCHK(hipStreamCreateWithPriority(&L.st2, hipStreamNonBlocking, lo));
 			HIPCHK(hipStreamCreateWithPriority(&L.st3, hipStreamNonBlocking, lo));
 		}
+		for (hipEvent_t *e : {&L.ev_timed_begin, &L.ev_timed_end, &L.ev_seed2_begin, &L.ev_seed2_end, &L.ev_occ_end, &L.ev_tier1_end, &L.ev_tiers_end}) HIPCHK(hipEventCreate(e));
 		HIPCHK(hipEventCreate(&L.ev_t3a));
 		HIPCHK(hipEventCreate(&L.ev_t3b));
 		HIPCHK(hipStreamCreateWithPriority(&L.st_hi, hipStreamNonBlocking, hi));
 		if (masked && bsx_tune_long("small_copies_unmasked", 1)) { HIPCHK(hipStreamCreateWithPriority(&L.st_cp, hipStreamNonBlocking, hi)); HIPCHK(hipEventCreateWithFlags(&L.ev_cp, hipEventDisableTiming)); }
-		HIPCHK(hipEventCreate(&L.ev3));
 		HIPCHK(hipEventCreateWithFlags(&L.ev_seed_done, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&L.ev_regions_done, hipEventDisableTiming));
-		HIPCHK(hipEventCreate(&L.ev4));
-		HIPCHK(hipEventCreate(&L.ev5));
-		HIPCHK(hipEventCreate(&L.ev6));
 		HIPCHK(hipEventCreateWithFlags(&L.rs.ev, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&L.rs.ev_tiers, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&L.pev[0], hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&L.pev[1], hipEventDisableTiming));
 		if (L.slabflags.reserve((size_t)d->n_cu * 16 * 4) != BSX_OK) return BSX_E_NOMEM;
 		HIPCHK(hipMemset(L.slabflags.p, 0, (size_t)d->n_cu * 16 * 4));
-		HIPCHK(hipEventCreate(&L.ev0));
-		HIPCHK(hipEventCreate(&L.ev1));
-		HIPCHK(hipEventCreate(&L.ev2));
-		if (L.small.reserve(SMALL_BYTES) != BSX_OK) return BSX_E_NOMEM;   // u64 slots 32..47: per-stage cycle counts of the region kernels ($BSX_PHASES)
+		if (L.small.reserve(SMALL_BYTES) != BSX_OK) return BSX_E_NOMEM;
 		HIPCHK(hipMemset(L.small.p, 0, SMALL_BYTES));
 	}
 	memset(&d->ix, 0, sizeof(d->ix));
@@ -186,9 +187,6 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 		L.small.release(); L.hstage.release(); L.regs.release(); L.regmeta.release(); L.slabs.release(); L.slabflags.release(); L.slabs3.release(); L.redo.release(); L.pin.release(); L.pos.release(); L.posoff.release(); L.xpool.release(); L.xmeta.release(); L.x4jobs.release(); L.fltab.release(); L.flt_key[0] = -1; L.tags.release(); L.mdpool.release(); L.gctx.release(); L.qcjobs.release(); L.qcpool.release(); L.mdkeys.release(); L.mdres.release(); L.mdslot.release(); L.dd.release(); L.c2rslab.release(); L.sswjobs.release(); L.msw_jobs.release(); L.msw_res.release(); L.msw_meta.release(); L.msw_roff.release();
 		if (L.pev[0]) (void)hipEventDestroy(L.pev[0]);
 		if (L.pev[1]) (void)hipEventDestroy(L.pev[1]);
-		if (L.ev0) (void)hipEventDestroy(L.ev0);
-		if (L.ev1) (void)hipEventDestroy(L.ev1);
-		if (L.ev2) (void)hipEventDestroy(L.ev2);
 		if (L.ev_seed_done) (void)hipEventDestroy(L.ev_seed_done);
 		if (L.ev_regions_done) (void)hipEventDestroy(L.ev_regions_done);
 		if (L.st) (void)hipStreamDestroy(L.st);
@@ -197,12 +195,9 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 		if (L.st3) (void)hipStreamDestroy(L.st3);
 		if (L.st_cp) (void)hipStreamDestroy(L.st_cp);
 		if (L.ev_cp) (void)hipEventDestroy(L.ev_cp);
+		for (hipEvent_t e : {L.ev_timed_begin, L.ev_timed_end, L.ev_seed2_begin, L.ev_seed2_end, L.ev_occ_end, L.ev_tier1_end, L.ev_tiers_end}) if (e) (void)hipEventDestroy(e);
 		if (L.ev_t3a) (void)hipEventDestroy(L.ev_t3a);
 		if (L.ev_t3b) (void)hipEventDestroy(L.ev_t3b);
-		if (L.ev3) (void)hipEventDestroy(L.ev3);
-		if (L.ev4) (void)hipEventDestroy(L.ev4);
-		if (L.ev5) (void)hipEventDestroy(L.ev5);
-		if (L.ev6) (void)hipEventDestroy(L.ev6);
 		for (int k = 0; k < 12; ++k) if (L.tier_ev[k]) { (void)hipEventDestroy(L.tier_ev[k]); L.tier_ev[k] = nullptr; }
 		if (L.rs.ev) (void)hipEventDestroy(L.rs.ev);
 		if (L.rs.ev_tiers) (void)hipEventDestroy(L.rs.ev_tiers);
@@ -488,12 +483,12 @@ static int lane_set_reads(bsx_device_t *d, int lane, const uint8_t *buf, size_t 
 
 extern "C" BSX_API int bsx_device_set_reads(bsx_device_t *d, const uint8_t *buf, size_t n) { return lane_set_reads(d, 0, buf, n); }
 
-// time one kernel (already enqueued between ev0/ev1 on the lane's stream)
+// time one kernel (already enqueued between ev_timed_begin / ev_timed_end on the lane's stream)
 static int finish_timed(Lane &L, int k)
 {
 	float ms = 0;
-	HIPCHK(hipEventSynchronize(L.ev1));
-	HIPCHK(hipEventElapsedTime(&ms, L.ev0, L.ev1));
+	HIPCHK(hipEventSynchronize(L.ev_timed_end));
+	HIPCHK(hipEventElapsedTime(&ms, L.ev_timed_begin, L.ev_timed_end));
 	L.k_ms[k] += ms; L.k_launch[k] += 1;
 	HIPCHK(hipGetLastError());
 	return BSX_OK;
@@ -506,11 +501,13 @@ extern "C" BSX_API int bsx_device_counters(bsx_device_t *d, uint64_t c[4], int r
 	c[0] = c[1] = c[2] = c[3] = 0;
 	for (int l = 0; l < BSX_LANES; ++l) {
 		uint64_t t[4];
-		HIPCHK(hipMemcpy(t, d->lane[l].small.p, 32, hipMemcpyDeviceToHost));
+		unsigned long long *ctr = dev_counters(d->lane[l]);
+		static_assert(CTR_FM_SLOW == 0 && CTR_LF_CALLS == 3, "c[0..3]: FM blocks (slow, fast), LF steps, LF calls");
+		HIPCHK(hipMemcpy(t, ctr + CTR_FM_SLOW, 32, hipMemcpyDeviceToHost));
 		for (int k = 0; k < 4; ++k) c[k] += t[k];
-		if (reset) HIPCHK(hipMemset(d->lane[l].small.p, 0, 32));
+		if (reset) HIPCHK(hipMemset(ctr + CTR_FM_SLOW, 0, 32));
 		for (int b = 0; b < 2; ++b) { // the later seeding passes' FM blocks (counted apart: bsx_device_seed_passes)
-			char *p = (char*)d->lane[l].small.p + (size_t)(b ? SEED3_CTR : SEED2_CTR) * 8;
+			unsigned long long *p = ctr + (b ? CTR_SEED3 : CTR_SEED2) + CTR_FM_SLOW;
 			HIPCHK(hipMemcpy(t, p, 16, hipMemcpyDeviceToHost));
 			c[0] += t[0]; c[1] += t[1];
 			if (reset) HIPCHK(hipMemset(p, 0, 16));
@@ -526,12 +523,12 @@ extern "C" BSX_API int bsx_device_seed_table(bsx_device_t *d, uint64_t *lookups,
 	HIPCHK(hipSetDevice(d->ordinal));
 	uint64_t tot = 0;
 	for (int l = 0; l < BSX_LANES; ++l) {
-		static const int at[3] = {120, SEED2_CTR + 120, SEED3_CTR + 120};
+		static const int at[3] = {CTR_TAB_LOOKUPS, CTR_SEED2 + CTR_TAB_LOOKUPS, CTR_SEED3 + CTR_TAB_LOOKUPS};
 		for (int b = 0; b < 3; ++b) {
 			uint64_t t = 0;
-			HIPCHK(hipMemcpy(&t, (char*)d->lane[l].small.p + (size_t)at[b] * 8, 8, hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(&t, dev_counters(d->lane[l]) + at[b], 8, hipMemcpyDeviceToHost));
 			tot += t;
-			if (reset) HIPCHK(hipMemset((char*)d->lane[l].small.p + (size_t)at[b] * 8, 0, 8));
+			if (reset) HIPCHK(hipMemset(dev_counters(d->lane[l]) + at[b], 0, 8));
 		}
 	}
 	if (lookups) *lookups = tot;
@@ -551,14 +548,15 @@ extern "C" BSX_API int bsx_device_seed_passes(bsx_device_t *d, uint64_t w[6], do
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
 		uint64_t t[2], u = 0;
-		HIPCHK(hipMemcpy(t, L.small.p, 16, hipMemcpyDeviceToHost));
-		HIPCHK(hipMemcpy(&u, (char*)L.small.p + 120 * 8, 8, hipMemcpyDeviceToHost));
+		unsigned long long *ctr = dev_counters(L);
+		HIPCHK(hipMemcpy(t, ctr + CTR_FM_SLOW, 16, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(&u, ctr + CTR_TAB_LOOKUPS, 8, hipMemcpyDeviceToHost));
 		w[0] += t[0] + t[1]; w[1] += u;
-		HIPCHK(hipMemcpy(t, (char*)L.small.p + SEED2_CTR * 8, 16, hipMemcpyDeviceToHost));
-		HIPCHK(hipMemcpy(&u, (char*)L.small.p + (SEED2_CTR + 120) * 8, 8, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(t, ctr + CTR_SEED2 + CTR_FM_SLOW, 16, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(&u, ctr + CTR_SEED2 + CTR_TAB_LOOKUPS, 8, hipMemcpyDeviceToHost));
 		w[2] += t[0] + t[1]; w[3] += u;
 		w[4] += (uint64_t)L.seed2_launches; w[5] += L.seed2_tasks;
-		ms[0] += L.k_ms[0]; ms[1] += L.seed2_ms;
+		ms[0] += L.k_ms[KT_SEED]; ms[1] += L.seed2_ms;
 		if (reset) { L.seed2_ms = 0; L.seed2_launches = 0; L.seed2_tasks = 0; }
 	}
 	return BSX_OK;
@@ -574,7 +572,7 @@ extern "C" BSX_API int bsx_device_region_work(bsx_device_t *d, uint64_t w[5], in
 
 extern "C" BSX_API int bsx_device_kernel_time(bsx_device_t *d, int k, double *total_ms, int64_t *launches, int reset)
 {
-	if (!d || k < 0 || k >= 8) return BSX_E_ARG;
+	if (!d || k < 0 || k >= KT_N) return BSX_E_ARG;
 	double ms = 0; int64_t n = 0;
 	for (int l = 0; l < BSX_LANES; ++l) {
 		ms += d->lane[l].k_ms[k]; n += d->lane[l].k_launch[k];
@@ -647,7 +645,7 @@ static int lane_seed_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int6
 		}
 		int list_cap = max_len + 2;
 		int waves = (int)std::min<int64_t>((cn + 63) / 64, (int64_t)d->n_cu * 16);
-		const size_t per_lane = (size_t)mem_cap * 32 + (size_t)list_cap * 16;   // mem_cap SMEMs of 32 bytes, one list of list_cap 16-byte entries
+		const size_t per_lane = seed_lane_bytes(mem_cap, list_cap);
 		waves = (int)std::max<size_t>(4, std::min<size_t>((size_t)waves, ((size_t)8 << 30) / (64 * per_lane)));   // (long reads seeded again with long lists: fewer waves, not tens of GB)
 		int grid = (waves + 3) / 4;
 		size_t lanes = (size_t)grid * 256;
@@ -658,20 +656,20 @@ static int lane_seed_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int6
 		if ((rc = L.aux.reserve((size_t)cn * 12 + 64)) != BSX_OK) return rc;
 		if ((rc = L.qpack.reserve(seedt_pack_bytes(cn))) != BSX_OK) return rc;
 		long long *d_off = (long long*)L.aux.p; int *d_n = (int*)((char*)L.aux.p + (size_t)cn * 8);
-		unsigned long long *ctr = dev_counters(L);
+		unsigned long long *ctr = dev_counters(L); CtrShared::Seed *sc = &ctr_shared(L)->seed;
 		HIPCHK(hipMemcpyAsync(L.jobs.p, cur, (size_t)cn * sizeof(bsx_seed_task_t), hipMemcpyHostToDevice, L.st));
-		HIPCHK(hipMemsetAsync(ctr + 4, 0, 16, L.st));   // out_cursor (u64) + task_cursor (u32)
-		HIPCHK(hipEventRecord(L.ev0, L.st));
+		HIPCHK(hipMemsetAsync(sc, 0, sizeof(*sc), L.st));   // the interval cursor and the task cursor
+		HIPCHK(hipEventRecord(L.ev_timed_begin, L.st));
 		launch_seed(L.st, grid, d->ix, (const uint8_t*)L.reads.p, (const bsx_seed_task_t*)L.jobs.p, (int)cn, P,
-		            (DevIntv*)L.scratch.p, list_cap, mem_cap, (DevIntv*)L.out.p, dense_cap, ctr + 4, d_off, d_n,
-		            (unsigned int*)(ctr + 5), ctr, 0, (unsigned int*)L.slabflags.p, grid * 4, 0, 0, (uint32_t*)L.qpack.p);
-		HIPCHK(hipEventRecord(L.ev1, L.st));
-		if ((rc = finish_timed(L, 7)) != BSX_OK) return rc;   // the batch form, for what the host chains: not the chunk-wide launch of slot 0
+		            (DevIntv*)L.scratch.p, list_cap, mem_cap, (DevIntv*)L.out.p, dense_cap, &sc->intv_cursor, d_off, d_n,
+		            &sc->task_cursor, ctr, 0, (unsigned int*)L.slabflags.p, grid * 4, 0, 0, (uint32_t*)L.qpack.p);
+		HIPCHK(hipEventRecord(L.ev_timed_end, L.st));
+		if ((rc = finish_timed(L, KT_SEED_OTHER)) != BSX_OK) return rc;   // the batch form, for what the host chains: not the chunk-wide launch of KT_SEED
 		std::vector<long long> r_off((size_t)cn); std::vector<int> r_n((size_t)cn);
 		unsigned long long used = 0;
 		D2H(L.st, r_off.data(), d_off, (size_t)cn * 8);
 		D2H(L.st, r_n.data(), d_n, (size_t)cn * 4);
-		D2H(L.st, &used, ctr + 4, 8);
+		D2H(L.st, &used, &sc->intv_cursor, 8);
 		if (used > dense_cap) used = dense_cap;
 		std::vector<int64_t> next;
 		if (round == 0) {
@@ -711,27 +709,90 @@ static int lane_seed_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int6
 // ------------------------------------------------------------------------------------------
 // K1+K2 -> K3 + chaining + chain filter + chain-to-region on the device; the interval lists never leave HBM
 // ------------------------------------------------------------------------------------------
-static int lane_regions_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int64_t n, const bsx_seed_task_t *tasks,
-                              bsx_region_t **out, int64_t *out_cap, int64_t *out_off, int32_t *out_n,
-                              bsx_intv_t **decl_intv, int64_t *decl_cap, int64_t *decl_off)
+#define TRY(x) do { int rc_ = (x); if (rc_ != BSX_OK) return rc_; } while (0)
+
+// arrays carved out of a device buffer one behind the other: take<T>(count) aligns for T
+struct Bump {
+	char *p, *end;
+	explicit Bump(const DevBuf &b) : p((char*)b.p), end((char*)b.p + b.cap) {}
+	template <class T> T *take(size_t n) { p = (char*)(((size_t)p + alignof(T) - 1) & ~(size_t)(alignof(T) - 1)); T *r = (T*)p; p += n * sizeof(T); return r; }
+	bool ok() const { return p <= end; }
+};
+
+// One tier sequence: the launches from tier 1 to tier 3 over a task list.  There are two: the chunk's on the lane's stream, and the side
+// stream's over the strand searches seeded again there.
+struct TierSeq {
+	hipStream_t st; bool main_seq;
+	RgLaunch G;               // tasks and their number, interval offsets and counts, region offsets and counts, position offsets
+	long long *offs; int *cnts;   // (G.task_off, G.task_n as the seeding passes write them)
+	unsigned char *cls;       // launch_occ: the first tier whose tables hold the strand search
+	// what each launch hands on: tier 1 -> ra -> tier 1b -> rm -> tier 1c -> rl -> tier 2 -> rb -> tier 3; rc, rh: what the first and second
+	// chains -> regions launches decline; x2: what tier 2 exports (tier2_export); rf: what takes that tier's full form
+	int *ra, *rm, *rl, *rb, *rc, *rh, *x2, *rf;
+	RgXPoolArg X;
+	TierCtr *c;               // its counts and cursors in the lane's counter block (device memory)
+};
+// The arrays of a sequence, n entries each.  The chunk's lie in four buffers; the side sequence's one behind the other in one (the same Bump four times).
+static void seq_carve(TierSeq &S, size_t n, Bump &lists, Bump &meta, Bump &xmeta, Bump &posoff)
 {
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	Lane &L = d->lane[lane];
-	if (n == 0) return BSX_OK;
-	if (n > 0x7fffffff) return BSX_E_ARG;
-	HIPCHK(hipSetDevice(d->ordinal));
-	struct timespec ts_in, ts_out;
-	clock_gettime(CLOCK_MONOTONIC, &ts_in);
-	int rc, max_len = 0;
-	for (int64_t i = 0; i < n; ++i) max_len = std::max(max_len, tasks[i].len);
+	S.offs = lists.take<long long>(n); S.cnts = lists.take<int>(n);
+	S.G.reg_off = meta.take<long long>(n); S.G.reg_n = meta.take<int>(n);
+	for (int **q : {&S.ra, &S.rm, &S.rl, &S.rb, &S.rc, &S.rh, &S.x2, &S.rf}) *q = meta.take<int>(n);
+	S.X.xoff = xmeta.take<long long>(n); S.X.xlist = xmeta.take<int>(n);
+	S.G.pos_off = posoff.take<long long>(n);
+	S.cls = meta.take<unsigned char>(n);
+	S.G.task_off = S.offs; S.G.task_n = S.cnts; S.G.n_tasks = (int)n;
+}
+
+// a seeding pass over n2 strand searches whose lists overflowed: a lane each, lists eight times as long
+struct SeedAgain { int grid; long long cap; size_t scratch; bool fits; };
+static SeedAgain seed_again_size(size_t n2, int mem_cap, int list_cap, int n_slabs)
+{
+	SeedAgain s;
+	s.grid = (int)((n2 + 255) / 256);
+	s.cap = std::max<long long>((long long)mem_cap * 8, 1024);
+	s.scratch = (size_t)s.grid * 256 * seed_lane_bytes(s.cap, list_cap);
+	s.fits = s.grid * 4 <= n_slabs && s.scratch <= ((size_t)24 << 30);   // (one slab per four waves of the pass: n_slabs bounds it)
+	return s;
+}
+
+// what the stages of one lane_regions_batch call pass along: the call's arguments, the plan (sizes, caps, grids, the tune settings read once),
+// the two sequences, and what the second seeding pass and the marks leave behind
+struct RgBatch {
+	bsx_device_t *d; Lane &L; int lane; const bsx_opt_t *opt; int64_t n; const bsx_seed_task_t *tasks;
+	SeedParams P; RegParams R;
+	int max_len = 0; bool long_reads = false, any_flt = false, export_all = false;
+	int mem_cap = 0, list_cap = 0; bool seed_direct = false;
+	unsigned long long direct_n = 0, dense_cap = 0, regs_cap = 0, pos_cap = 0, xcap = 0, x4_cap = 0, ssw_cap = 0;
+	int seed_quota = 0, trip_budget = 0, budget2_mul = 1, reg_quota = 1, mid_quota = 1, c2r_quota = 1, n_slabs = 0;
+	int grid = 0, big_grid = 0, huge_grid = 0, c2rh_grid = 0;
+	int chain = 0, use_mid = 0, use_x4 = 0, tier2_export = 0; long merge_min = 0;
+	bool order3 = false, early3 = false, use_1c = false, trace = false, trace_tiers = false, per_tier = false;
+	TierSeq main, side;
+	int *retry_e = nullptr;   // what launch_occ lists for the last HBM tier ahead of everything else
+	std::vector<int> first_n;   // the first pass's counts (negative: overflowed), when the host has fetched them
+	std::vector<int> merged_which; const int *merged_cnt = nullptr; bool merged = false;   // the strand searches of the second pass inside the main sequence, and where their new counts are
+	std::vector<int64_t> redo;  // the strand searches that go to the side stream
+	int n_marks = 0; const char *mark_name[12];
+	struct timespec ts_in, ts0, ts1, ts2, ts3, ts_out;
+	unsigned long long used = 0;   // regions of the main sequence
+};
+static double ms_between(const struct timespec &a, const struct timespec &b) { return (b.tv_sec - a.tv_sec) * 1e3 + (b.tv_nsec - a.tv_nsec) * 1e-6; }
+
+// stage 1: the kernels' parameters, and the seed filter's table by read length
+static int rg_params(RgBatch &B)
+{
+	Lane &L = B.L; const bsx_opt_t *opt = B.opt; const int64_t n = B.n;
+	for (int64_t i = 0; i < n; ++i) B.max_len = std::max(B.max_len, B.tasks[i].len);
+	const int max_len = B.max_len;
 	if (max_len >= 1 << 18) return BSX_E_ARG;   // a lane addresses its slab with 32-bit byte offsets (seed_core.hpp): 64 lanes x 32 B x (8 x max_len) entries of the second pass must stay below 2^32
-	SeedParams P;
+	SeedParams &P = B.P;
 	P.min_seed_len = opt->min_seed_len;
 	P.split_len = (int)(opt->min_seed_len * opt->split_factor + .499);
 	P.split_width = opt->split_width;
 	P.max_mem_intv = (int)opt->max_mem_intv;
 	P.start_width = (opt->flag & BSX_F_SELF_OVLP) ? 2 : 1;
-	RegParams R;
+	RegParams &R = B.R;
 	R.a = opt->a; R.w = opt->w; R.o_del = opt->o_del; R.e_del = opt->e_del; R.o_ins = opt->o_ins; R.e_ins = opt->e_ins;
 	R.pen_clip5 = opt->pen_clip5; R.pen_clip3 = opt->pen_clip3; R.min_seed_len = opt->min_seed_len; R.min_chain_weight = opt->min_chain_weight;
 	R.max_chain_gap = opt->max_chain_gap; R.max_occ = opt->max_occ; R.bsstrand = opt->bsstrand; R.max_chain_extend = (uint32_t)opt->max_chain_extend;
@@ -741,617 +802,675 @@ static int lane_regions_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, i
 	R.ext_win = (int)bsx_tune_long("ext_win", 1);
 	// mem_flt_chained_seeds (memchain.c:537-548) by read length: does the seed-SW filter run, and with which threshold.  Tabulated
 	// here because the rule goes through log() and the float / double conversions of the reference's expression.
-	bool any_flt = false;
-	{
-		std::vector<int32_t> ft((size_t)max_len + 1, INT32_MIN);
-		for (int l = 1; l <= max_len; ++l) {
-			const double min_l = opt->min_chain_weight ? 1.1f * opt->min_chain_weight : 5.5f * log((double)l);
-			if (min_l > 0.05f * l) continue;
-			ft[l] = (int32_t)(opt->a * min_l + .499);
-		}
-		for (int64_t i = 0; i < n && !any_flt; ++i) any_flt = tasks[i].len >= 0 && ft[tasks[i].len] != INT32_MIN;   // (for a read of this chunk, not for some length below its longest)
-		// (the table follows from the longest read, -W and -A: uploaded again only when one of them changes)
-		if (!(L.fltab.p && L.flt_key[0] == max_len && L.flt_key[1] == opt->min_chain_weight && L.flt_key[2] == opt->a)) {
-			if ((rc = L.fltab.reserve(ft.size() * 4)) != BSX_OK) return rc;
-			H2D(L.st, L.fltab.p, ft.data(), ft.size() * 4);
-			L.flt_key[0] = max_len; L.flt_key[1] = opt->min_chain_weight; L.flt_key[2] = opt->a;
-		}
-		R.flt_tab = (const int32_t*)L.fltab.p; R.flt_len = max_len;
+	std::vector<int32_t> ft((size_t)max_len + 1, INT32_MIN);
+	for (int l = 1; l <= max_len; ++l) {
+		const double min_l = opt->min_chain_weight ? 1.1f * opt->min_chain_weight : 5.5f * log((double)l);
+		if (min_l > 0.05f * l) continue;
+		ft[l] = (int32_t)(opt->a * min_l + .499);
 	}
+	for (int64_t i = 0; i < n && !B.any_flt; ++i) B.any_flt = B.tasks[i].len >= 0 && ft[B.tasks[i].len] != INT32_MIN;   // (for a read of this chunk, not for some length below its longest)
+	// (the table follows from the longest read, -W and -A: uploaded again only when one of them changes)
+	if (!(L.fltab.p && L.flt_key[0] == max_len && L.flt_key[1] == opt->min_chain_weight && L.flt_key[2] == opt->a)) {
+		TRY(L.fltab.reserve(ft.size() * 4));
+		H2D(L.st, L.fltab.p, ft.data(), ft.size() * 4);
+		L.flt_key[0] = max_len; L.flt_key[1] = opt->min_chain_weight; L.flt_key[2] = opt->a;
+	}
+	R.flt_tab = (const int32_t*)L.fltab.p; R.flt_len = max_len;
 	// Chunks with reads above the short kernels' 256 bases (up to regions_long_max_query(); longer ones are chained by the caller) or with
 	// the seed-SW filter active take the instantiations with longer tables, every tier exports its chains, and the filter (k_seedsw)
 	// runs ahead of chains -> regions.
-	const int long_reads = max_len > 256 ? 1 : 0;
-	const bool export_all = long_reads || any_flt;
+	B.long_reads = max_len > 256;
+	B.export_all = B.long_reads || B.any_flt;
+	return BSX_OK;
+}
 
+// stage 2: sizes, caps, grids and tune settings; the buffers; the main sequence's arrays and cursors
+static int rg_plan(RgBatch &B)
+{
+	Lane &L = B.L; bsx_device_t *d = B.d; const int64_t n = B.n; const int max_len = B.max_len;
 	// $BSX_SEED_MEM_CAP (tests): a short first-pass list, so that ordinary reads take the seeded-again path too
-	const int mem_cap = bsx_tune_is_set("seed_mem_cap") ? std::max(4, (int)bsx_tune_long("seed_mem_cap", 64)) : std::max(64, max_len), list_cap = max_len + 2;
+	B.mem_cap = bsx_tune_is_set("seed_mem_cap") ? std::max(4, (int)bsx_tune_long("seed_mem_cap", 64)) : std::max(64, max_len); B.list_cap = max_len + 2;
 	// room for the interval lists (32 B each) and regions (56 B each) of the whole chunk; repeat-rich genomes average
 	// dozens of intervals per strand search, and HBM is not the scarce resource here
 	const unsigned long long lf = (unsigned long long)std::max(1, (max_len + 149) / 150);   // pools are sized per 150 bases of read
 	// the interval lists: strand search t's own stretch of mem_cap entries (k_seedt writes them where they stay), then room for the lists of the
 	// strand searches seeded again with longer lists, which go one behind the other from the cursor
-	const bool seed_direct = bsx_tune_long("seed_direct", 1) != 0 && !bsx_tune_is_set("seed_form")
-	                         && (unsigned long long)n * (unsigned long long)mem_cap <= (768ull << 20);   // (24 GB of lists: a chunk of short reads with one very long one keeps the lists one behind the other)   // ($BSX_SEED_DIRECT=0: one list behind the other, copied there when a strand search is done)
-	const unsigned long long direct_n = seed_direct ? (unsigned long long)n * (unsigned long long)mem_cap : 0;
-	const unsigned long long dense_cap = direct_n + (unsigned long long)n * (seed_direct ? 16 : 96) * lf + (1u << 20), regs_cap = (unsigned long long)n * 24 + 65536;   // (a read inside a repeat family has dozens of regions: 6 per strand search overflowed on an hg38-like genome)
+	B.seed_direct = bsx_tune_long("seed_direct", 1) != 0 && !bsx_tune_is_set("seed_form")
+	                && (unsigned long long)n * (unsigned long long)B.mem_cap <= (768ull << 20);   // (24 GB of lists: a chunk of short reads with one very long one keeps the lists one behind the other)   // ($BSX_SEED_DIRECT=0: one list behind the other, copied there when a strand search is done)
+	B.direct_n = B.seed_direct ? (unsigned long long)n * (unsigned long long)B.mem_cap : 0;
+	B.dense_cap = B.direct_n + (unsigned long long)n * (B.seed_direct ? 16 : 96) * lf + (1u << 20); B.regs_cap = (unsigned long long)n * 24 + 65536;   // (a read inside a repeat family has dozens of regions: 6 per strand search overflowed on an hg38-like genome)
 	// workgroups with a bounded life (a few tasks per lane / wave), many more of them than fit on the chip
-	const int seed_quota = (int)bsx_tune_long("seed_quota", bsx_tune_is_set("seed_form") ? 1 : 0);   // strand searches per lane, 0 = lanes take them until none is left.  The table form (k_seedt.hip) runs persistent lanes: a lane that is done takes the next strand search in the same trip (measured at hg38 scale: 68 ms against 97 with one per lane and 86 with four); the kernel without the table does best with one (292 ms against 335 with two and 359 persistent: its lanes then move through the seeding passes together)
+	B.seed_quota = (int)bsx_tune_long("seed_quota", bsx_tune_is_set("seed_form") ? 1 : 0);   // strand searches per lane, 0 = lanes take them until none is left.  The table form (k_seedt.hip) runs persistent lanes: a lane that is done takes the next strand search in the same trip (measured at hg38 scale: 68 ms against 97 with one per lane and 86 with four); the kernel without the table does best with one (292 ms against 335 with two and 359 persistent: its lanes then move through the seeding passes together)
 	// extensions after which the first seeding pass hands a strand search to the second one (0: never)
 	// (4096 for reads of 150 bases, which need ~1.2 k; in proportion for longer ones)
-	const int trip_budget = std::max(0, (int)bsx_tune_long("seed_trip_budget", 4096));   // (the kernel scales it per 256 bases of read)
-	const int reg_quota = std::max(1, (int)bsx_tune_long("regions_quota", 16));
-	const int n_slabs = d->n_cu * 16;
+	B.trip_budget = std::max(0, (int)bsx_tune_long("seed_trip_budget", 4096));   // (the kernel scales it per 256 bases of read)
+	B.budget2_mul = std::max(1, (int)bsx_tune_long("seed_budget2", 8));   // the second pass's budget, in first-pass budgets
+	B.merge_min = bsx_tune_long("redo_merge_min", 4096);   // (tests: 1 = always merged, a huge number or a negative one = never)
+	B.reg_quota = std::max(1, (int)bsx_tune_long("regions_quota", 16));
+	B.n_slabs = d->n_cu * 16;
 	const int seed_wpc = 16;   // quota 0 = persistent waves, sixteen per CU
-	int grid = seed_quota > 0 ? (int)((n + 256LL * seed_quota - 1) / (256LL * seed_quota))
+	B.grid = B.seed_quota > 0 ? (int)((n + 256LL * B.seed_quota - 1) / (256LL * B.seed_quota))
 	                          : (int)((std::min<int64_t>((n + 63) / 64, (int64_t)d->n_cu * seed_wpc) + 3) / 4);
-	const size_t lanes = (size_t)n_slabs * 64, scratch_bytes = lanes * ((size_t)mem_cap * 32 + (size_t)list_cap * 16);   // as in lane_seed_batch
+	const size_t scratch_bytes = (size_t)B.n_slabs * 64 * seed_lane_bytes(B.mem_cap, B.list_cap);
 	// the HBM tiers: workgroups of four waves over per-wave slabs; they are bound by the latency of their slabs, so what counts is waves in flight:
 	// three workgroups per CU for the first (its kernel is held to 168 VGPRs for that and spills: 710 -> 578 ms per chunk on the hg38-like genome
 	// all the same), one per CU for the second (1.3 MB of slab a wave; 222 -> 167 ms: a launch lasts as long as its largest strand search)
 	// (the last tier: one workgroup of four waves per CU, or two -- "tier3_wgs"; its list longest strand search first -- "tier3_order")
-	const int big_grid = d->n_cu * 3, huge_grid = d->n_cu * std::max(1, std::min(3, (int)bsx_tune_long("tier3_wgs", 2)));
-	const bool order3 = bsx_tune_long("tier3_order", 1) != 0;
-	if ((rc = L.scratch.reserve(scratch_bytes)) != BSX_OK) return rc;
-	if ((rc = L.jobs.reserve((size_t)n * sizeof(bsx_seed_task_t))) != BSX_OK) return rc;
-	if ((rc = L.out.reserve((size_t)dense_cap * sizeof(DevIntv))) != BSX_OK) return rc;
-	if ((rc = L.aux.reserve((size_t)n * 12 + 64)) != BSX_OK) return rc;
-	if ((rc = L.qpack.reserve(seedt_pack_bytes(n))) != BSX_OK) return rc;
-	if ((rc = L.regs.reserve((size_t)regs_cap * sizeof(bsx_region_t))) != BSX_OK) return rc;
-	if ((rc = L.regmeta.reserve((size_t)n * 49 + 64)) != BSX_OK) return rc;
-	const int c2rh_grid = d->n_cu * 5;   // workgroups of the chains -> regions launch with its tables in HBM (a slab each)
-	if ((rc = L.c2rslab.reserve((size_t)c2rh_grid * c2r_hbm_slab_bytes())) != BSX_OK) return rc;
-	if ((rc = L.slabs.reserve((size_t)big_grid * 6 * regions_slab_bytes(2))) != BSX_OK) return rc;   // (the exporting form runs three workgroups per CU)
-	if ((rc = L.slabs3.reserve((size_t)huge_grid * 4 * regions_slab_bytes(3))) != BSX_OK) return rc;
+	B.big_grid = d->n_cu * 3; B.huge_grid = d->n_cu * std::max(1, std::min(3, (int)bsx_tune_long("tier3_wgs", 2)));
+	B.order3 = bsx_tune_long("tier3_order", 1) != 0;
+	B.c2rh_grid = d->n_cu * 5;   // workgroups of the chains -> regions launch with its tables in HBM (a slab each)
+	B.chain = (int)bsx_tune_long("chain_stages", 3);   // 0: none, 1: seeding, 2: seeding and regions, 3: the same but the HBM tiers (a few long strand searches on a few waves) hold nobody back (measured A/B on one box, 16 chunks: 1.76 / 1.81 M reads/s with 2, 2.00 / 1.89 M with 3)
+	// tier 1 -> ra -> LDS tier with larger tables -> rm -> tier 2 (HBM slabs) -> rb -> tier 3
+	B.use_mid = (int)bsx_tune_long("regions_mid", 1);
+	// strand searches a wave of the larger LDS tier / of the chains -> regions launch takes before it leaves (bounded workgroup life)
+	B.mid_quota = std::max(1, (int)bsx_tune_long("mid_quota", 8));
+	B.c2r_quota = std::max(1, (int)bsx_tune_long("c2r_quota", 16));
+	B.use_1c = bsx_tune_long("tier1c", 1) != 0;   // ($BSX_TIER1C=0: the tier sequence of rounds 2-4, for the A/B)
+	B.tier2_export = (int)bsx_tune_long("tier2_export", 0);   // 1: the first HBM tier in steps (run_tiers_ordinary) instead of its monolithic form (chains, filter and extensions inline in one launch)
+	// $BSX_PHASES: the main sequence's launches one by one (events between them); $BSX_TIERS: the launch times alone (no cycle counters in the kernels)
+	// $BSX_PHASES=2: the stage counters read (and zeroed) after every launch of the main sequence: where each tier's wave cycles go
+	B.trace = bsx_phases() != 0; B.trace_tiers = B.trace || bsx_tune_long("tiers", 0) != 0; B.per_tier = bsx_phases() == 2;
+	// The last HBM tier beside the others (rg_occ_and_early_tier3): not with the exporting tiers (kilobase reads, the seed filter), and not
+	// under phases=2 (the stage counters are read tier by tier).
+	B.early3 = bsx_tune_long("tier3_early", 1) != 0 && !B.export_all && !B.long_reads && bsx_phases() != 2 && L.st3;
+	TRY(L.scratch.reserve(scratch_bytes));
+	TRY(L.jobs.reserve((size_t)n * sizeof(bsx_seed_task_t)));
+	TRY(L.out.reserve((size_t)B.dense_cap * sizeof(DevIntv)));
+	TRY(L.aux.reserve((size_t)n * 12 + 64));
+	TRY(L.qpack.reserve(seedt_pack_bytes(n)));
+	TRY(L.regs.reserve((size_t)B.regs_cap * sizeof(bsx_region_t)));
+	TRY(L.regmeta.reserve((size_t)n * 49 + 64));
+	TRY(L.c2rslab.reserve((size_t)B.c2rh_grid * c2r_hbm_slab_bytes()));
+	TRY(L.slabs.reserve((size_t)B.big_grid * 6 * regions_slab_bytes(2)));   // (the exporting form runs three workgroups per CU)
+	TRY(L.slabs3.reserve((size_t)B.huge_grid * 4 * regions_slab_bytes(3)));
 	// one u64 per seed occurrence of the chunk: ~125 per strand search against an hg38-sized genome (a 3-letter 19-mer has random
 	// copies there), a few dozen against small ones.  $BSX_POS_CAP (tests): a cap small enough for strand searches to find no room.
-	const unsigned long long pos_cap = bsx_tune_is_set("pos_cap") ? strtoull(bsx_tune_str("pos_cap"), 0, 10) : (unsigned long long)n * 384 * lf + (1u << 20);
-	if ((rc = L.pos.reserve((size_t)pos_cap * 8)) != BSX_OK) return rc;
-	if ((rc = L.posoff.reserve((size_t)n * 8 + 64)) != BSX_OK) return rc;
+	B.pos_cap = bsx_tune_is_set("pos_cap") ? strtoull(bsx_tune_str("pos_cap"), 0, 10) : (unsigned long long)n * 384 * lf + (1u << 20);
+	TRY(L.pos.reserve((size_t)B.pos_cap * 8));
+	TRY(L.posoff.reserve((size_t)n * 8 + 64));
 	// what the LDS tiers export for the chains -> regions launch: ~0.5 KB per strand search (a task that finds no room goes to the next tier)
-	const unsigned long long xcap = (unsigned long long)n * 2560 * lf + (64u << 20);   // (a dozen chains per strand search at hg38 size: 24 + 16 bytes each, 48 more for its extensions)
-	if ((rc = L.xpool.reserve((size_t)xcap)) != BSX_OK) return rc;
-	if ((rc = L.xmeta.reserve((size_t)n * 12 + 64)) != BSX_OK) return rc;
+	B.xcap = (unsigned long long)n * 2560 * lf + (64u << 20);   // (a dozen chains per strand search at hg38 size: 24 + 16 bytes each, 48 more for its extensions)
+	TRY(L.xpool.reserve((size_t)B.xcap));
+	TRY(L.xmeta.reserve((size_t)n * 12 + 64));
 	// the extensions of the exported chains' best seeds are made ahead of chains -> regions, four to a wavefront (k_ext4.hip); $BSX_X4=0: all
 	// of them inline in k_c2r (the tests compare the two).  Not for chunks whose lists the seed-SW filter rewrites after the export.
-	const int use_x4 = (int)bsx_tune_long("x4", 1);
-	const unsigned long long x4_cap = (unsigned long long)n * 12 * lf + (1u << 20);
-	if (use_x4 && !export_all && (rc = L.x4jobs.reserve((size_t)x4_cap * x4_job_bytes())) != BSX_OK) return rc;
+	B.use_x4 = (int)bsx_tune_long("x4", 1);
+	B.x4_cap = (unsigned long long)n * 12 * lf + (1u << 20);
+	if (B.use_x4 && !B.export_all) TRY(L.x4jobs.reserve((size_t)B.x4_cap * x4_job_bytes()));
 	// the seed filter's alignments (reads of 700 bases and more: memchain.c:501-535) are one batch per chunk: a few dozen per strand search
 	// ($BSX_SSW_CAP, tests: a list too short for the chunk -- what finds no room in it is aligned a wavefront at a time)
-	const unsigned long long ssw_cap = !any_flt ? 0 : bsx_tune_is_set("ssw_cap") ? std::max(8ull, strtoull(bsx_tune_str("ssw_cap"), 0, 10))
+	B.ssw_cap = !B.any_flt ? 0 : bsx_tune_is_set("ssw_cap") ? std::max(8ull, strtoull(bsx_tune_str("ssw_cap"), 0, 10))
 	                                   : std::min<unsigned long long>((unsigned long long)n * 24 * lf + (1u << 20), 0x3ffffff0ull);
-	if (any_flt && (rc = L.sswjobs.reserve((size_t)ssw_cap * seedsw_job_bytes())) != BSX_OK) return rc;
-	unsigned long long *d_pos = (unsigned long long*)L.pos.p; long long *d_posoff = (long long*)L.posoff.p;
-	long long *d_off = (long long*)L.aux.p; int *d_n = (int*)((char*)L.aux.p + (size_t)n * 8);
-	long long *r_off = (long long*)L.regmeta.p; int *r_n = (int*)((char*)L.regmeta.p + (size_t)n * 8);
-	int *retry_a = (int*)((char*)L.regmeta.p + (size_t)n * 12), *retry_b = (int*)((char*)L.regmeta.p + (size_t)n * 16);
-	int *retry_m = (int*)((char*)L.regmeta.p + (size_t)n * 20);
-	int *retry_l = (int*)((char*)L.regmeta.p + (size_t)n * 24);
-	unsigned char *d_cls = (unsigned char*)L.regmeta.p + (size_t)n * 28;
-	int *retry_c = (int*)((char*)L.regmeta.p + (((size_t)n * 29 + 3) & ~(size_t)3));   // what the first chains -> regions launch declines (ordinary chunks)
-	int *retry_e = retry_c + 4 * n;   // what launch_occ lists for the last HBM tier ahead of everything else (u32 count and cursor: slot 22)
-	int *retry_h = retry_c + n, *xlist_t2 = retry_c + 2 * n, *retry_f = retry_c + 3 * n;   // round 6: what the second declines (-> the one with tables in HBM); the strand searches the first HBM tier exports; what takes that tier's full form
-	// counters (u64 slots of L.small): [4] interval cursor  [5] seed task cursor  [6] region cursor
-	// u32 view from slot 7: [0] tier-1 task cursor [1] tier-2 count [2] tier-2 cursor [3] tier-3 count [4] tier-3 cursor
-	//                       [5] redo count [6] redo tier-3 cursor [7] redo seed task cursor  ([8],[9] = u64 slot 11: the K3 cursor)
-	//                       [10] count of what the LDS tier in between hands to tier 2  [11] that tier's cursor
-	//                       u64 slot 13: cursor of the export pool; slot 14 as two u32: exported task count, k_c2r's cursor
-	unsigned long long *ctr = dev_counters(L);
-	unsigned int *c32 = (unsigned int*)(ctr + 7);
-	RgXPoolArg XA;
-	XA.base = (unsigned char*)L.xpool.p; XA.cap = xcap; XA.cursor = ctr + 13; XA.xoff = (long long*)L.xmeta.p; XA.xlist = (int*)((char*)L.xmeta.p + (size_t)n * 8);
-	XA.xcount = (unsigned int*)(ctr + 14);
-	XA.ext = use_x4 && !export_all ? 1 : 0;
-	const uint8_t *d_reads = (const uint8_t*)L.reads.p;
-	const bsx_seed_task_t *d_tasks = (const bsx_seed_task_t*)L.jobs.p;
+	if (B.any_flt) TRY(L.sswjobs.reserve((size_t)B.ssw_cap * seedsw_job_bytes()));
+
+	TierSeq &M = B.main;
+	M.st = L.st; M.main_seq = true; M.c = ctr_tiers(L, true);
+	Bump lists(L.aux), meta(L.regmeta), xmeta(L.xmeta), posoff(L.posoff);
+	seq_carve(M, (size_t)n, lists, meta, xmeta, posoff);
+	B.retry_e = meta.take<int>((size_t)n);
+	if (!lists.ok() || !meta.ok() || !xmeta.ok() || !posoff.ok()) return BSX_E_INTERNAL;
+	CtrShared *SH = ctr_shared(L);
+	RgLaunch &G = M.G;
+	G.ix = &d->ix; G.sc = &L.sc; G.P = &B.R; G.reads = (const uint8_t*)L.reads.p; G.tasks = (const bsx_seed_task_t*)L.jobs.p;
+	G.seeds_dense = (const DevIntv*)L.out.p;
+	G.out = (bsx_region_t*)L.regs.p; G.out_cap = B.regs_cap; G.out_cursor = &SH->region_cursor;
+	G.counters = dev_counters(L); G.pos = (unsigned long long*)L.pos.p;
+	M.X.base = (unsigned char*)L.xpool.p; M.X.cap = B.xcap; M.X.cursor = &SH->xpool_cursor; M.X.xcount = &M.c->front.x_count;
+	M.X.ext = B.use_x4 && !B.export_all ? 1 : 0;
+	return BSX_OK;
+}
+
+// stage 3 (lane's stream): the tasks up, the cursors zeroed, the chunk-wide seeding pass behind the chunk before it
+static int rg_seed_first(RgBatch &B)
+{
+	Lane &L = B.L; bsx_device_t *d = B.d; const int64_t n = B.n; TierSeq &M = B.main;
+	CtrShared *SH = ctr_shared(L); unsigned long long *ctr = dev_counters(L);
 	L.rb_tasks = n;
 	L.ddl.valid = false;
-	H2D(L.st, L.jobs.p, tasks, (size_t)n * sizeof(bsx_seed_task_t));
-	HIPCHK(hipMemsetAsync(ctr + 4, 0, 96, L.st));
-	HIPCHK(hipMemsetAsync(ctr + 20, 0, 8, L.st));   // (count and cursor of the second chains -> regions launch)
-	HIPCHK(hipMemsetAsync(ctr + 22, 0, 8, L.st));   // (count and cursor of the early launch of the last HBM tier)
-	HIPCHK(hipMemsetAsync(ctr + 119, 0, 8, L.st));  // (the first seeding pass's count of strand searches to be seeded again)
-	HIPCHK(hipMemsetAsync(ctr + 70, 0, 80, L.st));  // (round 6: counts and cursors of the launches between the second chains -> regions launch and the last HBM tier)
-	HIPCHK(hipMemsetD32Async((hipDeviceptr_t)(ctr + 4), (int)(uint32_t)direct_n, 1, L.st));            // the cursor starts behind the strand searches' own stretches
-	HIPCHK(hipMemsetD32Async((hipDeviceptr_t)((uint32_t*)(ctr + 4) + 1), (int)(uint32_t)(direct_n >> 32), 1, L.st));
-	const int chain = (int)bsx_tune_long("chain_stages", 3);   // 0: none, 1: seeding, 2: seeding and regions, 3: the same but the HBM tiers (a few long strand searches on a few waves) hold nobody back (measured A/B on one box, 16 chunks: 1.76 / 1.81 M reads/s with 2, 2.00 / 1.89 M with 3)
-	if (chain >= 1) {
+	H2D(L.st, L.jobs.p, B.tasks, (size_t)n * sizeof(bsx_seed_task_t));
+	HIPCHK(hipMemsetAsync(SH, 0, offsetof(CtrShared, early3), L.st));
+	HIPCHK(hipMemsetAsync(&M.c->front, 0, sizeof(M.c->front), L.st));
+	HIPCHK(hipMemsetAsync(&SH->early3, 0, sizeof(SH->early3), L.st));
+	HIPCHK(hipMemsetAsync(ctr + CTR_OVERFLOW, 0, 8, L.st));  // (the first seeding pass's count of strand searches to be seeded again)
+	HIPCHK(hipMemsetAsync(&M.c->late, 0, sizeof(M.c->late), L.st));
+	HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&SH->seed.intv_cursor, (int)(uint32_t)B.direct_n, 1, L.st));            // the cursor starts behind the strand searches' own stretches
+	HIPCHK(hipMemsetD32Async((hipDeviceptr_t)((uint32_t*)&SH->seed.intv_cursor + 1), (int)(uint32_t)(B.direct_n >> 32), 1, L.st));
+	if (B.chain >= 1) {
 		std::lock_guard<std::mutex> g(d->chain_mu);
 		if (d->chain_seed && d->chain_seed != L.ev_seed_done) HIPCHK(hipStreamWaitEvent(L.st, d->chain_seed, 0));
 		// 4: front halves one after the other -- a chunk's seeding also waits for the region kernels of the chunk before it
-		if (chain >= 4 && d->chain_regions && d->chain_regions != L.ev_regions_done) HIPCHK(hipStreamWaitEvent(L.st, d->chain_regions, 0));
+		if (B.chain >= 4 && d->chain_regions && d->chain_regions != L.ev_regions_done) HIPCHK(hipStreamWaitEvent(L.st, d->chain_regions, 0));
 	}
-	HIPCHK(hipEventRecord(L.ev0, L.st));
-	launch_seed(L.st, grid, d->ix, d_reads, d_tasks, (int)n, P,
-	            (DevIntv*)L.scratch.p, list_cap, mem_cap, (DevIntv*)L.out.p, dense_cap, ctr + 4, d_off, d_n,
-	            (unsigned int*)(ctr + 5), ctr, seed_quota, (unsigned int*)L.slabflags.p, n_slabs, trip_budget, R.prof, (uint32_t*)L.qpack.p, seed_direct ? 0ull : ~0ull);
-	HIPCHK(hipEventRecord(L.ev1, L.st));
-	if (chain >= 1) {
+	HIPCHK(hipEventRecord(L.ev_timed_begin, L.st));
+	launch_seed(L.st, B.grid, d->ix, M.G.reads, M.G.tasks, (int)n, B.P,
+	            (DevIntv*)L.scratch.p, B.list_cap, B.mem_cap, (DevIntv*)L.out.p, B.dense_cap, &SH->seed.intv_cursor, M.offs, M.cnts,
+	            &SH->seed.task_cursor, ctr, B.seed_quota, (unsigned int*)L.slabflags.p, B.n_slabs, B.trip_budget, B.R.prof, (uint32_t*)L.qpack.p, B.seed_direct ? 0ull : ~0ull);
+	HIPCHK(hipEventRecord(L.ev_timed_end, L.st));
+	if (B.chain >= 1) {
 		std::lock_guard<std::mutex> g(d->chain_mu);
 		HIPCHK(hipEventRecord(L.ev_seed_done, L.st));
 		d->chain_seed = L.ev_seed_done;
 	}
-	// Strand searches whose interval list overflowed are seeded again with lists eight times as long.  A few of them (reads inside tandem
-	// repeats: ~300 k dependent FM steps on one lane, tens of milliseconds) go to the side stream and through a tier sequence of their own
-	// while the main one runs (below).  MANY of them -- an hg38-like genome: 4 % of the strand searches, reads inside young copies of a repeat
-	// family, 23 ms for 43 k -- are seeded again right here and rejoin the chunk's one tier sequence (round 5): the second sequence could only
-	// start when the first had ended (shared slabs and export lists), and the front half waited for it as long again as for the first
-	// whenever the chunks in flight were in step (the command line's steady state: 8.5 s front halves).  The price is a host round trip
-	// between seeding and the suffix-array lookups for every chunk (the counts, 8 MB).
-	std::vector<int> first_n;   // the first pass's counts (negative: overflowed)
-	std::vector<int> merged_which; const int *merged_cnt = nullptr;   // the strand searches of the second pass inside this sequence, and where their new counts are
-	bool merged = false;
-	const int budget2_mul = std::max(1, (int)bsx_tune_long("seed_budget2", 8));   // the second pass's budget, in first-pass budgets
-	const long merge_min = bsx_tune_long("redo_merge_min", 4096);   // (tests: 1 = always merged, a huge number or a negative one = never)
-	// Whether there are that many is the kernel's own count (counters[119]: 8 bytes back, not every strand search's count), and the host waits
+	return BSX_OK;
+}
+
+// stage 4 (lane's stream): the merged second pass.
+// Strand searches whose interval list overflowed are seeded again with lists eight times as long.  A few of them (reads inside tandem
+// repeats: ~300 k dependent FM steps on one lane, tens of milliseconds) go to the side stream and through a tier sequence of their own
+// while the main one runs (rg_side_sequence).  MANY of them -- an hg38-like genome: 4 % of the strand searches, reads inside young copies of a
+// repeat family, 23 ms for 43 k -- are seeded again right here and rejoin the chunk's one tier sequence (round 5): the second sequence could
+// only start when the first had ended (shared slabs and export lists), and the front half waited for it as long again as for the first
+// whenever the chunks in flight were in step (the command line's steady state: 8.5 s front halves).  The price is a host round trip
+// between seeding and the suffix-array lookups for every chunk (the counts, 8 MB).
+static int rg_seed_merged(RgBatch &B)
+{
+	Lane &L = B.L; bsx_device_t *d = B.d; const int64_t n = B.n; TierSeq &M = B.main;
+	CtrShared *SH = ctr_shared(L); unsigned long long *ctr = dev_counters(L);
+	// Whether there are that many is the kernel's own count (CTR_OVERFLOW: 8 bytes back, not every strand search's count), and the host waits
 	// for it only when the lane's last chunk came anywhere near the threshold: on a clean genome, where a few dozen overflow, nothing stands
 	// between a chunk's seeding and its suffix-array lookups after the lane's first chunk.
 	unsigned long long n_over = 0;
-	const bool may_merge = merge_min >= 0 && merge_min <= (long)n;
-	if (may_merge && (L.last_overflow < 0 || L.last_overflow >= merge_min / 4)) {
-		HIPCHK(hipEventSynchronize(L.ev1));
-		D2H(L.st, &n_over, ctr + 119, 8);
+	const bool may_merge = B.merge_min >= 0 && B.merge_min <= (long)n;
+	if (may_merge && (L.last_overflow < 0 || L.last_overflow >= B.merge_min / 4)) {
+		HIPCHK(hipEventSynchronize(L.ev_timed_end));
+		D2H(L.st, &n_over, ctr + CTR_OVERFLOW, 8);
 		L.last_overflow = (long)n_over;
 	}
-	if (may_merge && (long)n_over >= merge_min) {
-		first_n.resize((size_t)n);
-		D2H(L.st, first_n.data(), d_n, (size_t)n * 4);
+	if (may_merge && (long)n_over >= B.merge_min) {
+		B.first_n.resize((size_t)n);
+		D2H(L.st, B.first_n.data(), M.cnts, (size_t)n * 4);
 		std::vector<int> which;
-		for (int64_t i = 0; i < n; ++i) if (first_n[i] < 0) which.push_back((int)i);
+		for (int64_t i = 0; i < n; ++i) if (B.first_n[i] < 0) which.push_back((int)i);
 		const size_t n2 = which.size();
-		const int g2 = (int)((n2 + 255) / 256);
-		const long long cap2 = std::max<long long>((long long)mem_cap * 8, 1024);
-		const size_t scratch2 = (size_t)g2 * 256 * ((size_t)cap2 * 32 + (size_t)list_cap * 16);
-		if ((long)n2 >= merge_min && n2 > 0 && n2 <= 262144 && g2 * 4 <= n_slabs && scratch2 <= ((size_t)24 << 30)) {
-			if ((rc = L.scratch2.reserve(scratch2)) != BSX_OK) return rc;
-			if ((rc = L.redo.reserve(n2 * (sizeof(bsx_seed_task_t) + 8 + 4 + 4) + 1024)) != BSX_OK) return rc;
+		const SeedAgain sa = seed_again_size(n2, B.mem_cap, B.list_cap, B.n_slabs);
+		if ((long)n2 >= B.merge_min && n2 > 0 && n2 <= 262144 && sa.fits) {
+			TRY(L.scratch2.reserve(sa.scratch));
+			TRY(L.redo.reserve(n2 * (sizeof(bsx_seed_task_t) + 8 + 4 + 4) + 1024));
 			L.rs.sub.resize(n2);
-			for (size_t j = 0; j < n2; ++j) L.rs.sub[j] = tasks[which[j]];
-			bsx_seed_task_t *t2 = (bsx_seed_task_t*)L.redo.p;
-			long long *off2 = (long long*)(t2 + n2); int *cnt2 = (int*)(off2 + n2); int *which_d = cnt2 + n2;
+			for (size_t j = 0; j < n2; ++j) L.rs.sub[j] = B.tasks[which[j]];
+			Bump b(L.redo);
+			bsx_seed_task_t *t2 = b.take<bsx_seed_task_t>(n2);
+			long long *off2 = b.take<long long>(n2); int *cnt2 = b.take<int>(n2); int *which_d = b.take<int>(n2);
+			if (!b.ok()) return BSX_E_INTERNAL;
 			H2D(L.st, t2, L.rs.sub.data(), n2 * sizeof(bsx_seed_task_t));
 			H2D(L.st, which_d, which.data(), n2 * sizeof(int));
-			HIPCHK(hipMemsetAsync(ctr + 99, 0, 8, L.st));   // (u32 [7] of the second sequence's cursors: its seed task cursor)
-			HIPCHK(hipEventRecord(L.ev5, L.st));
+			HIPCHK(hipMemsetAsync(&SH->seed2_task_cursor, 0, sizeof(SH->seed2_task_cursor), L.st));
+			HIPCHK(hipEventRecord(L.ev_seed2_begin, L.st));
 			// (with a budget of its own, eight times the first pass's: the launch lasts as long as its slowest lane, and the handful of reads
 			// inside tandem repeats -- hundreds of thousands of dependent FM steps -- made it 90-170 ms for 23 ms of work; they go on to the
-			// side stream below like the few of a clean genome)
-			launch_seed(L.st, g2, d->ix, d_reads, t2, (int)n2, P, (DevIntv*)L.scratch2.p, list_cap, (int)cap2, (DevIntv*)L.out.p, dense_cap, ctr + 4,
-			            off2, cnt2, (unsigned int*)(ctr + 96) + 7, ctr + SEED2_CTR, 0, (unsigned int*)L.slabflags.p, g2 * 4, trip_budget * budget2_mul, bsx_phases() ? 2 : 0, (uint32_t*)L.qpack.p);
-			hipLaunchKernelGGL(k_patch_lists, dim3((unsigned int)((n2 + 255) / 256)), dim3(256), 0, L.st, (const int*)which_d, (int)n2, (const long long*)off2, (const int*)cnt2, d_off, d_n);
-			HIPCHK(hipEventRecord(L.ev6, L.st));
-			merged = true; merged_which.swap(which); merged_cnt = cnt2;
+			// side stream like the few of a clean genome)
+			launch_seed(L.st, sa.grid, d->ix, M.G.reads, t2, (int)n2, B.P, (DevIntv*)L.scratch2.p, B.list_cap, (int)sa.cap, (DevIntv*)L.out.p, B.dense_cap, &SH->seed.intv_cursor,
+			            off2, cnt2, &SH->seed2_task_cursor, ctr + CTR_SEED2, 0, (unsigned int*)L.slabflags.p, sa.grid * 4, B.trip_budget * B.budget2_mul, bsx_phases() ? 2 : 0, (uint32_t*)L.qpack.p);
+			hipLaunchKernelGGL(k_patch_lists, dim3((unsigned int)((n2 + 255) / 256)), dim3(256), 0, L.st, (const int*)which_d, (int)n2, (const long long*)off2, (const int*)cnt2, M.offs, M.cnts);
+			HIPCHK(hipEventRecord(L.ev_seed2_end, L.st));
+			B.merged = true; B.merged_which.swap(which); B.merged_cnt = cnt2;
 			if (bsx_phases()) fprintf(stderr, "[M::regions_batch] %zu strand searches seeded again inside the main sequence\n", n2);
 		}
 	}
-	if (!merged) { HIPCHK(hipEventRecord(L.ev5, L.st)); HIPCHK(hipEventRecord(L.ev6, L.st)); }
-	// The last HBM tier beside the others (round 6): its launch lasts as long as its longest strand search -- 190 ms for a read inside a tandem repeat,
-	// on a device it leaves almost empty -- and what it takes is known as soon as the occurrences are counted (more intervals or occurrences than the
-	// tier before it holds).  launch_occ lists those, the first tier skips them, and the launch goes to a stream of its own right behind the
-	// suffix-array lookups; what the first HBM tier hands on later (a strand search that grew along the way) gets the launch at the end as before.
-	// Not with the exporting tiers (kilobase reads, the seed filter), and not under phases=2 (the stage counters are read tier by tier).
-	const bool early3 = bsx_tune_long("tier3_early", 1) != 0 && !export_all && !long_reads && bsx_phases() != 2 && L.st3;
-	launch_occ(L.st, d->n_cu, d->ix, d_tasks, (int)n, (const DevIntv*)L.out.p, d_off, d_n, opt->max_occ, d_pos, pos_cap, ctr + 11, d_posoff, ctr, d_cls, nullptr,
-	           early3 ? retry_e : nullptr, early3 ? (unsigned int*)(ctr + 22) : nullptr);
-	HIPCHK(hipEventRecord(L.ev4, L.st));
-	if (early3) {
-		HIPCHK(hipStreamWaitEvent(L.st3, L.ev4, 0));
+	if (!B.merged) { HIPCHK(hipEventRecord(L.ev_seed2_begin, L.st)); HIPCHK(hipEventRecord(L.ev_seed2_end, L.st)); }
+	return BSX_OK;
+}
+
+// stage 5 (lane's stream, then the lane's third): the suffix-array lookups, and the last HBM tier beside the others (round 6).
+// That tier's launch lasts as long as its longest strand search -- 190 ms for a read inside a tandem repeat, on a device it leaves almost
+// empty -- and what it takes is known as soon as the occurrences are counted (more intervals or occurrences than the tier before it holds).
+// launch_occ lists those, the first tier skips them, and the launch goes to a stream of its own right behind the suffix-array lookups; what
+// the first HBM tier hands on later (a strand search that grew along the way) gets the launch at the end as before.
+static int rg_occ_and_early_tier3(RgBatch &B)
+{
+	Lane &L = B.L; bsx_device_t *d = B.d; TierSeq &M = B.main; CtrShared *SH = ctr_shared(L);
+	launch_occ(L.st, d->n_cu, M.G, B.opt->max_occ, B.pos_cap, &SH->k3_cursor, M.cls, nullptr,
+	           B.early3 ? B.retry_e : nullptr, B.early3 ? &SH->early3.count : nullptr);
+	HIPCHK(hipEventRecord(L.ev_occ_end, L.st));
+	if (B.early3) {
+		HIPCHK(hipStreamWaitEvent(L.st3, L.ev_occ_end, 0));
 		HIPCHK(hipEventRecord(L.ev_t3a, L.st3));
-		if (order3) launch_order_list(L.st3, retry_e, (unsigned int*)(ctr + 22), (const DevIntv*)L.out.p, d_off, d_n, opt->max_occ);
-		launch_regions_slab(L.st3, 3, huge_grid, d->ix, L.sc, R, d_reads, d_tasks, (const DevIntv*)L.out.p, d_off, d_n,
-		                    (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, r_off, r_n, retry_e, (unsigned int*)(ctr + 22), (unsigned int*)(ctr + 22) + 1, L.slabs3.p, nullptr, nullptr, ctr, d_posoff, d_pos);
+		if (B.order3) launch_order_list(L.st3, B.retry_e, &SH->early3.count, M.G.seeds_dense, M.offs, M.cnts, B.opt->max_occ);
+		launch_regions_slab(L.st3, 3, B.huge_grid, M.G, B.retry_e, &SH->early3.count, &SH->early3.cursor, L.slabs3.p, nullptr, nullptr);
 		HIPCHK(hipEventRecord(L.ev_t3b, L.st3));
 	}
-	if (chain >= 2) {
+	if (B.chain >= 2) {
 		std::lock_guard<std::mutex> g(d->chain_mu);
 		if (d->chain_regions && d->chain_regions != L.ev_regions_done) HIPCHK(hipStreamWaitEvent(L.st, d->chain_regions, 0));
 	}
-	// tier 1 -> retry_a -> LDS tier with larger tables -> retry_m -> tier 2 (HBM slabs) -> retry_b -> tier 3
-	const int use_mid = (int)bsx_tune_long("regions_mid", 1);
-	// strand searches a wave of the larger LDS tier / of the chains -> regions launch takes before it leaves (bounded workgroup life)
-	const int mid_quota = std::max(1, (int)bsx_tune_long("mid_quota", 8));
-	const int c2r_quota = std::max(1, (int)bsx_tune_long("c2r_quota", 16));
-	// The tier sequence over a task list (the chunk's, and once more the re-seeded strand searches' on the side stream).  k32: u32 cursors and
-	// counts ([0] tier-1 cursor [1] tier-2 count [2] tier-2 cursor [3] tier-3 count [4] tier-3 cursor [5] k_seedsw's cursor [10] what the
-	// larger LDS tier hands on [11] its cursor); xc32: exported count | k_c2r's cursor.
-	const bool trace_tiers = bsx_phases() != 0 || bsx_tune_long("tiers", 0) != 0;   // $BSX_TIERS: the launch times alone (no cycle counters in the kernels)
-	int n_marks = 0; const char *mark_name[12];
-	auto run_tiers = [&](hipStream_t st, const bsx_seed_task_t *T, int64_t nT, const long long *offs, const int *cnts, long long *roffs, int *rns,
-	                     int *ra, int *rm, int *rb, unsigned int *k32, unsigned int *xc32, const RgXPoolArg &XP, const long long *posoffs,
-	                     const unsigned char *clsx, bool main_seq, int *rl, unsigned int *l_count, unsigned int *l_cursor, unsigned int *x4c, int *rc_list, unsigned int *rc32, unsigned int *ssw32,
-	                     int *rh_list, int *x2_list, int *rf_list, unsigned int *h32) -> int {
-		int rc2;
-		const int rgrid = (int)((nT + 4LL * reg_quota - 1) / (4LL * reg_quota));
-		// $BSX_PHASES: the main sequence's launches one by one (events between them)
-		// $BSX_PHASES=2: the stage counters read (and zeroed) after every launch of the main sequence: where each tier's wave cycles go
-		const bool per_tier = bsx_phases() == 2;
-#define TIER_MARK(name_) do { if (main_seq && trace_tiers && n_marks < 12) { if (!L.tier_ev[n_marks]) HIPCHK(hipEventCreate(&L.tier_ev[n_marks])); HIPCHK(hipEventRecord(L.tier_ev[n_marks], st)); mark_name[n_marks++] = name_; \
-		if (per_tier) { unsigned long long pf_[16]; HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipMemcpy(pf_, ctr + 32, sizeof(pf_), hipMemcpyDeviceToHost)); HIPCHK(hipMemset(ctr + 32, 0, sizeof(pf_))); \
-			{ unsigned long long ds_[12]; HIPCHK(hipMemcpy(ds_, ctr + 160, sizeof(ds_), hipMemcpyDeviceToHost)); HIPCHK(hipMemset(ctr + 160, 0, sizeof(ds_))); \
-			  if (ds_[2] | ds_[3] | ds_[4] | ds_[6] | ds_[8] | ds_[10]) fprintf(stderr, "[M::regions_batch] %s hands on: %llu for their intervals, %llu for their occurrences (or a list too long), %llu chains, %llu tied chain starts, %llu regions, %llu an interval to be walked further\n", name_, ds_[8], ds_[2], ds_[3], ds_[4], ds_[6], ds_[10]); } \
-			if (pf_[11]) fprintf(stderr, "[M::regions_batch] %s: seed loops: %llu seeds reached, %llu skipped as contained, %llu took the extension made ahead, %llu extended in place (%llu extensions, %llu rows)\n", name_, pf_[11], pf_[12], pf_[13], pf_[14], pf_[8], pf_[9]); \
-			double tot_ = 0; for (int k_ = 0; k_ < 8; ++k_) tot_ += (double)pf_[k_]; \
-			if (tot_ > 0) fprintf(stderr, "[M::regions_batch] %s: intervals %.1f%% occurrences %.1f%% chaining %.1f%% weights+order %.1f%% sort %.1f%% filter %.1f%% prologues+seed tests %.1f%% extension %.1f%% of %.0f M wave cycles\n", name_, \
-			                      100 * pf_[0] / tot_, 100 * pf_[1] / tot_, 100 * pf_[2] / tot_, 100 * pf_[3] / tot_, 100 * pf_[4] / tot_, 100 * pf_[5] / tot_, 100 * pf_[6] / tot_, 100 * pf_[7] / tot_, tot_ * 1e-6); } } } while (0)
-		TIER_MARK("start");
-		launch_regions(st, rgrid, d->ix, L.sc, R, d_reads, T, (int)nT, (const DevIntv*)L.out.p, offs, cnts,
-		               (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, k32 + 0, ra, k32 + 1, reg_quota, ctr, posoffs, d_pos, clsx, XP, long_reads);
-		if (main_seq) HIPCHK(hipEventRecord(L.ev3, st));
-		TIER_MARK("tier 1");
-		if (use_mid)
-			launch_regions_mid(st, (int)((nT + 2LL * mid_quota - 1) / (2LL * mid_quota)), d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-			                   (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, ra, k32 + 1, k32 + 11, rm, k32 + 10, ctr, posoffs, d_pos, XP, mid_quota, long_reads);
-		TIER_MARK("tier 1b");
-		int *to2 = use_mid ? rm : ra; unsigned int *n2c = use_mid ? k32 + 10 : k32 + 1;
-		if (use_mid && long_reads) { // kilobase reads: a second LDS tier with larger tables (two workgroups per CU) for what outgrows the first (three)
-			launch_regions_mid(st, (int)((nT + 2LL * mid_quota - 1) / (2LL * mid_quota)), d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-			                   (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, rm, k32 + 10, l_cursor, rl, l_count, ctr, posoffs, d_pos, XP, mid_quota, 3);
-			to2 = rl; n2c = l_count;
-			TIER_MARK("tier 1c");
-		}
-		const bool use_1c = bsx_tune_long("tier1c", 1) != 0;   // ($BSX_TIER1C=0: the tier sequence of rounds 2-4, for the A/B)
-		const bool tier1c = use_mid && !long_reads && !export_all && use_1c;
-		if (tier1c) { // ordinary reads inside repeat families: an LDS tier with twice the tables behind the first two (round 5)
-			launch_regions_mid(st, (int)((nT + 2LL * mid_quota - 1) / (2LL * mid_quota)), d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-			                   (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, rm, k32 + 10, l_cursor, rl, l_count, ctr, posoffs, d_pos, XP, mid_quota, 4);
-			to2 = rl; n2c = l_count;
-			TIER_MARK("tier 1c");
-		}
-		const int c2r_grid = (int)((nT + 4LL * c2r_quota - 1) / (4LL * c2r_quota));
-		if (export_all) {
-			// every tier exports; then the seed-SW filter where it applies, then chains -> regions (what outgrows its tables is left to the caller)
-			launch_regions_slab(st, 2, big_grid, d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-			                    (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, to2, n2c, k32 + 2, L.slabs.p, rb, k32 + 3, ctr, posoffs, d_pos, &XP);
-			TIER_MARK("tier 2 (exports)");
-			launch_regions_slab(st, 3, huge_grid, d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-			                    (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, rb, k32 + 3, k32 + 4, L.slabs3.p, nullptr, nullptr, ctr, posoffs, d_pos, &XP);
-			TIER_MARK("tier 3 (exports)");
-			if (any_flt) { // (the side stream's run comes after the main one's on the device -- it waits for the tiers -- and may use the same job list)
-				// ssw32: [0] job count [1] the third launch's cursor; k32[5]: the first launch's
-				launch_seedsw(st, (int)std::min<int64_t>(nT, (int64_t)d->n_cu * 32), d->n_cu, d->ix, L.sc, R, d_reads, T, XP, k32 + 5, ssw32, L.sswjobs.p, (unsigned int)ssw_cap, ctr);
-			}
-			TIER_MARK("seed filter");
-#ifdef BSX_DEBUG_XCHECK
-			if (main_seq) { // debug builds (tools/dbg/lds_variants.sh): every exported record looked at before k_c2r reads it
-				unsigned long long used = 0; unsigned int xn = 0;
-				HIPCHK(hipStreamSynchronize(st));
-				D2H(st, &used, XP.cursor, 8); D2H(st, &xn, XP.xcount, 4);
-				HIPCHK(hipStreamSynchronize(st));
-				fprintf(stderr, "[xcheck] %u records, %llu bytes of %llu\n", xn, used, XP.cap);
-				if (used > XP.cap) used = XP.cap;
-				std::vector<unsigned char> a((size_t)used);
-				std::vector<long long> xo((size_t)nT); std::vector<int> xl((size_t)xn);
-				D2H(st, a.data(), XP.base, (size_t)used); D2H(st, xo.data(), XP.xoff, (size_t)nT * 8); D2H(st, xl.data(), XP.xlist, (size_t)xn * 4);
-				HIPCHK(hipStreamSynchronize(st));
-				std::vector<std::pair<long long, long long>> span;
-				long n_bad = 0;
-				for (unsigned int k = 0; k < xn; ++k) {
-					const int t = xl[k];
-					if (t < 0 || t >= nT) { fprintf(stderr, "[xcheck] list entry %u names task %d\n", k, t); ++n_bad; continue; }
-					const long long o = xo[t];
-					if (o < 0 || (unsigned long long)o + 24 > used) { fprintf(stderr, "[xcheck] task %d offset %lld\n", t, o); ++n_bad; continue; }
-					const int *H = (const int*)(a.data() + o);
-					const int nk = H[0], nsd = H[1], has = H[4], tier = H[5];
-					const long long bytes = 24 + (long long)nk * 24 + (long long)nsd * 16 + (has ? (long long)nk * 48 : 0);
-					span.push_back(std::make_pair(o, o + bytes));
-					bool bad = nk <= 0 || nsd < nk || (unsigned long long)(o + bytes) > used;
-					long long so_expect = 0;
-					for (int c = 0; c < nk && !bad; ++c) {
-						const unsigned char *xc = a.data() + o + 24 + (size_t)c * 24;
-						const long long pos = *(const long long*)xc; const int rid = *(const int*)(xc + 8), so = *(const int*)(xc + 12);
-						const int nm = *(const unsigned short*)(xc + 16), ne = *(const unsigned short*)(xc + 18);
-						if (rid < 0 || rid >= d->ix.n_seqs || pos < 0 || pos >= 2 * d->ix.l_pac || so < so_expect || so + nm + ne > nsd) {
-							fprintf(stderr, "[xcheck] task %d (len %d, tier tables %d) record at %lld: %d chains %d seeds; chain %d: pos %lld rid %d seed_off %d (expected %lld) main %d extra %d\n",
-							        t, T == d_tasks ? tasks[t].len : -1, tier, o, nk, nsd, c, pos, rid, so, so_expect, nm, ne);
-							bad = true;
-						}
-						so_expect = so + nm + ne;   // (k_seedsw shortens a main list in place and moves the backup list up behind it: offsets stay those of the export)
-					}
-					if (bad) { ++n_bad; if (nk <= 0 || nsd < nk) fprintf(stderr, "[xcheck] task %d (tier tables %d) record at %lld: %d chains %d seeds %lld bytes\n", t, tier, o, nk, nsd, bytes); }
-				}
-				std::sort(span.begin(), span.end());
-				for (size_t k = 1; k < span.size(); ++k) if (span[k].first < span[k - 1].second) { fprintf(stderr, "[xcheck] records overlap: [%lld, %lld) and [%lld, %lld)\n", span[k - 1].first, span[k - 1].second, span[k].first, span[k].second); ++n_bad; }
-				fprintf(stderr, "[xcheck] %ld bad\n", n_bad);
-			}
-#endif
-			// (what outgrows the launch's tables -- 64 regions of a strand search, 256 seeds of a list -- gets a second one with up to 1024 of each, the
-			// regions in HBM; round 6: those were forty strand searches per chunk of kilobase reads chained on the host, a second of its time each chunk)
-			launch_c2r(st, c2r_grid, d->ix, L.sc, R, d_reads, T, XP, (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, xc32 + 1, rh_list, h32 + 0, ctr, c2r_quota, long_reads);
-			{
-				RgXPoolArg XB3 = XP;
-				XB3.xlist = rh_list; XB3.xcount = h32 + 0;
-				launch_c2r(st, d->n_cu * 2, d->ix, L.sc, R, d_reads, T, XB3, (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, h32 + 1, nullptr, nullptr, ctr, 1 << 30, 4, L.c2rslab.p);
-			}
-			TIER_MARK("chains -> regions");
-			return BSX_OK;
-		}
-		// chains -> regions of everything the two LDS tiers exported; what outgrows its tables joins the list of the HBM tiers.
-		// (The first HBM tier exporting its chains as well -- 156 instead of 225 VGPRs, its chains through k_c2r with everybody else's -- was
-		// measured in rounds 3 and 4 and removed: what k_c2r cannot hold, 64 regions and 128 seeds a chain, takes the full form afterwards anyway,
-		// 1468 against 1287 ms per chunk on the hg38-like genome.  Round 6 takes it up again with a chains -> regions launch that CAN hold them:)
-		//
-		// h32 (u32): [0] what the second chains -> regions launch declines [1] the third's cursor | [4] what takes the HBM tier's full form [5] its
-		// cursor | [6] the exporting launch's cursor
-		const int t2x = tier1c && XP.ext ? (int)bsx_tune_long("tier2_export", 0) : 0;   // 1: the first HBM tier in steps (below) instead of its monolithic form (chains, filter and extensions inline in one launch)
-		if (XP.ext) {
-			launch_x4(st, d->n_cu, d->ix, L.sc, R, d_reads, T, (long long)nT, XP, L.x4jobs.p, x4_cap, x4c, R.prof ? ctr + 56 : nullptr);
-			TIER_MARK("extensions");
-		}
-		if (tier1c) { // ... and what the chains -> regions launch declines (more than 64 regions, lists of more than 128 seeds) gets a second one with larger tables
-			launch_c2r(st, c2r_grid, d->ix, L.sc, R, d_reads, T, XP, (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, xc32 + 1, rc_list, rc32, ctr, c2r_quota);
-			RgXPoolArg XB2 = XP;
-			XB2.xlist = rc_list; XB2.xcount = rc32;
-			if (t2x) { // ... and what THAT declines (up to 1024 regions, 1024 seeds a list) a third, the regions it makes in HBM: the record and its extensions are there
-				launch_c2r(st, d->n_cu * 2, d->ix, L.sc, R, d_reads, T, XB2, (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, rc32 + 1, rh_list, h32 + 0, ctr, 1 << 30, 2);
-				RgXPoolArg XB3 = XP;
-				XB3.xlist = rh_list; XB3.xcount = h32 + 0;
-				launch_c2r(st, c2rh_grid, d->ix, L.sc, R, d_reads, T, XB3, (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, h32 + 1, rf_list, h32 + 4, ctr, 1 << 30, 3, L.c2rslab.p);
-			} else
-			launch_c2r(st, d->n_cu * 2, d->ix, L.sc, R, d_reads, T, XB2, (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, rc32 + 1, to2, n2c, ctr, 1 << 30, 2);   // (few strand searches, long ones: persistent waves)
-		} else
-		launch_c2r(st, c2r_grid, d->ix, L.sc, R, d_reads, T, XP, (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, xc32 + 1, to2, n2c, ctr, c2r_quota);
-		if (main_seq && chain == 3) { // the HBM tiers (a few long strand searches on a few waves) do not hold the next chunk's region launches back
-			std::lock_guard<std::mutex> g(d->chain_mu);
-			HIPCHK(hipEventRecord(L.ev_regions_done, st));
-			d->chain_regions = L.ev_regions_done;
-		}
-		TIER_MARK("chains -> regions");
-		if (t2x) {
-			// The first HBM tier in steps (round 6, "tier2_export=1"; measured and not the default).  What outgrew the LDS tiers'
-			// tables is chained and filtered over the tier's slabs and EXPORTED like the LDS tiers' strand searches; its chains' best seeds are extended
-			// ahead, several jobs to a wavefront (k_extl / k_ext4) -- inline, a wavefront each, the extensions are 58 % of the tier's cycles --; the seed
-			// loop is run by the chains -> regions launch that keeps up to 1024 regions in HBM.  Only what even that cannot hold takes the tier's
-			// monolithic form; what outgrows the tier's tables goes on to the last tier as before.
-			RgXPoolArg XT = XP;
-			XT.xlist = x2_list; XT.xcount = h32 + 2;
-			if (t2x >= 2) XT.ext = 2;   // every seed of every main list extended ahead (a slot per seed): the seed loops of these strand searches skip one seed in fourteen
-			launch_regions_slab(st, 2, big_grid, d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-			                    (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, to2, n2c, h32 + 6, L.slabs.p, rb, k32 + 3, ctr, posoffs, d_pos, &XT);
-			TIER_MARK("tier 2 (chains)");
-			launch_x4(st, d->n_cu, d->ix, L.sc, R, d_reads, T, (long long)nT, XT, L.x4jobs.p, x4_cap, h32 + 8, nullptr);
-			TIER_MARK("tier 2 (extensions)");
-			launch_c2r(st, c2rh_grid, d->ix, L.sc, R, d_reads, T, XT, (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, h32 + 3, rf_list, h32 + 4, ctr, 1 << 30, 3, L.c2rslab.p);
-			TIER_MARK("tier 2 (chains -> regions)");
-			launch_regions_slab(st, 2, big_grid, d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-			                    (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, rf_list, h32 + 4, h32 + 5, L.slabs.p, rb, k32 + 3, ctr, posoffs, d_pos);
-		} else
-		launch_regions_slab(st, 2, big_grid, d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-		                    (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, to2, n2c, k32 + 2, L.slabs.p, rb, k32 + 3, ctr, posoffs, d_pos);
-		TIER_MARK("tier 2");
-		if (main_seq && early3) HIPCHK(hipStreamWaitEvent(st, L.ev_t3b, 0));   // (the early launch: it shares the tier's slabs, and everything behind this point waits for its regions)
-		if (order3) launch_order_list(st, rb, k32 + 3, (const DevIntv*)L.out.p, offs, cnts, opt->max_occ);
-		launch_regions_slab(st, 3, huge_grid, d->ix, L.sc, R, d_reads, T, (const DevIntv*)L.out.p, offs, cnts,
-		                    (bsx_region_t*)L.regs.p, regs_cap, ctr + 6, roffs, rns, rb, k32 + 3, k32 + 4, L.slabs3.p, nullptr, nullptr, ctr, posoffs, d_pos);
-		TIER_MARK("tier 3");
-		return BSX_OK;
-	};
-	if ((rc = run_tiers(L.st, d_tasks, n, d_off, d_n, r_off, r_n, retry_a, retry_m, retry_b, c32, (unsigned int*)(ctr + 14), XA, d_posoff, d_cls, true, retry_l, c32 + 6, c32 + 7, (unsigned int*)(ctr + 16), retry_c, (unsigned int*)(ctr + 20), (unsigned int*)(ctr + 15),
-	                    retry_h, xlist_t2, retry_f, (unsigned int*)(ctr + 70))) != BSX_OK) return rc;
+	return BSX_OK;
+}
 
-	if (chain == 2 || chain >= 4) {
+// A mark between two launches of the main sequence ($BSX_PHASES, $BSX_TIERS): an event, and under $BSX_PHASES=2 the stage counters read
+// and zeroed, the host waiting for the stream
+static int tier_mark(RgBatch &B, const TierSeq &S, const char *name)
+{
+	Lane &L = B.L; unsigned long long *ctr = dev_counters(L);
+	if (!S.main_seq || !B.trace_tiers || B.n_marks >= 12) return BSX_OK;
+	if (!L.tier_ev[B.n_marks]) HIPCHK(hipEventCreate(&L.tier_ev[B.n_marks]));
+	HIPCHK(hipEventRecord(L.tier_ev[B.n_marks], S.st)); B.mark_name[B.n_marks++] = name;
+	if (!B.per_tier) return BSX_OK;
+	unsigned long long pf[CTR_STAGE_N], ds[CTR_HANDON_N];
+	HIPCHK(hipStreamSynchronize(S.st)); HIPCHK(hipMemcpy(pf, ctr + CTR_STAGE, sizeof(pf), hipMemcpyDeviceToHost)); HIPCHK(hipMemset(ctr + CTR_STAGE, 0, sizeof(pf)));
+	HIPCHK(hipMemcpy(ds, ctr + CTR_HANDON, sizeof(ds), hipMemcpyDeviceToHost)); HIPCHK(hipMemset(ctr + CTR_HANDON, 0, sizeof(ds)));
+	if (ds[2] | ds[3] | ds[4] | ds[6] | ds[8] | ds[10]) fprintf(stderr, "[M::regions_batch] %s hands on: %llu for their intervals, %llu for their occurrences (or a list too long), %llu chains, %llu tied chain starts, %llu regions, %llu an interval to be walked further\n", name, ds[8], ds[2], ds[3], ds[4], ds[6], ds[10]);
+	if (pf[11]) fprintf(stderr, "[M::regions_batch] %s: seed loops: %llu seeds reached, %llu skipped as contained, %llu took the extension made ahead, %llu extended in place (%llu extensions, %llu rows)\n", name, pf[11], pf[12], pf[13], pf[14], pf[8], pf[9]);
+	double tot = 0; for (int k = 0; k < 8; ++k) tot += (double)pf[k];
+	if (tot > 0) fprintf(stderr, "[M::regions_batch] %s: intervals %.1f%% occurrences %.1f%% chaining %.1f%% weights+order %.1f%% sort %.1f%% filter %.1f%% prologues+seed tests %.1f%% extension %.1f%% of %.0f M wave cycles\n", name,
+	                     100 * pf[0] / tot, 100 * pf[1] / tot, 100 * pf[2] / tot, 100 * pf[3] / tot, 100 * pf[4] / tot, 100 * pf[5] / tot, 100 * pf[6] / tot, 100 * pf[7] / tot, tot * 1e-6);
+	return BSX_OK;
+}
+
+#ifdef BSX_DEBUG_XCHECK
+// debug builds (tools/dbg/lds_variants.sh): every exported record of the main sequence looked at before k_c2r reads it
+static int xcheck_exports(RgBatch &B, const TierSeq &S)
+{
+	Lane &L = B.L; bsx_device_t *d = B.d; const hipStream_t st = S.st; const RgXPoolArg &XP = S.X; const int64_t nT = S.G.n_tasks;
+	unsigned long long used = 0; unsigned int xn = 0;
+	HIPCHK(hipStreamSynchronize(st));
+	D2H(st, &used, XP.cursor, 8); D2H(st, &xn, XP.xcount, 4);
+	HIPCHK(hipStreamSynchronize(st));
+	fprintf(stderr, "[xcheck] %u records, %llu bytes of %llu\n", xn, used, XP.cap);
+	if (used > XP.cap) used = XP.cap;
+	std::vector<unsigned char> a((size_t)used);
+	std::vector<long long> xo((size_t)nT); std::vector<int> xl((size_t)xn);
+	D2H(st, a.data(), XP.base, (size_t)used); D2H(st, xo.data(), XP.xoff, (size_t)nT * 8); D2H(st, xl.data(), XP.xlist, (size_t)xn * 4);
+	HIPCHK(hipStreamSynchronize(st));
+	std::vector<std::pair<long long, long long>> span;
+	long n_bad = 0;
+	for (unsigned int k = 0; k < xn; ++k) {
+		const int t = xl[k];
+		if (t < 0 || t >= nT) { fprintf(stderr, "[xcheck] list entry %u names task %d\n", k, t); ++n_bad; continue; }
+		const long long o = xo[t];
+		if (o < 0 || (unsigned long long)o + 24 > used) { fprintf(stderr, "[xcheck] task %d offset %lld\n", t, o); ++n_bad; continue; }
+		const int *H = (const int*)(a.data() + o);
+		const int nk = H[0], nsd = H[1], has = H[4], tier = H[5];
+		const long long bytes = 24 + (long long)nk * 24 + (long long)nsd * 16 + (has ? (long long)nk * 48 : 0);
+		span.push_back(std::make_pair(o, o + bytes));
+		bool bad = nk <= 0 || nsd < nk || (unsigned long long)(o + bytes) > used;
+		long long so_expect = 0;
+		for (int c = 0; c < nk && !bad; ++c) {
+			const unsigned char *xc = a.data() + o + 24 + (size_t)c * 24;
+			const long long pos = *(const long long*)xc; const int rid = *(const int*)(xc + 8), so = *(const int*)(xc + 12);
+			const int nm = *(const unsigned short*)(xc + 16), ne = *(const unsigned short*)(xc + 18);
+			if (rid < 0 || rid >= d->ix.n_seqs || pos < 0 || pos >= 2 * d->ix.l_pac || so < so_expect || so + nm + ne > nsd) {
+				fprintf(stderr, "[xcheck] task %d (len %d, tier tables %d) record at %lld: %d chains %d seeds; chain %d: pos %lld rid %d seed_off %d (expected %lld) main %d extra %d\n",
+				        t, B.tasks[t].len, tier, o, nk, nsd, c, pos, rid, so, so_expect, nm, ne);
+				bad = true;
+			}
+			so_expect = so + nm + ne;   // (k_seedsw shortens a main list in place and moves the backup list up behind it: offsets stay those of the export)
+		}
+		if (bad) { ++n_bad; if (nk <= 0 || nsd < nk) fprintf(stderr, "[xcheck] task %d (tier tables %d) record at %lld: %d chains %d seeds %lld bytes\n", t, tier, o, nk, nsd, bytes); }
+	}
+	std::sort(span.begin(), span.end());
+	for (size_t k = 1; k < span.size(); ++k) if (span[k].first < span[k - 1].second) { fprintf(stderr, "[xcheck] records overlap: [%lld, %lld) and [%lld, %lld)\n", span[k - 1].first, span[k - 1].second, span[k].first, span[k].second); ++n_bad; }
+	fprintf(stderr, "[xcheck] %ld bad\n", n_bad);
+	return BSX_OK;
+}
+#endif
+
+// the rest of a sequence whose every tier exports (kilobase reads, the seed filter): the HBM tiers, then the seed-SW filter where it applies,
+// then chains -> regions (what outgrows its tables is left to the caller).  to2 / n2c: what the LDS tiers handed on
+static int run_tiers_exporting(RgBatch &B, TierSeq &S, int *to2, unsigned int *n2c)
+{
+	Lane &L = B.L; bsx_device_t *d = B.d; const hipStream_t st = S.st; const RgLaunch &G = S.G;
+	TierCtr::Front *c = &S.c->front; TierCtr::Late *h = &S.c->late;
+	const int64_t nT = G.n_tasks;
+	launch_regions_slab(st, 2, B.big_grid, G, to2, n2c, &c->t2_cursor, L.slabs.p, S.rb, &c->rb_count, &S.X);
+	TRY(tier_mark(B, S, "tier 2 (exports)"));
+	launch_regions_slab(st, 3, B.huge_grid, G, S.rb, &c->rb_count, &c->t3_cursor, L.slabs3.p, nullptr, nullptr, &S.X);
+	TRY(tier_mark(B, S, "tier 3 (exports)"));
+	if (B.any_flt)   // (the side stream's run comes after the main one's on the device -- it waits for the tiers -- and may use the same job list)
+		launch_seedsw(st, (int)std::min<int64_t>(nT, (int64_t)d->n_cu * 32), d->n_cu, G, S.X, &c->ssw_prep_cursor, &c->ssw_jobs, L.sswjobs.p, (unsigned int)B.ssw_cap);
+	TRY(tier_mark(B, S, "seed filter"));
+#ifdef BSX_DEBUG_XCHECK
+	if (S.main_seq) TRY(xcheck_exports(B, S));
+#endif
+	// (what outgrows the launch's tables -- 64 regions of a strand search, 256 seeds of a list -- gets a second one with up to 1024 of each, the
+	// regions in HBM; round 6: those were forty strand searches per chunk of kilobase reads chained on the host, a second of its time each chunk)
+	launch_c2r(st, (int)((nT + 4LL * B.c2r_quota - 1) / (4LL * B.c2r_quota)), G, S.X, &c->c2r_cursor, S.rh, &h->rh_count, B.c2r_quota, B.long_reads ? RG_C2R_L : RG_C2R);
+	RgXPoolArg XB3 = S.X;
+	XB3.xlist = S.rh; XB3.xcount = &h->rh_count;
+	launch_c2r(st, d->n_cu * 2, G, XB3, &h->c2r3_cursor, nullptr, nullptr, 1 << 30, RG_C2R_HL, L.c2rslab.p);
+	TRY(tier_mark(B, S, "chains -> regions"));
+	return BSX_OK;
+}
+
+// the rest of an ordinary chunk's sequence: chains -> regions of everything the LDS tiers exported; what outgrows its tables joins the list of
+// the HBM tiers.
+// (The first HBM tier exporting its chains as well -- 156 instead of 225 VGPRs, its chains through k_c2r with everybody else's -- was
+// measured in rounds 3 and 4 and removed: what k_c2r cannot hold, 64 regions and 128 seeds a chain, takes the full form afterwards anyway,
+// 1468 against 1287 ms per chunk on the hg38-like genome.  Round 6 takes it up again with a chains -> regions launch that CAN hold them.)
+static int run_tiers_ordinary(RgBatch &B, TierSeq &S, int *to2, unsigned int *n2c, bool tier1c)
+{
+	Lane &L = B.L; bsx_device_t *d = B.d; const hipStream_t st = S.st; const RgLaunch &G = S.G;
+	TierCtr::Front *c = &S.c->front; TierCtr::Late *h = &S.c->late;
+	const int c2r_grid = (int)((G.n_tasks + 4LL * B.c2r_quota - 1) / (4LL * B.c2r_quota));
+	const int t2x = tier1c && S.X.ext ? B.tier2_export : 0;
+	if (S.X.ext) {
+		launch_x4(st, d->n_cu, G, S.X, L.x4jobs.p, B.x4_cap, S.c->x4, B.R.prof ? G.counters + CTR_EXT : nullptr);
+		TRY(tier_mark(B, S, "extensions"));
+	}
+	if (tier1c) { // ... and what the chains -> regions launch declines (more than 64 regions, lists of more than 128 seeds) gets a second one with larger tables
+		launch_c2r(st, c2r_grid, G, S.X, &c->c2r_cursor, S.rc, &c->rc_count, B.c2r_quota);
+		RgXPoolArg XB2 = S.X;
+		XB2.xlist = S.rc; XB2.xcount = &c->rc_count;
+		if (t2x) { // ... and what THAT declines (up to 1024 regions, 1024 seeds a list) a third, the regions it makes in HBM: the record and its extensions are there
+			launch_c2r(st, d->n_cu * 2, G, XB2, &c->c2r2_cursor, S.rh, &h->rh_count, 1 << 30, RG_C2R_B);
+			RgXPoolArg XB3 = S.X;
+			XB3.xlist = S.rh; XB3.xcount = &h->rh_count;
+			launch_c2r(st, B.c2rh_grid, G, XB3, &h->c2r3_cursor, S.rf, &h->rf_count, 1 << 30, RG_C2R_H, L.c2rslab.p);
+		} else
+			launch_c2r(st, d->n_cu * 2, G, XB2, &c->c2r2_cursor, to2, n2c, 1 << 30, RG_C2R_B);   // (few strand searches, long ones: persistent waves)
+	} else
+		launch_c2r(st, c2r_grid, G, S.X, &c->c2r_cursor, to2, n2c, B.c2r_quota);
+	if (S.main_seq && B.chain == 3) { // the HBM tiers (a few long strand searches on a few waves) do not hold the next chunk's region launches back
+		std::lock_guard<std::mutex> g(d->chain_mu);
+		HIPCHK(hipEventRecord(L.ev_regions_done, st));
+		d->chain_regions = L.ev_regions_done;
+	}
+	TRY(tier_mark(B, S, "chains -> regions"));
+	if (t2x) {
+		// The first HBM tier in steps (round 6, "tier2_export=1"; measured and not the default).  What outgrew the LDS tiers'
+		// tables is chained and filtered over the tier's slabs and EXPORTED like the LDS tiers' strand searches; its chains' best seeds are extended
+		// ahead, several jobs to a wavefront (k_extl / k_ext4) -- inline, a wavefront each, the extensions are 58 % of the tier's cycles --; the seed
+		// loop is run by the chains -> regions launch that keeps up to 1024 regions in HBM.  Only what even that cannot hold takes the tier's
+		// monolithic form; what outgrows the tier's tables goes on to the last tier as before.
+		RgXPoolArg XT = S.X;
+		XT.xlist = S.x2; XT.xcount = &h->x2_count;
+		if (t2x >= 2) XT.ext = 2;   // every seed of every main list extended ahead (a slot per seed): the seed loops of these strand searches skip one seed in fourteen
+		launch_regions_slab(st, 2, B.big_grid, G, to2, n2c, &h->t2_export_cursor, L.slabs.p, S.rb, &c->rb_count, &XT);
+		TRY(tier_mark(B, S, "tier 2 (chains)"));
+		launch_x4(st, d->n_cu, G, XT, L.x4jobs.p, B.x4_cap, S.c->x4_t2, nullptr);
+		TRY(tier_mark(B, S, "tier 2 (extensions)"));
+		launch_c2r(st, B.c2rh_grid, G, XT, &h->c2r_t2_cursor, S.rf, &h->rf_count, 1 << 30, RG_C2R_H, L.c2rslab.p);
+		TRY(tier_mark(B, S, "tier 2 (chains -> regions)"));
+		launch_regions_slab(st, 2, B.big_grid, G, S.rf, &h->rf_count, &h->t2_full_cursor, L.slabs.p, S.rb, &c->rb_count);
+	} else
+		launch_regions_slab(st, 2, B.big_grid, G, to2, n2c, &c->t2_cursor, L.slabs.p, S.rb, &c->rb_count);
+	TRY(tier_mark(B, S, "tier 2"));
+	if (S.main_seq && B.early3) HIPCHK(hipStreamWaitEvent(st, L.ev_t3b, 0));   // (the early launch: it shares the tier's slabs, and everything behind this point waits for its regions)
+	if (B.order3) launch_order_list(st, S.rb, &c->rb_count, G.seeds_dense, G.task_off, G.task_n, B.opt->max_occ);
+	launch_regions_slab(st, 3, B.huge_grid, G, S.rb, &c->rb_count, &c->t3_cursor, L.slabs3.p, nullptr, nullptr);
+	TRY(tier_mark(B, S, "tier 3"));
+	return BSX_OK;
+}
+
+// stage 6 (the sequence's stream): the tier sequence over a task list -- the chunk's, and once more the re-seeded strand searches' on the side stream
+static int run_tiers(RgBatch &B, TierSeq &S)
+{
+	Lane &L = B.L; const hipStream_t st = S.st; const RgLaunch &G = S.G; TierCtr::Front *c = &S.c->front;
+	const int64_t nT = G.n_tasks;
+	const int mid_grid = (int)((nT + 2LL * B.mid_quota - 1) / (2LL * B.mid_quota));
+	TRY(tier_mark(B, S, "start"));
+	launch_regions(st, (int)((nT + 4LL * B.reg_quota - 1) / (4LL * B.reg_quota)), G, &c->t1_cursor, S.ra, &c->ra_count, B.reg_quota, S.cls, S.X, B.long_reads);
+	if (S.main_seq) HIPCHK(hipEventRecord(L.ev_tier1_end, st));
+	TRY(tier_mark(B, S, "tier 1"));
+	if (B.use_mid) launch_regions_mid(st, mid_grid, G, S.ra, &c->ra_count, &c->t1b_cursor, S.rm, &c->rm_count, S.X, B.mid_quota, B.long_reads ? RG_MID_LONGS : RG_MID);
+	TRY(tier_mark(B, S, "tier 1b"));
+	int *to2 = B.use_mid ? S.rm : S.ra; unsigned int *n2c = B.use_mid ? &c->rm_count : &c->ra_count;
+	// a third LDS tier.  Kilobase reads: larger tables (two workgroups per CU) for what outgrows the first (three).  Ordinary reads inside
+	// repeat families: twice the tables of the tier before it (round 5)
+	const bool tier1c = B.use_mid && !B.long_reads && !B.export_all && B.use_1c;
+	if ((B.use_mid && B.long_reads) || tier1c) {
+		launch_regions_mid(st, mid_grid, G, S.rm, &c->rm_count, &c->t1c_cursor, S.rl, &c->rl_count, S.X, B.mid_quota, B.long_reads ? RG_MID_LONGB_L : RG_MID2);
+		to2 = S.rl; n2c = &c->rl_count;
+		TRY(tier_mark(B, S, "tier 1c"));
+	}
+	return B.export_all ? run_tiers_exporting(B, S, to2, n2c) : run_tiers_ordinary(B, S, to2, n2c, tier1c);
+}
+
+// stage 7 (host, then the side stream): strand searches whose interval list overflowed (reads inside tandem repeats: ~300 k dependent FM
+// steps on one lane) are seeded again on the side stream with much longer lists and no trip budget, then go through the same tiers as
+// everything else.  None of that is waited for here: everything is enqueued, and lane_regions_finish collects the result when the caller
+// gets to the chunk's back half.
+// (on a genome with hg38's repeat content these are 4 % of the strand searches -- reads inside young copies of a repeat family -- not
+// the few dozen tandem-repeat reads of a clean one)
+static int rg_side_sequence(RgBatch &B)
+{
+	Lane &L = B.L; bsx_device_t *d = B.d; const int64_t n = B.n; TierSeq &M = B.main; std::vector<int64_t> &redo = B.redo;
+	CtrShared *SH = ctr_shared(L);
+	clock_gettime(CLOCK_MONOTONIC, &B.ts0);
+	{
+		std::vector<int> s_n;
+		if (!B.first_n.empty()) s_n.swap(B.first_n);
+		else { s_n.resize((size_t)n); HIPCHK(hipEventSynchronize(L.ev_timed_end)); D2H(L.st2, s_n.data(), M.cnts, (size_t)n * 4); }
+		for (int64_t i = 0; i < n; ++i) if (s_n[i] < 0) redo.push_back(i); else L.work[1] += (uint64_t)s_n[i];
+		L.last_overflow = (long)redo.size();
+		if (B.merged) { // they are in the main sequence, but for those that the second pass gave up on as well (its budget, its list)
+			std::vector<int> c2(B.merged_which.size());
+			HIPCHK(hipEventSynchronize(L.ev_seed2_end));
+			D2H(L.st2, c2.data(), B.merged_cnt, c2.size() * 4);
+			redo.clear();
+			for (size_t j = 0; j < c2.size(); ++j) if (c2[j] < 0) redo.push_back(B.merged_which[j]); else L.work[1] += (uint64_t)c2[j];
+		}
+		if (redo.size() > 262144) redo.clear();   // (seed_again_size: n_slabs bounds the pass) leave them to the caller
+	}
+	clock_gettime(CLOCK_MONOTONIC, &B.ts1);
+	L.rs.active = false;
+	const size_t n2 = redo.size();
+	const SeedAgain sa = seed_again_size(n2, B.mem_cap, B.list_cap, B.n_slabs);
+	if (n2 && !sa.fits) redo.clear();
+	if (!redo.empty()) {
+		TRY(L.scratch2.reserve(sa.scratch));
+		L.rs.tasks = redo; L.rs.sub.resize(n2); L.rs.n2u = (unsigned int)n2;
+		for (size_t j = 0; j < n2; ++j) L.rs.sub[j] = B.tasks[redo[j]];
+		// device side, per re-seeded strand search: task | interval offset | region offset | position offset | export offset | interval
+		// count | region count | eight tier lists | export list | tier class (seq_carve)
+		TRY(L.redo.reserve(n2 * (sizeof(bsx_seed_task_t) + 8 + 8 + 8 + 8 + 4 + 4 + 16 + 4 + 4 + 12 + 1) + 1024));
+		TRY(L.rs.hres.reserve(n2 * 12 + 64));
+		TierSeq &S = B.side;
+		S = M;   // the same index, reads, pools and shared cursors
+		S.st = L.st2; S.main_seq = false; S.c = ctr_tiers(L, false);
+		Bump b(L.redo);
+		bsx_seed_task_t *t2 = b.take<bsx_seed_task_t>(n2);
+		seq_carve(S, n2, b, b, b, b);
+		if (!b.ok()) return BSX_E_INTERNAL;
+		S.G.tasks = t2; S.X.xcount = &S.c->front.x_count;
+		HIPCHK(hipMemcpyAsync(t2, L.rs.sub.data(), n2 * sizeof(bsx_seed_task_t), hipMemcpyHostToDevice, L.st2));
+		HIPCHK(hipMemsetAsync(&S.c->front, 0, sizeof(S.c->front), L.st2));
+		HIPCHK(hipMemsetAsync(&S.c->late, 0, sizeof(S.c->late), L.st2));
+		launch_seed(L.st2, sa.grid, d->ix, S.G.reads, t2, (int)n2, B.P, (DevIntv*)L.scratch2.p, B.list_cap, (int)sa.cap, (DevIntv*)L.out.p, B.dense_cap, &SH->seed.intv_cursor,
+		            S.offs, S.cnts, &S.c->front.seed_task_cursor, S.G.counters + CTR_SEED3, 0, (unsigned int*)L.slabflags.p, sa.grid * 4, 0, 0, (uint32_t*)L.qpack.p);   // (the main launch is over: its packed reads are no longer needed)
+		HIPCHK(hipStreamWaitEvent(L.st2, L.rs.ev_tiers, 0));   // the slabs of the HBM tiers and the export pool's lists are shared with the main launch sequence
+		launch_occ(L.st2, d->n_cu, S.G, B.opt->max_occ, B.pos_cap, &SH->k3_cursor, S.cls, &S.c->front.k3_start);
+		TRY(run_tiers(B, S));
+		HIPCHK(hipMemcpyAsync(L.rs.hres.p, S.G.reg_off, n2 * 8, hipMemcpyDeviceToHost, L.st2));
+		HIPCHK(hipMemcpyAsync((char*)L.rs.hres.p + n2 * 8, S.G.reg_n, n2 * 4, hipMemcpyDeviceToHost, L.st2));
+		HIPCHK(hipEventRecord(L.rs.ev, L.st2));
+		L.rs.active = true;
+	}
+	clock_gettime(CLOCK_MONOTONIC, &B.ts2);
+	return BSX_OK;
+}
+
+// stage 8 (host): wait for the main sequence, and put its launches' times into the lane's slots
+static int rg_wait_and_time(RgBatch &B)
+{
+	Lane &L = B.L; unsigned long long *ctr = dev_counters(L);
+	float ms0 = 0, ms1 = 0, ms2 = 0, ms3 = 0, ms_again = 0;
+	HIPCHK(hipEventRecord(L.ev_tiers_end, L.st));
+	HIPCHK(hipEventSynchronize(L.ev_tiers_end));
+	clock_gettime(CLOCK_MONOTONIC, &B.ts3);
+	if (B.trace_tiers && B.n_marks > 1) {
+		fprintf(stderr, "[M::regions_batch] region launches (ms):");
+		for (int k = 1; k < B.n_marks; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, L.tier_ev[k - 1], L.tier_ev[k]) == hipSuccess) fprintf(stderr, " %s %.1f |", B.mark_name[k], ms); }
+		if (B.early3) { float ms = 0; unsigned int ne = 0; D2H(L.st, &ne, &ctr_shared(L)->early3.count, 4); if (hipEventElapsedTime(&ms, L.ev_t3a, L.ev_t3b) == hipSuccess) fprintf(stderr, " tier 3 beside them (%u strand searches) %.1f |", ne, ms); }
+		fprintf(stderr, "\n");
+	}
+	if (B.trace) fprintf(stderr, "[M::regions_batch] seed kernel done +%.0f ms | redo of %zu strand searches enqueued +%.0f ms | all region tiers done +%.0f ms\n",
+	                     ms_between(B.ts0, B.ts1), B.redo.size(), ms_between(B.ts0, B.ts2), ms_between(B.ts0, B.ts3));
+	HIPCHK(hipEventElapsedTime(&ms0, L.ev_timed_begin, L.ev_timed_end));
+	HIPCHK(hipEventElapsedTime(&ms_again, L.ev_seed2_begin, L.ev_seed2_end));   // the second seeding pass, when it ran inside this sequence
+	if (B.merged && B.trace) { // requests per strand search of the second pass, by power of two (k_seedt, prof & 2)
+		unsigned long long hh[CTR_SEED_HIST_N];
+		HIPCHK(hipMemcpy(hh, ctr + CTR_SEED2 + CTR_SEED_HIST, sizeof(hh), hipMemcpyDeviceToHost)); HIPCHK(hipMemset(ctr + CTR_SEED2 + CTR_SEED_HIST, 0, sizeof(hh)));
+		fprintf(stderr, "[M::regions_batch] second seeding pass %.1f ms (budget %d requests); strand searches by requests made, < 2^k:", ms_again, B.trip_budget * B.budget2_mul);
+		for (int k = 0; k < CTR_SEED_HIST_N; ++k) if (hh[k]) fprintf(stderr, " k=%d: %llu |", k, hh[k]);
+		fprintf(stderr, "\n");
+	}
+	if (B.merged) { L.k_ms[KT_SEED_OTHER] += ms_again; L.k_launch[KT_SEED_OTHER] += 1; L.seed2_ms += ms_again; L.seed2_launches += 1; L.seed2_tasks += (uint64_t)B.merged_which.size(); }
+	HIPCHK(hipEventElapsedTime(&ms3, L.ev_seed2_end, L.ev_occ_end));   // K3 for the chunk (k_occ_expand + k_occ)
+	L.k_ms[KT_K3] += ms3; L.k_launch[KT_K3] += 1;
+	HIPCHK(hipEventElapsedTime(&ms1, L.ev_occ_end, L.ev_tier1_end));   // the first region tier alone
+	HIPCHK(hipEventElapsedTime(&ms2, L.ev_tier1_end, L.ev_tiers_end));   // the later tiers and the wait for the early launch of the last one
+	L.k_ms[KT_SEED] += ms0; L.k_launch[KT_SEED] += 1; L.k_ms[KT_TIER1] += ms1; L.k_launch[KT_TIER1] += 1; L.k_ms[KT_TIERS_LATER] += ms2; L.k_launch[KT_TIERS_LATER] += 1;
+	HIPCHK(hipGetLastError());
+	return BSX_OK;
+}
+
+// stage 9 (host): offsets, counts and regions of the main sequence down
+static int rg_download(RgBatch &B, bsx_region_t **out, int64_t *out_cap, int64_t *out_off, int32_t *out_n)
+{
+	Lane &L = B.L; const int64_t n = B.n; TierSeq &M = B.main; CtrShared *SH = ctr_shared(L);
+	unsigned long long used = 0;
+	std::vector<long long> h_off((size_t)n);
+	D2H(L.st, h_off.data(), M.G.reg_off, (size_t)n * 8);
+	D2H(L.st, out_n, M.G.reg_n, (size_t)n * 4);
+	D2H(L.st, &used, &SH->region_cursor, 8);
+	if (used > B.regs_cap) used = B.regs_cap;
+	{ // work of the chunk (bsx_device_region_work)
+		unsigned long long n_occ = 0;
+		D2H(L.st, &n_occ, &SH->k3_cursor, 8);
+		L.work[0] += (uint64_t)n; L.work[2] += n_occ < B.pos_cap ? n_occ : B.pos_cap; L.work[3] += used;
+		for (int64_t i = 0; i < n; ++i) L.work[4] += (uint64_t)(B.tasks[i].len > 0 ? B.tasks[i].len : 0);
+	}
+	for (int64_t i = 0; i < n; ++i) out_off[i] = h_off[i];
+	L.rs.used_main = used; L.rs.regs_cap = B.regs_cap;
+	for (size_t j = 0; j < B.redo.size(); ++j) out_n[B.redo[j]] = BSX_REGIONS_PENDING;   // lane_regions_finish fills these in
+	if (*out_cap < (int64_t)used + 65536) { *out_cap = (int64_t)used + 65536; *out = (bsx_region_t*)realloc(*out, sizeof(bsx_region_t) * (size_t)*out_cap); }
+	D2H(L.st, *out, L.regs.p, (size_t)used * sizeof(bsx_region_t));
+	B.used = used;
+	return BSX_OK;
+}
+
+// stage 10 (host, $BSX_PHASES): what the chunk's counters say, read and zeroed
+static int rg_report(RgBatch &B)
+{
+	Lane &L = B.L; unsigned long long *ctr = dev_counters(L);
+	CtrShared sh; TierCtr tc;
+	D2H(L.st, &tc, B.main.c, sizeof(tc));
+	D2H(L.st, &sh, ctr_shared(L), sizeof(sh));
+	const TierCtr::Front &f = tc.front;
+	fprintf(stderr, "[M::regions_batch] %lld strand searches: %llu intervals, %llu occurrences looked up ahead | left tier 1: %u, left tier 1b: %u, reached tier 2: %u, left tier 2: %u | second chains -> regions launch: %u | every tier exports: %d\n",
+	        (long long)B.n, sh.seed.intv_cursor, sh.k3_cursor, f.ra_count, f.rm_count, B.long_reads || B.export_all ? f.rl_count : f.rl_count ? f.rl_count : f.rm_count, f.rb_count, f.rc_count, B.export_all ? 1 : 0);
+	unsigned long long sp[CTR_SEED_N];
+	D2H(L.st, sp, ctr + CTR_SEED_CYC, sizeof(sp));
+	HIPCHK(hipMemsetAsync(ctr + CTR_SEED_CYC, 0, sizeof(sp), L.st));
+	if (sp[0]) fprintf(stderr, "[M::regions_batch] k_seed: %.0f M wave cycles, %.1f%% in the full machine (%llu passes, %.0f cycles each), publishing %.1f%% | %llu wave trips, %.0f cycles per trip\n",
+	                   sp[0] * 1e-6, 100.0 * sp[1] / sp[0], sp[4], sp[4] ? (double)sp[1] / sp[4] : 0.0, 100.0 * sp[2] / sp[0], sp[3], sp[3] ? (double)sp[0] / sp[3] : 0.0);
+	unsigned long long tq[CTR_SEEDT_N];
+	D2H(L.st, tq, ctr + CTR_SEEDT_HOT, sizeof(tq));
+	HIPCHK(hipMemsetAsync(ctr + CTR_SEEDT_HOT, 0, sizeof(tq), L.st));
+	if (sp[0] && tq[3]) fprintf(stderr, "[M::regions_batch] k_seedt: short machine %.1f%%, fetch %.1f%%, post %.1f%% of the wave cycles | %.1f requests per wave trip\n",
+	                            100.0 * tq[0] / sp[0], 100.0 * tq[1] / sp[0], 100.0 * tq[2] / sp[0], sp[3] ? (double)tq[3] / sp[3] : 0.0);
+	unsigned long long xp[CTR_EXT_N];
+	D2H(L.st, xp, ctr + CTR_EXT, sizeof(xp));
+	HIPCHK(hipMemsetAsync(ctr + CTR_EXT, 0, sizeof(xp), L.st));
+	if (xp[EXT4_JOBS] || xp[EXTL_JOBS]) fprintf(stderr, "[M::regions_batch] k_ext4: %llu jobs, %llu rows in %llu wave trips (%.2f rows per trip), %llu passes between extensions, %.2f slots per trip, %llu rows of narrow jobs\n", xp[0], xp[1], xp[2], xp[2] ? (double)xp[1] / xp[2] : 0.0, xp[3], xp[2] ? (double)xp[4] / xp[2] : 0.0, xp[5]);
+	if (xp[EXTL_JOBS]) fprintf(stderr, "[M::regions_batch] k_extl: %llu jobs (%llu sent on to k_ext4), %llu rows in %llu wave trips (%.1f rows per trip), %llu passes between extensions\n", xp[6], xp[10], xp[7], xp[8], xp[8] ? (double)xp[7] / xp[8] : 0.0, xp[9]);
+	unsigned long long pf[CTR_STAGE_N];
+	D2H(L.st, pf, ctr + CTR_STAGE, sizeof(pf));
+	HIPCHK(hipMemsetAsync(ctr + CTR_STAGE, 0, sizeof(pf), L.st));
+	double tot = 0; for (int k = 0; k < 8; ++k) tot += (double)pf[k];
+	if (tot > 0) fprintf(stderr, "[M::regions_batch] wave cycles by stage (all tiers): intervals %.1f%% occurrences %.1f%% chaining %.1f%% weights+order %.1f%% sort %.1f%% filter %.1f%% chain prologues+seed tests %.1f%% extension %.1f%% | %.0f M cycles, %llu extensions, %llu rows\n",
+	        100 * pf[0] / tot, 100 * pf[1] / tot, 100 * pf[2] / tot, 100 * pf[3] / tot, 100 * pf[4] / tot, 100 * pf[5] / tot, 100 * pf[6] / tot, 100 * pf[7] / tot, tot * 1e-6, pf[8], pf[9]);
+	if (pf[10]) fprintf(stderr, "[M::regions_batch] seed filter: %llu alignments\n", pf[10]);
+	if (pf[11]) fprintf(stderr, "[M::regions_batch] seed loops (mem_chain2region1): %llu seeds reached, %llu skipped as contained, %llu took the extension made ahead, %llu extended in place\n", pf[11], pf[12], pf[13], pf[14]);
+	// the HBM tiers: how long their strand searches take (a wave each)
+	unsigned long long tk[2 * CTR_TIER_TIME_N];
+	D2H(L.st, tk, ctr + CTR_TIER2_TIME, sizeof(tk));
+	HIPCHK(hipMemsetAsync(ctr + CTR_TIER2_TIME, 0, sizeof(tk), L.st));
+	for (int k = 0; k < 2; ++k) if (tk[4 * k + 2])
+		fprintf(stderr, "[M::regions_batch] tier %d: %llu strand searches, %.2f M cycles each on average, the longest %.1f M, the busiest wave %.1f M, all of them %.0f M\n",
+		        2 + k, tk[4 * k + 2], 1e-6 * tk[4 * k + 1] / tk[4 * k + 2], 1e-6 * tk[4 * k], 1e-6 * tk[4 * k + 3], 1e-6 * tk[4 * k + 1]);
+	unsigned long long th[CTR_T3_N];
+	D2H(L.st, th, ctr + CTR_T3_LONGEST, sizeof(th));
+	HIPCHK(hipMemsetAsync(ctr + CTR_T3_LONGEST, 0, sizeof(th), L.st));
+	if (th[0]) {
+		fprintf(stderr, "[M::regions_batch] tier 3: the longest strand search: %.1f M cycles, %llu intervals, %llu chains kept, %llu regions | strand searches by duration, < 2^k x 65536 cycles:",
+		        (double)(th[0] >> 36) * 4096e-6, (th[0] >> 24) & 4095, (th[0] >> 14) & 16383, th[0] & 16383);
+		for (int k = 0; k < CTR_T3_HIST_N; ++k) if (th[2 + k]) fprintf(stderr, " k=%d: %llu |", k, th[2 + k]);
+		fprintf(stderr, "\n");
+	}
+	return BSX_OK;
+}
+
+// stage 11 (host): declined tasks: hand their interval lists back (ordered by info, as bsx_seed_batch returns them)
+static int rg_declined(RgBatch &B, const int32_t *out_n, bsx_intv_t **decl_intv, int64_t *decl_cap, int64_t *decl_off)
+{
+	Lane &L = B.L; const int64_t n = B.n; TierSeq &M = B.main;
+	std::vector<int64_t> decl;
+	for (int64_t i = 0; i < n; ++i) if (out_n[i] < -1 && out_n[i] != BSX_REGIONS_PENDING) decl.push_back(i);
+	decl_off[0] = 0;
+	if (decl.empty()) return BSX_OK;
+	std::vector<long long> s_off((size_t)n); std::vector<int> s_n((size_t)n);
+	D2H(L.st, s_off.data(), M.offs, (size_t)n * 8);
+	D2H(L.st, s_n.data(), M.cnts, (size_t)n * 4);
+	int64_t tot = 0;
+	for (size_t j = 0; j < decl.size(); ++j) { decl_off[j] = tot; tot += s_n[decl[j]]; }
+	decl_off[decl.size()] = tot;
+	if (*decl_cap < tot) { *decl_cap = tot + (tot >> 2) + 16; *decl_intv = (bsx_intv_t*)realloc(*decl_intv, sizeof(bsx_intv_t) * (size_t)*decl_cap); }
+	const bsx_intv_t *dense = nullptr;
+	if (decl.size() > 256 && tot > 0) { // many: their lists gathered on the device (they lie a strand search's stretch apart), one copy
+		std::vector<long long> which(decl.begin(), decl.end()), doff(decl_off, decl_off + decl.size());
+		for (size_t j = 0; j < decl.size(); ++j) if (s_n[decl[j]] < 0) { which.clear(); break; }   // (a list that did not fit has no entries to fetch: leave the one-by-one path to skip it)
+		if (!which.empty()) {
+			const size_t nb = decl.size() * 8;
+			TRY(L.gath.reserve(2 * nb + (size_t)tot * sizeof(bsx_intv_t) + 64));
+			H2D(L.st, L.gath.p, which.data(), nb);
+			H2D(L.st, (char*)L.gath.p + nb, doff.data(), nb);
+			DevIntv *gd = (DevIntv*)((char*)L.gath.p + 2 * nb);
+			launch_gather_lists(L.st, (const DevIntv*)L.out.p, M.offs, M.cnts, (const long long*)L.gath.p, (const long long*)((char*)L.gath.p + nb), (long long)decl.size(), gd);
+			TRY(L.hstage.reserve((size_t)tot * sizeof(bsx_intv_t) + 64));
+			D2H(L.st, L.hstage.p, gd, (size_t)tot * sizeof(bsx_intv_t));
+			dense = (const bsx_intv_t*)L.hstage.p;
+		}
+	}
+	for (size_t j = 0; j < decl.size(); ++j) {
+		const int64_t i = decl[j]; const int cnt = s_n[i];
+		bsx_intv_t *dst = *decl_intv + decl_off[j];
+		if (cnt <= 0) continue;
+		if (dense) memcpy(dst, dense + decl_off[j], sizeof(bsx_intv_t) * (size_t)cnt);
+		else D2H(L.st, dst, (const bsx_intv_t*)L.out.p + s_off[i], sizeof(bsx_intv_t) * (size_t)cnt);
+		if (cnt > 1) std::sort(dst, dst + cnt, intv_info_lt);
+	}
+	return BSX_OK;
+}
+
+// The chunk's front half behind the seeding: the stages above in order.  The host waits at four points: for the seeding pass when the second
+// may have to be merged in (rg_seed_merged) and for its counts (rg_side_sequence), for the main sequence (rg_wait_and_time), and -- in
+// lane_regions_finish -- for the side stream.
+static int lane_regions_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int64_t n, const bsx_seed_task_t *tasks,
+                              bsx_region_t **out, int64_t *out_cap, int64_t *out_off, int32_t *out_n,
+                              bsx_intv_t **decl_intv, int64_t *decl_cap, int64_t *decl_off)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (n == 0) return BSX_OK;
+	if (n > 0x7fffffff) return BSX_E_ARG;
+	HIPCHK(hipSetDevice(d->ordinal));
+	RgBatch B = {d, d->lane[lane], lane, opt, n, tasks};
+	Lane &L = B.L;
+	clock_gettime(CLOCK_MONOTONIC, &B.ts_in);
+	TRY(rg_params(B));
+	TRY(rg_plan(B));
+	TRY(rg_seed_first(B));
+	TRY(rg_seed_merged(B));
+	TRY(rg_occ_and_early_tier3(B));
+	TRY(run_tiers(B, B.main));
+	if (B.chain == 2 || B.chain >= 4) {
 		std::lock_guard<std::mutex> g(d->chain_mu);
 		HIPCHK(hipEventRecord(L.ev_regions_done, L.st));
 		d->chain_regions = L.ev_regions_done;
 	}
 	HIPCHK(hipEventRecord(L.rs.ev_tiers, L.st));
-	// While those run: strand searches whose interval list overflowed (reads inside tandem repeats: ~300 k dependent FM steps
-	// on one lane) are seeded again on the side stream with much longer lists and go through the third tier as well.  None of
-	// that is waited for here: everything is enqueued, and lane_regions_finish collects the result when the caller gets to the
-	// chunk's back half.
-	const bool trace = bsx_phases() != 0;
-	struct timespec ts0, ts1, ts2, ts3;
-	clock_gettime(CLOCK_MONOTONIC, &ts0);
-	std::vector<int64_t> redo;            // task indices
-	{
-		std::vector<int> s_n;
-		if (!first_n.empty()) s_n.swap(first_n);
-		else { s_n.resize((size_t)n); HIPCHK(hipEventSynchronize(L.ev1)); D2H(L.st2, s_n.data(), d_n, (size_t)n * 4); }
-		for (int64_t i = 0; i < n; ++i) if (s_n[i] < 0) redo.push_back(i); else L.work[1] += (uint64_t)s_n[i];
-		L.last_overflow = (long)redo.size();
-		if (merged) { // they are in the main sequence, but for those that the second pass gave up on as well (its budget, its list)
-			std::vector<int> c2(merged_which.size());
-			HIPCHK(hipEventSynchronize(L.ev6));
-			D2H(L.st2, c2.data(), merged_cnt, c2.size() * 4);
-			redo.clear();
-			for (size_t j = 0; j < c2.size(); ++j) if (c2[j] < 0) redo.push_back(merged_which[j]); else L.work[1] += (uint64_t)c2[j];
-		}
-		if (redo.size() > 262144) redo.clear();   // (one slab per four waves of the second pass: n_slabs bounds it) leave them to the caller
-	}
-	clock_gettime(CLOCK_MONOTONIC, &ts1);
-	L.rs.active = false;
-	if (!redo.empty()) {
-		// Seeded again on the side stream with lists eight times as long and no trip budget, then through the same tiers as everything else
-		// (on a genome with hg38's repeat content these are 4 % of the strand searches -- reads inside young copies of a repeat family -- not
-		// the few dozen tandem-repeat reads of a clean one)
-		const size_t n2 = redo.size();
-		const int g2 = (int)((n2 + 255) / 256);
-		const long long cap2 = std::max<long long>((long long)mem_cap * 8, 1024);
-		const size_t scratch2 = (size_t)g2 * 256 * ((size_t)cap2 * 32 + (size_t)list_cap * 16);
-		if (g2 * 4 <= n_slabs && scratch2 <= ((size_t)24 << 30)) {
-			if ((rc = L.scratch2.reserve(scratch2)) != BSX_OK) return rc;
-			L.rs.tasks = redo; L.rs.sub.resize(n2); L.rs.n2u = (unsigned int)n2;
-			for (size_t j = 0; j < n2; ++j) L.rs.sub[j] = tasks[redo[j]];
-			// device side, per re-seeded strand search: task | interval offset | region offset | position offset | export offset | interval
-			// count | region count | three tier lists | export list | tier class
-			if ((rc = L.redo.reserve(n2 * (sizeof(bsx_seed_task_t) + 8 + 8 + 8 + 8 + 4 + 4 + 16 + 4 + 4 + 12 + 1) + 1024)) != BSX_OK) return rc;
-			if ((rc = L.rs.hres.reserve(n2 * 12 + 64)) != BSX_OK) return rc;
-			bsx_seed_task_t *t2 = (bsx_seed_task_t*)L.redo.p;
-			long long *off2 = (long long*)(t2 + n2); long long *roff2 = off2 + n2; long long *posoff2 = roff2 + n2; long long *xoff2 = posoff2 + n2;
-			int *cnt2 = (int*)(xoff2 + n2); int *rn2 = cnt2 + n2; int *ra2 = rn2 + n2, *rm2 = ra2 + n2, *rb2 = rm2 + n2, *rl2 = rb2 + n2, *xlist2 = rl2 + n2, *rc2l = xlist2 + n2;
-			int *rh2 = rc2l + n2, *x22 = rh2 + n2, *rf2 = x22 + n2;
-			unsigned char *cls2 = (unsigned char*)(rf2 + n2);
-			// its own cursors (u64 slots 96.. of the lane's counter block): u32 [0] tier-1 task cursor [1] tier-2 count [2] tier-2 cursor [3] tier-3
-			// count [4] tier-3 cursor [7] seed task cursor [10] count of what the larger LDS tier hands on [11] its cursor; slot 102: exported
-			// count | k_c2r cursor; slot 103: where its ranks start in the position pool
-			unsigned int *q32 = (unsigned int*)(ctr + 96);
-			HIPCHK(hipMemcpyAsync(t2, L.rs.sub.data(), n2 * sizeof(bsx_seed_task_t), hipMemcpyHostToDevice, L.st2));
-			HIPCHK(hipMemsetAsync(ctr + 96, 0, 80, L.st2));
-			HIPCHK(hipMemsetAsync(ctr + 80, 0, 80, L.st2));
-			launch_seed(L.st2, g2, d->ix, d_reads, t2, (int)n2, P, (DevIntv*)L.scratch2.p, list_cap, (int)cap2, (DevIntv*)L.out.p, dense_cap, ctr + 4,
-			            off2, cnt2, q32 + 7, ctr + SEED3_CTR, 0, (unsigned int*)L.slabflags.p, g2 * 4, 0, 0, (uint32_t*)L.qpack.p);   // (the main launch is over: its packed reads are no longer needed)
-			HIPCHK(hipStreamWaitEvent(L.st2, L.rs.ev_tiers, 0));   // the slabs of the HBM tiers and the export pool's lists are shared with the main launch sequence
-			RgXPoolArg XB = XA;
-			XB.xoff = xoff2; XB.xlist = xlist2; XB.xcount = (unsigned int*)(ctr + 102);
-			launch_occ(L.st2, d->n_cu, d->ix, t2, (int)n2, (const DevIntv*)L.out.p, off2, cnt2, opt->max_occ, d_pos, pos_cap, ctr + 11, posoff2, ctr, cls2, ctr + 103);
-			if ((rc = run_tiers(L.st2, t2, (int64_t)n2, off2, cnt2, roff2, rn2, ra2, rm2, rb2, q32, (unsigned int*)(ctr + 102), XB, posoff2, cls2, false, rl2, q32 + 6, q32 + 8, (unsigned int*)(ctr + 18), rc2l, (unsigned int*)(ctr + 104), (unsigned int*)(ctr + 105),
-				                    rh2, x22, rf2, (unsigned int*)(ctr + 80))) != BSX_OK) return rc;
-			HIPCHK(hipMemcpyAsync(L.rs.hres.p, roff2, n2 * 8, hipMemcpyDeviceToHost, L.st2));
-			HIPCHK(hipMemcpyAsync((char*)L.rs.hres.p + n2 * 8, rn2, n2 * 4, hipMemcpyDeviceToHost, L.st2));
-			HIPCHK(hipEventRecord(L.rs.ev, L.st2));
-			L.rs.active = true;
-		} else redo.clear();
-	}
-	clock_gettime(CLOCK_MONOTONIC, &ts2);
-	HIPCHK(hipEventRecord(L.ev2, L.st));
-	{
-		float ms0 = 0, ms1 = 0, ms2 = 0;
-		HIPCHK(hipEventSynchronize(L.ev2));
-		clock_gettime(CLOCK_MONOTONIC, &ts3);
-		if (trace_tiers && n_marks > 1) {
-			fprintf(stderr, "[M::regions_batch] region launches (ms):");
-			for (int k = 1; k < n_marks; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, L.tier_ev[k - 1], L.tier_ev[k]) == hipSuccess) fprintf(stderr, " %s %.1f |", mark_name[k], ms); }
-			if (early3) { float ms = 0; unsigned int ne = 0; D2H(L.st, &ne, ctr + 22, 4); if (hipEventElapsedTime(&ms, L.ev_t3a, L.ev_t3b) == hipSuccess) fprintf(stderr, " tier 3 beside them (%u strand searches) %.1f |", ne, ms); }
-			fprintf(stderr, "\n");
-		}
-		if (trace) fprintf(stderr, "[M::regions_batch] seed kernel done +%.0f ms | redo of %zu strand searches enqueued +%.0f ms | all region tiers done +%.0f ms\n",
-		                   (ts1.tv_sec - ts0.tv_sec) * 1e3 + (ts1.tv_nsec - ts0.tv_nsec) * 1e-6, redo.size(), (ts2.tv_sec - ts0.tv_sec) * 1e3 + (ts2.tv_nsec - ts0.tv_nsec) * 1e-6,
-		                   (ts3.tv_sec - ts0.tv_sec) * 1e3 + (ts3.tv_nsec - ts0.tv_nsec) * 1e-6);
-		HIPCHK(hipEventElapsedTime(&ms0, L.ev0, L.ev1));
-		float ms3 = 0, ms_again = 0;
-		HIPCHK(hipEventElapsedTime(&ms_again, L.ev5, L.ev6));   // the second seeding pass, when it ran inside this sequence
-		if (merged && trace) { // requests per strand search of the second pass, by power of two (k_seedt, prof & 2)
-			unsigned long long hh[20];
-			HIPCHK(hipMemcpy(hh, ctr + SEED2_CTR + 60, sizeof(hh), hipMemcpyDeviceToHost)); HIPCHK(hipMemset(ctr + SEED2_CTR + 60, 0, sizeof(hh)));
-			fprintf(stderr, "[M::regions_batch] second seeding pass %.1f ms (budget %d requests); strand searches by requests made, < 2^k:", ms_again, trip_budget * budget2_mul);
-			for (int k = 0; k < 20; ++k) if (hh[k]) fprintf(stderr, " k=%d: %llu |", k, hh[k]);
-			fprintf(stderr, "\n");
-		}
-		if (merged) { L.k_ms[7] += ms_again; L.k_launch[7] += 1; L.seed2_ms += ms_again; L.seed2_launches += 1; L.seed2_tasks += (uint64_t)merged_which.size(); }   // (slot 7: seeding outside the chunk-wide launch)
-		HIPCHK(hipEventElapsedTime(&ms3, L.ev6, L.ev4));   // K3 for the chunk (k_occ_expand + k_occ)
-		L.k_ms[1] += ms3; L.k_launch[1] += 1;
-		HIPCHK(hipEventElapsedTime(&ms1, L.ev4, L.ev3));   // the first region tier alone
-		HIPCHK(hipEventElapsedTime(&ms2, L.ev3, L.ev2));   // tiers 2 and 3 and the wait for re-seeded strand searches
-		L.k_ms[0] += ms0; L.k_launch[0] += 1; L.k_ms[5] += ms1; L.k_launch[5] += 1; L.k_ms[6] += ms2; L.k_launch[6] += 1;
-		HIPCHK(hipGetLastError());
-	}
-	unsigned long long used = 0;
-	std::vector<long long> h_off((size_t)n);
-	D2H(L.st, h_off.data(), r_off, (size_t)n * 8);
-	D2H(L.st, out_n, r_n, (size_t)n * 4);
-	D2H(L.st, &used, ctr + 6, 8);
-	if (used > regs_cap) used = regs_cap;
-	{ // work of the chunk (bsx_device_region_work)
-		unsigned long long n_occ = 0;
-		D2H(L.st, &n_occ, ctr + 11, 8);
-		L.work[0] += (uint64_t)n; L.work[2] += n_occ < pos_cap ? n_occ : pos_cap; L.work[3] += used;
-		for (int64_t i = 0; i < n; ++i) L.work[4] += (uint64_t)(tasks[i].len > 0 ? tasks[i].len : 0);
-	}
-	for (int64_t i = 0; i < n; ++i) out_off[i] = h_off[i];
-	L.rs.used_main = used; L.rs.regs_cap = regs_cap;
-	for (size_t j = 0; j < redo.size(); ++j) out_n[redo[j]] = BSX_REGIONS_PENDING;   // lane_regions_finish fills these in
-	if (*out_cap < (int64_t)used + 65536) { *out_cap = (int64_t)used + 65536; *out = (bsx_region_t*)realloc(*out, sizeof(bsx_region_t) * (size_t)*out_cap); }
-	D2H(L.st, *out, L.regs.p, (size_t)used * sizeof(bsx_region_t));
-
-	if (trace) {
-		unsigned int hc[12]; unsigned long long hu[12];
-		D2H(L.st, hc, c32, sizeof(hc));
-		D2H(L.st, hu, ctr, sizeof(hu));
-		unsigned long long hu20 = 0;
-		D2H(L.st, &hu20, ctr + 20, 8);
-		fprintf(stderr, "[M::regions_batch] %lld strand searches: %llu intervals, %llu occurrences looked up ahead | left tier 1: %u, left tier 1b: %u, reached tier 2: %u, left tier 2: %u | second chains -> regions launch: %u | every tier exports: %d\n",
-		        (long long)n, hu[4], hu[11], hc[1], hc[10], long_reads || export_all ? hc[6] : hc[6] ? hc[6] : hc[10], hc[3], (unsigned int)hu20, export_all ? 1 : 0);
-		unsigned long long sp[8];
-		D2H(L.st, sp, ctr + 48, sizeof(sp));
-		HIPCHK(hipMemsetAsync(ctr + 48, 0, sizeof(sp), L.st));
-		if (sp[0]) fprintf(stderr, "[M::regions_batch] k_seed: %.0f M wave cycles, %.1f%% in the full machine (%llu passes, %.0f cycles each), publishing %.1f%% | %llu wave trips, %.0f cycles per trip\n",
-		                   sp[0] * 1e-6, 100.0 * sp[1] / sp[0], sp[4], sp[4] ? (double)sp[1] / sp[4] : 0.0, 100.0 * sp[2] / sp[0], sp[3], sp[3] ? (double)sp[0] / sp[3] : 0.0);
-		{
-			unsigned long long tq[4];
-			D2H(L.st, tq, ctr + 121, sizeof(tq));
-			HIPCHK(hipMemsetAsync(ctr + 121, 0, sizeof(tq), L.st));
-			if (sp[0] && tq[3]) fprintf(stderr, "[M::regions_batch] k_seedt: short machine %.1f%%, fetch %.1f%%, post %.1f%% of the wave cycles | %.1f requests per wave trip\n",
-			                            100.0 * tq[0] / sp[0], 100.0 * tq[1] / sp[0], 100.0 * tq[2] / sp[0], sp[3] ? (double)tq[3] / sp[3] : 0.0);
-		}
-		{
-			unsigned long long xp[11];
-			D2H(L.st, xp, ctr + 56, sizeof(xp));
-			HIPCHK(hipMemsetAsync(ctr + 56, 0, sizeof(xp), L.st));
-			if (xp[0] || xp[6]) fprintf(stderr, "[M::regions_batch] k_ext4: %llu jobs, %llu rows in %llu wave trips (%.2f rows per trip), %llu passes between extensions, %.2f slots per trip, %llu rows of narrow jobs\n", xp[0], xp[1], xp[2], xp[2] ? (double)xp[1] / xp[2] : 0.0, xp[3], xp[2] ? (double)xp[4] / xp[2] : 0.0, xp[5]);
-			if (xp[6]) fprintf(stderr, "[M::regions_batch] k_extl: %llu jobs (%llu sent on to k_ext4), %llu rows in %llu wave trips (%.1f rows per trip), %llu passes between extensions\n", xp[6], xp[10], xp[7], xp[8], xp[8] ? (double)xp[7] / xp[8] : 0.0, xp[9]);
-		}
-		unsigned long long pf[16];
-		D2H(L.st, pf, ctr + 32, sizeof(pf));
-		HIPCHK(hipMemsetAsync(ctr + 32, 0, sizeof(pf), L.st));
-		double tot = 0; for (int k = 0; k < 8; ++k) tot += (double)pf[k];
-		if (tot > 0) fprintf(stderr, "[M::regions_batch] wave cycles by stage (all tiers): intervals %.1f%% occurrences %.1f%% chaining %.1f%% weights+order %.1f%% sort %.1f%% filter %.1f%% chain prologues+seed tests %.1f%% extension %.1f%% | %.0f M cycles, %llu extensions, %llu rows\n",
-		        100 * pf[0] / tot, 100 * pf[1] / tot, 100 * pf[2] / tot, 100 * pf[3] / tot, 100 * pf[4] / tot, 100 * pf[5] / tot, 100 * pf[6] / tot, 100 * pf[7] / tot, tot * 1e-6, pf[8], pf[9]);
-		if (pf[10]) fprintf(stderr, "[M::regions_batch] seed filter: %llu alignments\n", pf[10]);
-		if (pf[11]) fprintf(stderr, "[M::regions_batch] seed loops (mem_chain2region1): %llu seeds reached, %llu skipped as contained, %llu took the extension made ahead, %llu extended in place\n", pf[11], pf[12], pf[13], pf[14]);
-		{ // the HBM tiers: how long their strand searches take (a wave each)
-			unsigned long long tk[8];
-			D2H(L.st, tk, ctr + 110, sizeof(tk));
-			HIPCHK(hipMemsetAsync(ctr + 110, 0, sizeof(tk), L.st));
-			for (int k = 0; k < 2; ++k) if (tk[4 * k + 2])
-				fprintf(stderr, "[M::regions_batch] tier %d: %llu strand searches, %.2f M cycles each on average, the longest %.1f M, the busiest wave %.1f M, all of them %.0f M\n",
-				        2 + k, tk[4 * k + 2], 1e-6 * tk[4 * k + 1] / tk[4 * k + 2], 1e-6 * tk[4 * k], 1e-6 * tk[4 * k + 3], 1e-6 * tk[4 * k + 1]);
-			unsigned long long th[24];
-			D2H(L.st, th, ctr + 128, sizeof(th));
-			HIPCHK(hipMemsetAsync(ctr + 128, 0, sizeof(th), L.st));
-			if (th[0]) {
-				fprintf(stderr, "[M::regions_batch] tier 3: the longest strand search: %.1f M cycles, %llu intervals, %llu chains kept, %llu regions | strand searches by duration, < 2^k x 65536 cycles:",
-				        (double)(th[0] >> 36) * 4096e-6, (th[0] >> 24) & 4095, (th[0] >> 14) & 16383, th[0] & 16383);
-				for (int k = 0; k < 22; ++k) if (th[2 + k]) fprintf(stderr, " k=%d: %llu |", k, th[2 + k]);
-				fprintf(stderr, "\n");
-			}
-		}
-	}
-	clock_gettime(CLOCK_MONOTONIC, &ts_out);
-	if (trace) fprintf(stderr, "[M::regions_batch] entry to kernels enqueued %.0f ms | tiers done to regions downloaded %.0f ms (%llu regions)\n",
-	                   (ts0.tv_sec - ts_in.tv_sec) * 1e3 + (ts0.tv_nsec - ts_in.tv_nsec) * 1e-6, (ts_out.tv_sec - ts3.tv_sec) * 1e3 + (ts_out.tv_nsec - ts3.tv_nsec) * 1e-6, used);
-	// declined tasks: hand their interval lists back (ordered by info, as bsx_seed_batch returns them)
-	std::vector<int64_t> decl;
-	for (int64_t i = 0; i < n; ++i) if (out_n[i] < -1 && out_n[i] != BSX_REGIONS_PENDING) decl.push_back(i);
-	decl_off[0] = 0;
-	if (!decl.empty()) {
-		std::vector<long long> s_off((size_t)n); std::vector<int> s_n((size_t)n);
-		D2H(L.st, s_off.data(), d_off, (size_t)n * 8);
-		D2H(L.st, s_n.data(), d_n, (size_t)n * 4);
-		int64_t tot = 0;
-		for (size_t j = 0; j < decl.size(); ++j) { decl_off[j] = tot; tot += s_n[decl[j]]; }
-		decl_off[decl.size()] = tot;
-		if (*decl_cap < tot) { *decl_cap = tot + (tot >> 2) + 16; *decl_intv = (bsx_intv_t*)realloc(*decl_intv, sizeof(bsx_intv_t) * (size_t)*decl_cap); }
-		const bsx_intv_t *dense = nullptr;
-		if (decl.size() > 256 && tot > 0) { // many: their lists gathered on the device (they lie a strand search's stretch apart), one copy
-			std::vector<long long> which(decl.begin(), decl.end()), doff(decl_off, decl_off + decl.size());
-			for (size_t j = 0; j < decl.size(); ++j) if (s_n[decl[j]] < 0) { which.clear(); break; }   // (a list that did not fit has no entries to fetch: leave the one-by-one path to skip it)
-			if (!which.empty()) {
-				const size_t nb = decl.size() * 8;
-				if ((rc = L.gath.reserve(2 * nb + (size_t)tot * sizeof(bsx_intv_t) + 64)) != BSX_OK) return rc;
-				H2D(L.st, L.gath.p, which.data(), nb);
-				H2D(L.st, (char*)L.gath.p + nb, doff.data(), nb);
-				DevIntv *gd = (DevIntv*)((char*)L.gath.p + 2 * nb);
-				launch_gather_lists(L.st, (const DevIntv*)L.out.p, d_off, d_n, (const long long*)L.gath.p, (const long long*)((char*)L.gath.p + nb), (long long)decl.size(), gd);
-				if ((rc = L.hstage.reserve((size_t)tot * sizeof(bsx_intv_t) + 64)) != BSX_OK) return rc;
-				D2H(L.st, L.hstage.p, gd, (size_t)tot * sizeof(bsx_intv_t));
-				dense = (const bsx_intv_t*)L.hstage.p;
-			}
-		}
-		for (size_t j = 0; j < decl.size(); ++j) {
-			const int64_t i = decl[j]; const int cnt = s_n[i];
-			bsx_intv_t *dst = *decl_intv + decl_off[j];
-			if (cnt <= 0) continue;
-			if (dense) memcpy(dst, dense + decl_off[j], sizeof(bsx_intv_t) * (size_t)cnt);
-			else D2H(L.st, dst, (const bsx_intv_t*)L.out.p + s_off[i], sizeof(bsx_intv_t) * (size_t)cnt);
-			if (cnt > 1) std::sort(dst, dst + cnt, intv_info_lt);
-		}
-	}
-	if (trace) { // one line per call, with the lane: lines of chunks in flight together interleave
+	TRY(rg_side_sequence(B));
+	TRY(rg_wait_and_time(B));
+	TRY(rg_download(B, out, out_cap, out_off, out_n));
+	if (B.trace) TRY(rg_report(B));
+	clock_gettime(CLOCK_MONOTONIC, &B.ts_out);
+	if (B.trace) fprintf(stderr, "[M::regions_batch] entry to kernels enqueued %.0f ms | tiers done to regions downloaded %.0f ms (%llu regions)\n",
+	                     ms_between(B.ts_in, B.ts0), ms_between(B.ts3, B.ts_out), B.used);
+	TRY(rg_declined(B, out_n, decl_intv, decl_cap, decl_off));
+	if (B.trace) { // one line per call, with the lane: lines of chunks in flight together interleave
 		struct timespec te; clock_gettime(CLOCK_MONOTONIC, &te);
-#define MS_(a, b) (((b).tv_sec - (a).tv_sec) * 1e3 + ((b).tv_nsec - (a).tv_nsec) * 1e-6)
 		fprintf(stderr, "[M::regions_batch] lane %d from %.3f: %.0f ms = enqueue %.0f + seeding awaited %.0f + second pass enqueued %.0f + tiers awaited %.0f + counts and regions down %.0f + the rest %.0f\n",
-		        lane, ts_in.tv_sec % 1000 + ts_in.tv_nsec * 1e-9, MS_(ts_in, te), MS_(ts_in, ts0), MS_(ts0, ts1), MS_(ts1, ts2), MS_(ts2, ts3), MS_(ts3, ts_out), MS_(ts_out, te));
-#undef MS_
+		        lane, B.ts_in.tv_sec % 1000 + B.ts_in.tv_nsec * 1e-9, ms_between(B.ts_in, te), ms_between(B.ts_in, B.ts0), ms_between(B.ts0, B.ts1), ms_between(B.ts1, B.ts2), ms_between(B.ts2, B.ts3), ms_between(B.ts3, B.ts_out), ms_between(B.ts_out, te));
 	}
 	return BSX_OK;
 }
@@ -1377,7 +1496,7 @@ static int lane_regions_finish(bsx_device_t *d, int lane, bsx_region_t **out, in
 	// their regions lie behind the main sequence's in the device's pool: one copy of that stretch (a copy per strand search was tens
 	// of thousands of small transfers per chunk on a repeat-rich genome), then each list is taken from it
 	unsigned long long used_all = 0;
-	D2H(L.st2, &used_all, dev_counters(L) + 6, 8);
+	D2H(L.st2, &used_all, &ctr_shared(L)->region_cursor, 8);
 	if (used_all > L.rs.regs_cap) used_all = L.rs.regs_cap;   // (a cursor past the pool: the strand searches that found no room carry status 7)
 	const unsigned long long lo = L.rs.used_main, hi = std::max<unsigned long long>(used_all, lo);
 	std::vector<bsx_region_t> stretch;
@@ -1422,10 +1541,10 @@ static int lane_sa_batch(bsx_device_t *d, int lane, int64_t n, const bsx_sa_job_
 	if ((rc = L.res.reserve((size_t)n * 8)) != BSX_OK) return rc;
 	HIPCHK(hipMemcpyAsync(L.jobs.p, jobs, (size_t)n * sizeof(bsx_sa_job_t), hipMemcpyHostToDevice, L.st));
 	int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)d->n_cu * 8);
-	HIPCHK(hipEventRecord(L.ev0, L.st));
+	HIPCHK(hipEventRecord(L.ev_timed_begin, L.st));
 	launch_sa(L.st, grid, d->ix, (const bsx_sa_job_t*)L.jobs.p, (long long)n, (uint64_t*)L.res.p, dev_counters(L));
-	HIPCHK(hipEventRecord(L.ev1, L.st));
-	if ((rc = finish_timed(L, 1)) != BSX_OK) return rc;
+	HIPCHK(hipEventRecord(L.ev_timed_end, L.st));
+	if ((rc = finish_timed(L, KT_K3)) != BSX_OK) return rc;
 	D2H(L.st, pos, L.res.p, (size_t)n * 8);
 	return BSX_OK;
 }
@@ -1496,7 +1615,7 @@ static int lane_extend_batch(bsx_device_t *d, int lane, int64_t n, const bsx_ext
 		HIPCHK(hipMemcpyAsync((int*)L.aux.p + off, order[c].data(), order[c].size() * 4, hipMemcpyHostToDevice, S));
 		off += order[c].size();
 	}
-	HIPCHK(hipEventRecord(L.ev0, S));
+	HIPCHK(hipEventRecord(L.ev_timed_begin, S));
 	off = 0;
 	for (int c = 0; c < 4; ++c) if (!order[c].empty()) {
 		if (c == 3)
@@ -1507,8 +1626,8 @@ static int lane_extend_batch(bsx_device_t *d, int lane, int64_t n, const bsx_ext
 		              (long long)order[c].size(), (bsx_ext_res_t*)L.res.p, QCAP[c], NCS[c], d->n_cu);
 		off += order[c].size();
 	}
-	HIPCHK(hipEventRecord(L.ev1, S));
-	if ((rc = finish_timed(L, 2)) != BSX_OK) return rc;
+	HIPCHK(hipEventRecord(L.ev_timed_end, S));
+	if ((rc = finish_timed(L, KT_EXTEND)) != BSX_OK) return rc;
 	D2H(S, res, L.res.p, (size_t)n * sizeof(bsx_ext_res_t));
 	return BSX_OK;
 }
@@ -1562,7 +1681,7 @@ static int lane_sw_batch(bsx_device_t *d, int lane, int64_t n, const bsx_sw_job_
 		H2D(L.st_hi, (int*)L.aux.p + off, order[c].data(), order[c].size() * 4);
 		off += order[c].size();
 	}
-	HIPCHK(hipEventRecord(L.ev0, L.st_hi));
+	HIPCHK(hipEventRecord(L.ev_timed_begin, L.st_hi));
 	off = 0;
 	for (int c = 0; c < 4; ++c) if (!order[c].empty()) {
 		const long long m = (long long)order[c].size();
@@ -1577,12 +1696,12 @@ static int lane_sw_batch(bsx_device_t *d, int lane, int64_t n, const bsx_sw_job_
 		}
 		off += order[c].size();
 	}
-	HIPCHK(hipEventRecord(L.ev1, L.st_hi));
+	HIPCHK(hipEventRecord(L.ev_timed_end, L.st_hi));
 	const double ts1 = tr_sw ? bsx_now_s() : 0;
-	if ((rc = finish_timed(L, 3)) != BSX_OK) return rc;
+	if ((rc = finish_timed(L, KT_SW)) != BSX_OK) return rc;
 	const double ts2 = tr_sw ? bsx_now_s() : 0;
 	D2H(L.st_hi, res, L.res.p, (size_t)n * sizeof(bsx_sw_res_t));
-	if (tr_sw) { float ms = 0; (void)hipEventElapsedTime(&ms, L.ev0, L.ev1);
+	if (tr_sw) { float ms = 0; (void)hipEventElapsedTime(&ms, L.ev_timed_begin, L.ev_timed_end);
 		fprintf(stderr, "[M::sw_batch] %lld jobs: upload %.3f s, waited %.3f s for the kernels (%.3f s on the device), download %.3f s\n", (long long)n, ts1 - ts0, ts2 - ts1, ms * 1e-3, bsx_now_s() - ts2); }
 	return BSX_OK;
 }
@@ -1607,13 +1726,13 @@ static int lane_regions_dedup(bsx_device_t *d, int lane, const bsx_opt_t *opt, i
 	const bool with_long = long_off && long_idx && long_cap && per_read <= 4 && bsx_tune_long("long_dedup", 1) != 0;
 	const size_t pool_cap = with_long ? (size_t)L.rs.used_main + 64 : 0;
 	// layout of L.dd: counts | short lists | [long: class lists (2 n_reads ints) | offsets (n_reads i64) | 2 counters + cursor (16 B) | pool]
-	const size_t o_idx = (size_t)n_reads * 4, o_list = (o_idx + (size_t)n_reads * cap + 15) & ~(size_t)15, o_off = o_list + (size_t)n_reads * 8, o_ctr = o_off + (size_t)n_reads * 8, o_pool = o_ctr + 16;
+	const size_t o_idx = (size_t)n_reads * 4, o_list = (o_idx + (size_t)n_reads * cap + 15) & ~(size_t)15, o_off = o_list + (size_t)n_reads * 8, o_cnt = o_off + (size_t)n_reads * 8, o_pool = o_cnt + 16;
 	if ((rc = L.dd.reserve(with_long ? o_pool + pool_cap * 2 + 64 : o_idx + (size_t)n_reads * cap + 64)) != BSX_OK) return rc;
 	const long long *r_off = (const long long*)L.regmeta.p; const int *r_n = (const int*)((const char*)L.regmeta.p + (size_t)n * 8);
 	int *d_n = (int*)L.dd.p; unsigned char *d_idx = (unsigned char*)L.dd.p + o_idx;
 	int *d_list = with_long ? (int*)((char*)L.dd.p + o_list) : nullptr;
 	long long *d_off = (long long*)((char*)L.dd.p + o_off);
-	unsigned int *d_cnt = with_long ? (unsigned int*)((char*)L.dd.p + o_ctr) : nullptr;
+	unsigned int *d_cnt = with_long ? (unsigned int*)((char*)L.dd.p + o_cnt) : nullptr;
 	if (with_long) {
 		HIPCHK(hipMemsetAsync(d_cnt, 0, 16, L.st));
 		HIPCHK(hipMemsetAsync(d_off, 0xff, (size_t)n_reads * 8, L.st));   // -1: the read's list (if it has one) is among the short ones
@@ -1689,11 +1808,11 @@ static int lane_msw_plan(bsx_device_t *d, int lane, const bsx_opt_t *opt, const 
 		if (bound > (1 << 20)) { *n_jobs = -1; return BSX_OK; }                       // (absurd insert-size bounds: the host's path sizes its scratch from the jobs)
 		if ((rc = L.scratch.reserve((size_t)blocks_cap * 4 * 4 * (size_t)bound * 8)) != BSX_OK) return rc;
 		const int blocks = (int)std::min<long long>(((long long)nj + 15) / 16, blocks_cap);
-		HIPCHK(hipEventRecord(L.ev0, L.st_hi));
+		HIPCHK(hipEventRecord(L.ev_timed_begin, L.st_hi));
 		launch_swl(L.st_hi, d->ix, L.sc, (const uint8_t*)L.reads.p, (const bsx_sw_job_t*)L.msw_jobs.p, (const int*)d_ord, (long long)nj,
 		           (bsx_sw_res_t*)L.msw_res.p, (unsigned long long*)L.scratch.p, (int)bound, blocks, (max_len + 15) / 16);
-		HIPCHK(hipEventRecord(L.ev1, L.st_hi));
-		if ((rc = finish_timed(L, 3)) != BSX_OK) return rc;
+		HIPCHK(hipEventRecord(L.ev_timed_end, L.st_hi));
+		if ((rc = finish_timed(L, KT_SW)) != BSX_OK) return rc;
 		if (*res_cap < (int64_t)nj) { *res_cap = (int64_t)nj + (nj >> 2) + 1024; *res = (bsx_sw_res_t*)realloc(*res, sizeof(bsx_sw_res_t) * (size_t)*res_cap); }
 		D2H(L.st_hi, *res, L.msw_res.p, (size_t)nj * sizeof(bsx_sw_res_t));
 	}
@@ -1767,7 +1886,7 @@ static int lane_global_batch(bsx_device_t *d, int lane, int64_t n, const bsx_glb
 	const size_t rows_off = (ztot + 256 + 255) & ~(size_t)255, rows_bytes = hbm_qmax ? (size_t)blocks[3] * global_hbm_row_bytes(hbm_qmax) : 0;
 	if ((rc = L.scratch.reserve(rows_off + rows_bytes)) != BSX_OK) return rc;
 	if ((rc = L.pool.reserve(cigar_pool_len * 4 + 64)) != BSX_OK) return rc;
-	unsigned long long *md_cursor = dev_counters(L) + 60;
+	unsigned long long *md_cursor = dev_counters(L) + CTR_MD_CURSOR;
 	if (tags) {
 		if ((rc = L.tags.reserve((size_t)n * sizeof(bsx_glb_tag_t))) != BSX_OK) return rc;
 		if ((rc = L.mdpool.reserve(md_bound)) != BSX_OK) return rc;
@@ -1784,7 +1903,7 @@ static int lane_global_batch(bsx_device_t *d, int lane, int64_t n, const bsx_glb
 		H2D(L.st_hi, (int*)L.aux.p + off, order[c].data(), order[c].size() * 4);
 		off += order[c].size();
 	}
-	HIPCHK(hipEventRecord(L.ev0, L.st_hi));
+	HIPCHK(hipEventRecord(L.ev_timed_begin, L.st_hi));
 	off = 0;
 	for (int c = 0; c < 4; ++c) if (!order[c].empty()) {
 		if (c == 3)
@@ -1799,8 +1918,8 @@ static int lane_global_batch(bsx_device_t *d, int lane, int64_t n, const bsx_glb
 		              ctx ? (bsx_glb_ctx_t*)L.gctx.p : nullptr);
 		off += order[c].size();
 	}
-	HIPCHK(hipEventRecord(L.ev1, L.st_hi));
-	if ((rc = finish_timed(L, 4)) != BSX_OK) return rc;
+	HIPCHK(hipEventRecord(L.ev_timed_end, L.st_hi));
+	if ((rc = finish_timed(L, KT_GLOBAL)) != BSX_OK) return rc;
 	D2H(L.st_hi, res, L.res.p, (size_t)n * sizeof(bsx_glb_res_t));
 	D2H(L.st_hi, cigar_pool, L.pool.p, cigar_pool_len * 4);
 	if (tags) {
@@ -1961,7 +2080,7 @@ static int md_room(bsx_device_t *d, Lane &L, uint64_t more, unsigned long long *
 		unsigned long long lost = 0;
 		launch_md_rehash(L.st_hi, d->md, d->md_slots, T, want, ctr);
 		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(&lost, ctr + 2, 8, hipMemcpyDeviceToHost, L.st_hi));
+		HIPCHK(hipMemcpyAsync(&lost, ctr + MD_CTR_LOST, 8, hipMemcpyDeviceToHost, L.st_hi));
 		HIPCHK(hipStreamSynchronize(L.st_hi));
 		if (lost) { (void)hipFree(T); return BSX_E_INTERNAL; }
 		(void)hipFree(d->md);

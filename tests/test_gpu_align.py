@@ -127,6 +127,36 @@ def test_device_regions_equal_host_chaining(data, name, args):
     assert ("every tier exports: 1" in err) == special and ("every tier exports: 0" in err) == (not special), name
 
 
+def test_launch_marks_and_per_tier_readout(data):
+    """The marks between the region launches ($BSX_TIERS: events only) and $BSX_PHASES=2 (the stage counters read and zeroed after
+    every launch, the host waiting for the stream each time) change what the host does between the launches, not the SAM.  With the
+    marks alone the launches of an ordinary chunk are named in the order the code gives them at default settings; under phases=2
+    every tier reports its wave cycles and the last HBM tier is not launched beside the others."""
+    import re
+    from biscuit_amd._lib import tune_env
+    args = CASES[1][1]
+
+    def go(env):
+        e = dict(os.environ)
+        e.update(tune_env(env))
+        p = subprocess.run([HIP] + args, cwd=data, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120, env=e)
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        return b"\n".join(l for l in p.stdout.split(b"\n") if not l.startswith(b"@PG")), p.stderr.decode()
+
+    plain, _ = go({})
+    marks, err_marks = go({"tiers": "1"})
+    per_tier, err_tier = go({"BSX_PHASES": "2"})
+    assert plain.count(b"\n") > 8000
+    assert marks == plain and per_tier == plain
+    lines = re.findall(r"\[M::regions_batch\] region launches \(ms\):(.*)", err_marks)
+    assert lines, err_marks[-1500:]
+    for rest in lines:
+        names = re.findall(r" ([^|]+?) [0-9.]+ \|", rest)
+        assert names[:7] == ["tier 1", "tier 1b", "tier 1c", "extensions", "chains -> regions", "tier 2", "tier 3"], rest
+    assert re.search(r"\[M::regions_batch\] tier 1: intervals .* wave cycles", err_tier), err_tier[-3000:]
+    assert "region launches (ms):" in err_tier and "tier 3 beside them" not in err_tier
+
+
 def test_device_regions_equal_host_chaining_repeat_rich(tmp_path):
     """Same A/B at the bench's workload shape (synthetic genome with repeat families, 2x150 pairs, -b 0):
     60k pairs through bsx_process_seqs with the device regions pass and with host chaining; every read's
