@@ -88,7 +88,7 @@ class GlbTag(C.Structure):
 
 class Backend(C.Structure):  # bsx_backend_t (csrc/host/bsx_core.h)
     _fields_ = [("ctx", C.c_void_p), ("name", C.c_char_p)] + [(n, C.c_void_p) for n in
-                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p)]
+                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p)]
 
 
 class GlbCtx(C.Structure):  # bsx_glb_ctx_t: [strand hypothesis][A, C, G, T, N context][retained, converted]
@@ -100,6 +100,18 @@ class QcJob(C.Structure):  # bsx_qc_job_t
 
 
 QC_REVERSE, QC_READ2, QC_STRAND, QC_CINREAD, QC_BSCONV, QC_READ_LEN = 0x1, 0x2, 0x10, 0x20, 0x40, 301
+
+
+QC_COV, QC_COV_Q40 = 0x80, 0x100      # bsx_qc_job_t.flags: the job counts towards the depth of the coverage tables (all; and q40)
+COV_TILE, COV_N_TABLES, COV_MASK_TOPGC, COV_MASK_BOTGC = 4096, 12, 0, 1      # BSX_COV_TILE: positions a workgroup of k_cov.hip's final passes scans at a time
+
+
+class CovTable(C.Structure):  # bsx_cov_table_t
+    _fields_ = [("n_bins", C.c_uint64), ("count", C.POINTER(C.c_uint64))]
+
+
+class CovTables(C.Structure):  # bsx_cov_tables_t: [region * 4 + class * 2 + kind]; region: whole genome, top GC, bottom GC; class: all, q40; kind: bases, CpGs
+    _fields_ = [("t", CovTable * 12), ("have_gc", C.c_int)]
 
 
 class QcCounts(C.Structure):  # bsx_qc_counts_t: [CpG, CpH][read][position][converted, retained], the eight totals, confusion[tag * 4 + inferred]

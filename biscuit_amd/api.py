@@ -142,6 +142,11 @@ def _libc_free(p):
     _libc.free(p)
 
 
+def cov_tables_arrays(t):
+    """a filled _lib.CovTables as int64 arrays (copies)"""
+    return [np.ctypeslib.as_array(t.t[i].count, shape=(int(t.t[i].n_bins),)).astype(np.int64) for i in range(12 if t.have_gc else 4)]
+
+
 class Device(Batches):
     """bsx_device_* : one HIP device with the index resident in HBM.  Raises if there is no GPU."""
 
@@ -277,6 +282,40 @@ class Device(Batches):
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         B.check(f(self.h, C.byref(c), int(reset)), "bsx_qc_read")
         return (np.array(c.readpos, dtype=np.int64).reshape(2, 2, 301, 2), np.array(c.conv, dtype=np.int64), np.array(c.confusion, dtype=np.int64))
+
+    def cov_batch(self, jobs, pool):
+        """bsx_cov_batch: the M runs of the jobs with QC_COV (array of _lib.QcJob's layout; pool: their CIGAR words) added to the device's depth state"""
+        jobs = np.ascontiguousarray(jobs, dtype=np.dtype(B.QcJob))
+        pool = np.ascontiguousarray(pool, dtype=np.uint32)
+        f = B.lib().bsx_cov_batch
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t]
+        B.check(f(self.h, len(jobs), _p(jobs), _p(pool), pool.size), "bsx_cov_batch")
+
+    def cov_set_mask(self, which, intervals):
+        """bsx_cov_set_mask: mask `which` (_lib.COV_MASK_TOPGC / _BOTGC) = the union of the half-open intervals [(beg, end)] of forward coordinates"""
+        iv = np.ascontiguousarray(intervals, dtype=np.int64).reshape(-1, 2)
+        f = B.lib().bsx_cov_set_mask
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        B.check(f(self.h, int(which), len(iv), _p(iv) if len(iv) else None), "bsx_cov_set_mask")
+
+    def cov_tables(self):
+        """bsx_cov_tables -> twelve int64 arrays count[depth] (four without the masks), in the order of _lib.CovTables"""
+        t = B.CovTables()
+        L = B.lib()
+        L.bsx_cov_tables.argtypes = [C.c_void_p, C.c_void_p]
+        L.bsx_cov_tables_free.argtypes = [C.c_void_p]
+        L.bsx_cov_tables_free.restype = None
+        B.check(L.bsx_cov_tables(self.h, C.byref(t)), "bsx_cov_tables")
+        try:
+            return cov_tables_arrays(t)
+        finally:
+            L.bsx_cov_tables_free(C.byref(t))
+
+    def cov_reset(self):
+        """bsx_cov_reset: the depth state and both masks freed"""
+        f = B.lib().bsx_cov_reset
+        f.argtypes = [C.c_void_p]
+        B.check(f(self.h), "bsx_cov_reset")
 
     def markdup_batch(self, keys, first_ordinal):
         """bsx_markdup_batch: keys = uint64[n, 2] (_lib.MarkdupKey's layout; both words all ones: skipped), the template with ordinal

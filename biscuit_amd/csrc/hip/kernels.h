@@ -45,6 +45,23 @@ void launch_global(hipStream_t st, const DevIndex &ix, const DevScoring &sc, con
 // k_qc.hip: the column counts of `biscuit qc` over n records (bsx_qc_job_t), added to the device's table (bsx_qc_counts_t as 64-bit cells)
 void launch_qc(hipStream_t st, const DevIndex &ix, const uint8_t *reads, long long reads_len, const bsx_qc_job_t *jobs, long long n, const uint32_t *pool,
                unsigned long long *table, int n_cu);
+// k_cov.hip: the BISCUITqc coverage tables.  diff: cov_diff_entries(l_pac) entries of two ints (all, q40), the difference array of the depth, zero
+// past entry l_pac; a mask: cov_mask_words(l_pac) words, bit (p & 31) of word p >> 5 for position p.  launch_cov_add: the M runs of the jobs with
+// BSX_QC_COV as +1 / -1 events.  The tables, in this order: launch_cov_sums (tsum: cov_n_tiles(l_pac) pairs, afterwards each tile's carry-in),
+// launch_cov_max (*gmax, zeroed before: the largest `all` depth), launch_cov_count (bins: BSX_COV_N_TABLES x nb zeroed 64-bit cells, nb > *gmax;
+// m_top and m_bot both or neither; lds_bins: a power of two up to COV_LDS_BINS_MAX; a workgroup adds its LDS cells to bins every flush_tiles tiles,
+// flush_tiles x BSX_COV_TILE < 2^32).  ix.pac must be readable for 8 bytes past its l_pac / 4 + 1 (bsx_device_upload_index reserves 16): the last
+// lanes below l_pac read their 16 bases as one dword and the next base from the byte behind it)
+#define COV_LDS_BINS_MAX 512
+size_t cov_n_tiles(long long l_pac);
+size_t cov_diff_entries(long long l_pac);
+size_t cov_mask_words(long long l_pac);
+void launch_cov_add(hipStream_t st, int n_cu, void *diff, long long l_pac, const bsx_qc_job_t *jobs, long long n, const uint32_t *pool, long long pool_len);
+void launch_cov_paint(hipStream_t st, int n_cu, uint32_t *mask, long long l_pac, const long long *beg_end, long long n);
+void launch_cov_sums(hipStream_t st, int n_cu, const void *diff, long long n_tiles, void *tsum);
+void launch_cov_max(hipStream_t st, int n_cu, const DevIndex &ix, const void *diff, const void *carry, long long n_tiles, int *gmax);
+void launch_cov_count(hipStream_t st, int n_cu, const DevIndex &ix, const void *diff, const void *carry, long long n_tiles, const uint32_t *m_top,
+                      const uint32_t *m_bot, int lds_bins, int flush_tiles, unsigned long long *bins, long long nb);
 // k_markdup.hip: the device's table of template keys (bsx_markdup_batch).  A slot: claim word (0: empty), lowest ordinal, the key (all ones: none yet)
 struct MdSlot { unsigned long long claim, ord, k0, k1; };
 enum { MD_CTR_TAKEN = 0, MD_CTR_OPEN = 1, MD_CTR_LOST = 2 };   // ctr[] of the two launchers below

@@ -82,6 +82,10 @@ struct bsx_device {
 	DevBuf bwt[2], sa[2], pac, ctg, holes, seedtab[2];
 	DevBuf qc;   // bsx_qc_counts_t: the BISCUITqc column counts of every lane's batches (k_qc.hip), zeroed when made and by bsx_qc_read(reset)
 	std::mutex qc_mu;
+	// the depth state of the coverage tables (k_cov.hip): the difference array (made and zeroed on first use) and the two optional masks, kept
+	// until bsx_cov_reset / close
+	void *cov_diff = nullptr; uint32_t *cov_mask[2] = {nullptr, nullptr};
+	std::mutex cov_mu;
 	// the table of template keys (k_markdup.hip): made by the first bsx_markdup_batch, doubled as it fills, kept until bsx_markdup_reset / close
 	MdSlot *md = nullptr; uint64_t md_slots = 0, md_used = 0;
 	std::mutex md_mu;
@@ -173,6 +177,12 @@ extern "C" BSX_API int bsx_device_open(int ordinal, bsx_device_t **out)
 	return BSX_OK;
 }
 
+static void cov_release(bsx_device *d)
+{
+	if (d->cov_diff) { (void)hipFree(d->cov_diff); d->cov_diff = nullptr; }
+	for (int w = 0; w < 2; ++w) if (d->cov_mask[w]) { (void)hipFree(d->cov_mask[w]); d->cov_mask[w] = nullptr; }
+}
+
 extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 {
 	if (!d) return;
@@ -181,6 +191,7 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 	for (int i = 0; i < 2; ++i) { d->bwt[i].release(); d->sa[i].release(); d->seedtab[i].release(); }
 	d->pac.release(); d->ctg.release(); d->holes.release(); d->qc.release();
 	if (d->md) { (void)hipFree(d->md); d->md = nullptr; d->md_slots = d->md_used = 0; }
+	cov_release(d);
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
 		L.reads.release(); L.qpack.release(); L.gath.release(); L.jobs.release(); L.res.release(); L.scratch.release(); L.scratch2.release(); L.out.release(); L.aux.release(); L.pool.release();
@@ -2001,7 +2012,9 @@ static int qc_table(bsx_device_t *d)   // the device's table, made on first use
 	HIPCHK(hipMemset(d->qc.p, 0, sizeof(bsx_qc_counts_t)));
 	return BSX_OK;
 }
-static int lane_qc_batch(bsx_device_t *d, int lane, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
+static int cov_state_locked(bsx_device_t *d);
+// with_cov: the same upload also feeds k_cov_add (the jobs with BSX_QC_COV into the depth state of the coverage tables, below)
+static int lane_qc_batch(bsx_device_t *d, int lane, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len, bool with_cov = false)
 {
 	if (!d || !d->has_index) return BSX_E_NODEVICE;
 	if (n == 0) return BSX_OK;
@@ -2012,9 +2025,10 @@ static int lane_qc_batch(bsx_device_t *d, int lane, int64_t n, const bsx_qc_job_
 		if ((size_t)j.cig_off + j.n_cigar > cigar_pool_len || j.rlen > (1u << 30) || j.fpos < 0 || j.fpos >= d->ix.l_pac) {
 			fprintf(stderr, "[bsx-hip] qc job %lld: invalid\n", (long long)i); return BSX_E_ARG;
 		}
-		uint64_t span = 0;
-		for (uint32_t k = 0; k < j.n_cigar; ++k) { const uint32_t c = cigar_pool[j.cig_off + k]; if ((c & 0xf) > 4) return BSX_E_ARG; span += c >> 4; }
+		uint64_t span = 0, rspan = 0;
+		for (uint32_t k = 0; k < j.n_cigar; ++k) { const uint32_t c = cigar_pool[j.cig_off + k], op = c & 0xf; if (op > 4) return BSX_E_ARG; span += c >> 4; if (op == 0 || op == 2) rspan += c >> 4; }
 		if (span > (1u << 30)) return BSX_E_ARG;
+		if (with_cov && (uint64_t)j.fpos + rspan > (uint64_t)d->ix.l_pac) { fprintf(stderr, "[bsx-hip] cov job %lld: beyond the reference\n", (long long)i); return BSX_E_ARG; }
 	}
 	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
 	HIPCHK(hipSetDevice(d->ordinal));
@@ -2027,6 +2041,14 @@ static int lane_qc_batch(bsx_device_t *d, int lane, int64_t n, const bsx_qc_job_
 	launch_qc(L.st_hi, d->ix, (const uint8_t*)L.reads.p, (long long)L.n_reads, (const bsx_qc_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p,
 	          (unsigned long long*)d->qc.p, d->n_cu);
 	HIPCHK(hipGetLastError());
+	if (with_cov) { // (the depth state stays where it is until the launch is done: bsx_cov_reset takes the same lock)
+		std::lock_guard<std::mutex> lock(d->cov_mu);
+		if ((rc = cov_state_locked(d)) != BSX_OK) { (void)hipStreamSynchronize(L.st_hi); return rc; }
+		launch_cov_add(L.st_hi, d->n_cu, d->cov_diff, d->ix.l_pac, (const bsx_qc_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p, (long long)cigar_pool_len);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipStreamSynchronize(L.st_hi));
+		return BSX_OK;
+	}
 	HIPCHK(hipStreamSynchronize(L.st_hi));   // the lane's read buffer belongs to the next chunk once the caller is done with this one
 	return BSX_OK;
 }
@@ -2045,6 +2067,133 @@ static int dev_qc_read(bsx_device_t *d, bsx_qc_counts_t *out, int reset)
 extern "C" BSX_API int bsx_qc_batch(bsx_device_t *d, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
 { return lane_qc_batch(d, 0, n, jobs, cigar_pool, cigar_pool_len); }
 extern "C" BSX_API int bsx_qc_read(bsx_device_t *d, bsx_qc_counts_t *out, int reset) { return dev_qc_read(d, out, reset); }
+
+// ------------------------------------------------------------------------------------------
+// BISCUITqc coverage tables (k_cov.hip)
+// ------------------------------------------------------------------------------------------
+static int cov_alloc(const char *what, size_t bytes, void **out)   // zeroed device memory that is not a lane's
+{
+	*out = nullptr;
+	if (hipMalloc(out, bytes) != hipSuccess) {
+		size_t fr = 0, tot = 0; (void)hipGetLastError(); (void)hipMemGetInfo(&fr, &tot);
+		fprintf(stderr, "[bsx-hip] coverage tables: no room for %s, %zu bytes (%zu of %zu bytes free)\n", what, bytes, fr, tot);
+		*out = nullptr; return BSX_E_NOMEM;
+	}
+	// the lanes' streams do not wait for the null stream: the zeroes are there before anything is launched on one of them
+	if (hipMemsetAsync(*out, 0, bytes, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(*out); *out = nullptr; return BSX_E_NODEVICE; }
+	return BSX_OK;
+}
+static int cov_state_locked(bsx_device_t *d)   // the difference array, made on first use; the caller holds cov_mu
+{
+	if (d->cov_diff) return BSX_OK;
+	return cov_alloc("the depth state", cov_diff_entries(d->ix.l_pac) * 8, &d->cov_diff);
+}
+static int lane_cov_batch(bsx_device_t *d, int lane, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (n == 0) return BSX_OK;
+	if (n < 0 || !jobs || (!cigar_pool && cigar_pool_len)) return BSX_E_ARG;
+	Lane &L = d->lane[lane];
+	for (int64_t i = 0; i < n; ++i) { // every event of every job inside the array, every CIGAR word inside the pool
+		const bsx_qc_job_t &j = jobs[i];
+		if ((size_t)j.cig_off + j.n_cigar > cigar_pool_len || j.fpos < 0 || j.fpos > d->ix.l_pac) { fprintf(stderr, "[bsx-hip] cov job %lld: invalid\n", (long long)i); return BSX_E_ARG; }
+		uint64_t span = 0;
+		for (uint32_t k = 0; k < j.n_cigar; ++k) { const uint32_t c = cigar_pool[j.cig_off + k]; const uint32_t op = c & 0xf; if (op > 4) return BSX_E_ARG; if (op == 0 || op == 2) span += c >> 4; }
+		if ((uint64_t)j.fpos + span > (uint64_t)d->ix.l_pac) { fprintf(stderr, "[bsx-hip] cov job %lld: beyond the reference\n", (long long)i); return BSX_E_ARG; }
+	}
+	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
+	std::lock_guard<std::mutex> lock(d->cov_mu);   // until the launch is done: bsx_cov_reset frees the state under the same lock
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc;
+	if ((rc = cov_state_locked(d)) != BSX_OK) return rc;
+	if ((rc = L.qcjobs.reserve((size_t)n * sizeof(bsx_qc_job_t))) != BSX_OK) return rc;
+	if ((rc = L.qcpool.reserve(cigar_pool_len * 4 + 64)) != BSX_OK) return rc;
+	H2D(L.st_hi, L.qcjobs.p, jobs, (size_t)n * sizeof(bsx_qc_job_t));
+	H2D(L.st_hi, L.qcpool.p, cigar_pool, cigar_pool_len * 4);
+	launch_cov_add(L.st_hi, d->n_cu, d->cov_diff, d->ix.l_pac, (const bsx_qc_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p, (long long)cigar_pool_len);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(L.st_hi));   // the staging buffers are the next batch's
+	return BSX_OK;
+}
+static int dev_cov_set_mask(bsx_device_t *d, int which, int64_t n, const int64_t *beg_end)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (which < 0 || which > 1 || n < 0 || (n && !beg_end)) return BSX_E_ARG;
+	for (int64_t i = 0; i < n; ++i) if (beg_end[2 * i] < 0 || beg_end[2 * i] > beg_end[2 * i + 1] || beg_end[2 * i + 1] > d->ix.l_pac) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->cov_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	HIPCHK(hipDeviceSynchronize());
+	const size_t bytes = cov_mask_words(d->ix.l_pac) * 4;
+	int rc;
+	if (d->cov_mask[which]) HIPCHK(hipMemset(d->cov_mask[which], 0, bytes));
+	else if ((rc = cov_alloc("a mask", bytes, (void**)&d->cov_mask[which])) != BSX_OK) return rc;
+	if (n == 0) return BSX_OK;
+	long long *iv = nullptr;
+	if (hipMalloc((void**)&iv, (size_t)n * 16) != hipSuccess) { (void)hipGetLastError(); return BSX_E_NOMEM; }
+	hipError_t e = hipMemcpy(iv, beg_end, (size_t)n * 16, hipMemcpyHostToDevice);
+	if (e == hipSuccess) { launch_cov_paint(0, d->n_cu, d->cov_mask[which], d->ix.l_pac, iv, (long long)n); e = hipGetLastError(); }
+	if (e == hipSuccess) e = hipDeviceSynchronize();
+	(void)hipFree(iv);
+	HIPCHK(e);
+	return BSX_OK;
+}
+static int dev_cov_tables(bsx_device_t *d, bsx_cov_tables_t *out)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (!out) return BSX_E_ARG;
+	memset(out, 0, sizeof(*out));
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc;
+	long lds_bins = bsx_tune_long("cov_lds_bins", COV_LDS_BINS_MAX), flush_tiles = bsx_tune_long("cov_flush_tiles", 524287);
+	if (lds_bins < 1 || lds_bins > COV_LDS_BINS_MAX || (lds_bins & (lds_bins - 1)) || flush_tiles < 1 || flush_tiles > 524287) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->cov_mu);
+	if ((rc = cov_state_locked(d)) != BSX_OK) return rc;
+	if ((d->cov_mask[0] != nullptr) != (d->cov_mask[1] != nullptr)) { fprintf(stderr, "[bsx-hip] coverage tables: one GC mask without the other\n"); return BSX_E_ARG; }
+	HIPCHK(hipDeviceSynchronize());   // every lane's batches
+	const long long n_tiles = (long long)cov_n_tiles(d->ix.l_pac);
+	void *tsum = nullptr, *bins = nullptr;
+	if ((rc = cov_alloc("the tile sums", (size_t)n_tiles * 8 + 16, &tsum)) != BSX_OK) return rc;
+	int *gmax = (int*)((char*)tsum + (size_t)n_tiles * 8);
+	int vmax = 0;
+	hipError_t e = hipSuccess;
+	launch_cov_sums(0, d->n_cu, d->cov_diff, n_tiles, tsum);
+	launch_cov_max(0, d->n_cu, d->ix, d->cov_diff, tsum, n_tiles, gmax);
+	e = hipGetLastError();
+	if (e == hipSuccess) e = hipMemcpy(&vmax, gmax, 4, hipMemcpyDeviceToHost);
+	const uint64_t nb = (uint64_t)(vmax < 0 ? 0 : vmax) + 1;
+	std::vector<uint64_t> host((size_t)BSX_COV_N_TABLES * nb);
+	if (e == hipSuccess && (rc = cov_alloc("the bins", host.size() * 8, &bins)) == BSX_OK) {
+		launch_cov_count(0, d->n_cu, d->ix, d->cov_diff, tsum, n_tiles, d->cov_mask[0], d->cov_mask[1], (int)lds_bins, (int)flush_tiles, (unsigned long long*)bins, (long long)nb);
+		e = hipGetLastError();
+		if (e == hipSuccess) e = hipMemcpy(host.data(), bins, host.size() * 8, hipMemcpyDeviceToHost);
+	}
+	(void)hipFree(tsum);
+	if (bins) (void)hipFree(bins);
+	if (rc != BSX_OK) return rc;
+	HIPCHK(e);
+	out->have_gc = d->cov_mask[0] ? 1 : 0;
+	for (int i = 0; i < (out->have_gc ? BSX_COV_N_TABLES : 4); ++i) {
+		out->t[i].count = (uint64_t*)malloc(nb * 8);
+		if (!out->t[i].count) { bsx_cov_tables_free(out); return BSX_E_NOMEM; }
+		memcpy(out->t[i].count, host.data() + (size_t)i * nb, nb * 8);
+		out->t[i].n_bins = nb;
+	}
+	return BSX_OK;
+}
+static int dev_cov_reset(bsx_device_t *d)
+{
+	if (!d) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->cov_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (d->cov_diff || d->cov_mask[0] || d->cov_mask[1]) HIPCHK(hipDeviceSynchronize());
+	cov_release(d);
+	return BSX_OK;
+}
+extern "C" BSX_API int bsx_cov_batch(bsx_device_t *d, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
+{ return lane_cov_batch(d, 0, n, jobs, cigar_pool, cigar_pool_len); }
+extern "C" BSX_API int bsx_cov_set_mask(bsx_device_t *d, int which, int64_t n, const int64_t *beg_end) { return dev_cov_set_mask(d, which, n, beg_end); }
+extern "C" BSX_API int bsx_cov_tables(bsx_device_t *d, bsx_cov_tables_t *out) { return dev_cov_tables(d, out); }
+extern "C" BSX_API int bsx_cov_reset(bsx_device_t *d) { return dev_cov_reset(d); }
 
 // ------------------------------------------------------------------------------------------
 // duplicate templates (k_markdup.hip)
@@ -2191,6 +2340,17 @@ static int be_qc(void *c, int64_t n, const bsx_qc_job_t *j, const uint32_t *pool
 
 static int be_markdup(void *c, int64_t n, const bsx_markdup_key_t *k, uint64_t first, uint8_t *out) { return lane_markdup_batch(LR(c), n, k, first, out); }
 
+static int be_cov(void *c, int op, int64_t n, const bsx_qc_job_t *j, const uint32_t *pool, size_t len, const int64_t *beg_end, bsx_cov_tables_t *out)
+{
+	bsx_device_t *d = ((LaneRef*)c)->d;
+	if (op == BSX_COV_OP_BATCH) return lane_cov_batch(LR(c), n, j, pool, len);
+	if (op == BSX_COV_OP_QC_BATCH) return lane_qc_batch(LR(c), n, j, pool, len, true);
+	if (op == BSX_COV_OP_MASK || op == BSX_COV_OP_MASK + 1) return dev_cov_set_mask(d, op - BSX_COV_OP_MASK, n, beg_end);
+	if (op == BSX_COV_OP_TABLES) return dev_cov_tables(d, out);
+	if (op == BSX_COV_OP_RESET) return dev_cov_reset(d);
+	return BSX_E_ARG;
+}
+
 static LaneRef g_lane_ref[8][BSX_LANES];   // ctx storage for the vtables (by device ordinal)
 
 extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *out)
@@ -2202,7 +2362,7 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	memset(out, 0, sizeof(*out));
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
-	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup;
+	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov;
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

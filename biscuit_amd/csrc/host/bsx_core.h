@@ -196,7 +196,14 @@ typedef struct bsx_backend {
 	/* optional (may be NULL): bsx_markdup_batch on the backend's table of template keys; n < 0 empties the table (bsx_markdup_reset).  Without it
 	 * the host keeps the table (markdup.c). */
 	int (*markdup_batch)(void *ctx, int64_t n, const bsx_markdup_key_t *keys, uint64_t first_ordinal, uint8_t *dup_out);
+	/* optional (may be NULL; a backend that clears the struct has it NULL): the backend's depth state of the BISCUITqc coverage tables, by op:
+	 * BSX_COV_OP_BATCH (bsx_cov_batch over n jobs), BSX_COV_OP_MASK + which (bsx_cov_set_mask: n intervals at beg_end), BSX_COV_OP_TABLES
+	 * (bsx_cov_tables into out), BSX_COV_OP_RESET (bsx_cov_reset), BSX_COV_OP_QC_BATCH (qc_batch and BSX_COV_OP_BATCH over the same n jobs
+	 * from one upload: what a slice with both options calls).  Without it the host keeps the state (cov.c). */
+	int (*cov_batch)(void *ctx, int op, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len,
+	                 const int64_t *beg_end, bsx_cov_tables_t *out);
 } bsx_backend_t;
+enum { BSX_COV_OP_BATCH = 0, BSX_COV_OP_MASK = 1 /* + which: 1, 2 */, BSX_COV_OP_TABLES = 3, BSX_COV_OP_RESET = 4, BSX_COV_OP_QC_BATCH = 5 };
 /* what msw_plan says about a pair: base = its first job in res (-1: the pair is left to the host's own plan), n_c[i] = candidates of read i it
  * looked at, mask[i] = which of them have a job (bit j: candidate j), in job order: read 0's, then read 1's */
 typedef struct { int32_t base, n_c[2], pad; uint64_t mask[2]; } bsx_msw_pair_t;

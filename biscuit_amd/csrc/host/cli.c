@@ -66,6 +66,10 @@ static int usage(void)
 		"  qc        : --qc PREFIX  write the BISCUITqc tables of the records written, as `biscuit qc <ref> <bam> PREFIX` would: PREFIX_mapq_table.txt,\n"
 		"              _dup_report.txt, _strand_table.txt, _totalReadConversionRate.txt, _CpGRetentionByReadPos.txt, _CpHRetentionByReadPos.txt and,\n"
 		"              for paired input, _isize_table.txt\n"
+		"  qc-cov    : --qc-cov  with --qc PREFIX: the coverage tables of BISCUITqc over the same records, PREFIX_covdist_{all,q40}_{base,cpg}_table.txt and\n"
+		"              PREFIX_cv_table.txt (depth under the M runs of every record without 0x4; q40: MAPQ >= 40; CpGs from the reference, depth\n"
+		"              the smaller of the two bases'); one process only (refused with WORLD_SIZE > 1)\n"
+		"              --qc-topgc FILE --qc-botgc FILE  (both or neither; BED, plain or gzip) also the eight _topgc / _botgc tables\n"
 		"  markdup   : --markdup  0x400 on every record of a template (a pair, or a single read) whose ends' unclipped 5' positions, strands and YD\n"
 		"              equal those of an earlier template of the input; one process only (refused with WORLD_SIZE > 1)\n"
 		"  device    : $BSX_DEVICE selects the HIP device ordinal (default 0)\n\n");
@@ -334,9 +338,30 @@ static void bsconv_report(void)
 /* --markdup needs one table for the whole input: the tables of several devices would have to be one */
 #define MARKDUP_RANKS_MSG "--markdup marks duplicates over the whole input in one table on one device: it cannot run with WORLD_SIZE > 1"
 
+/* --qc-cov needs the depth of every position over the whole input: the histograms of several devices do not add up to it */
+#define QC_COV_RANKS_MSG "--qc-cov keeps the depth of the whole input on one device: it cannot run with WORLD_SIZE > 1"
+
 /* --qc: the tables of `biscuit qc` (src/qc.c) over this call's records; with several ranks rank 0 writes the sum (bsx_align_main_ranks_with) */
 static char g_qc_prefix[4096];
 static int g_qc_paired;
+static int qc_cov_report(void)
+{
+	bsx_cov_tables_t t;
+	int rc = bsx_process_qc_cov_tables(&t);
+	if (rc == BSX_OK) rc = bsx_cov_write(g_qc_prefix, &t);
+	if (rc != BSX_OK) fprintf(stderr, "[E::%s] writing the coverage tables failed (%s)\n", "main_align", bsx_strerror(rc));
+	bsx_cov_tables_free(&t);
+	return rc;
+}
+/* the BED file of --qc-topgc / --qc-botgc as mask `which` of this call's coverage tables */
+static int qc_cov_mask(int which, const char *path, const bsx_index_t *idx)
+{
+	int64_t n = 0, *iv = 0;
+	int rc = bsx_cov_read_bed(path, idx, &n, &iv);
+	if (rc == BSX_OK) rc = bsx_process_set_qc_cov_mask(which, n, iv);
+	free(iv);
+	return rc;
+}
 static int qc_report(void)
 {
 	bsx_qc_totals_t *t = (bsx_qc_totals_t*)malloc(sizeof(*t));
@@ -364,10 +389,12 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		{"bsconv", no_argument, 0, 1000}, {"bsconv-max-cph", required_argument, 0, 1001}, {"bsconv-max-cpa", required_argument, 0, 1002},
 		{"bsconv-max-cpc", required_argument, 0, 1003}, {"bsconv-max-cpt", required_argument, 0, 1004}, {"bsconv-max-cpy", required_argument, 0, 1005},
 		{"bsconv-max-cph-frac", required_argument, 0, 1006}, {"bsconv-max-cpy-frac", required_argument, 0, 1007},
-		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {"qc", required_argument, 0, 1010}, {"markdup", no_argument, 0, 1011}, {0, 0, 0, 0}
+		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {"qc", required_argument, 0, 1010}, {"markdup", no_argument, 0, 1011},
+		{"qc-cov", no_argument, 0, 1012}, {"qc-topgc", required_argument, 0, 1013}, {"qc-botgc", required_argument, 0, 1014}, {0, 0, 0, 0}
 	};
 	bsx_bsconv_conf_t bsconv;
-	int bsconv_on = 0, qc_on = 0, markdup_on = 0;
+	int bsconv_on = 0, qc_on = 0, markdup_on = 0, qc_cov_on = 0;
+	const char *gc_bed[2] = {0, 0};
 
 	bsx_bsconv_conf_init(&bsconv);
 	g_write_error = 0;   /* per call: a failed write of an earlier call in this process must not fail this one */
@@ -380,6 +407,8 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	while ((c = getopt_long(argc, argv, ":@:1:2:3:5:9ab:c:d:ef:g:hijk:m:pqr:s:v:w:x:y:z:A:B:CD:E:FG:H:I:J:K:L:MN:O:PQ:R:ST:U:VW:X:Y", long_opts, 0)) >= 0) {
 		if (c == 1010) { qc_on = 1; snprintf(g_qc_prefix, sizeof(g_qc_prefix), "%s", optarg); }
 		else if (c == 1011) markdup_on = 1;
+		else if (c == 1012) qc_cov_on = 1;
+		else if (c == 1013 || c == 1014) gc_bed[c - 1013] = optarg;
 		else if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
 			bsconv_on = 1;
 			if (c == 1000) bsconv.annotate = 1;
@@ -527,7 +556,12 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	bsx_opt_fill_matrices(opt);
 	if (bsconv_on) bsconv.annotate = 1;   /* a filter implies the annotation */
 	bsx_process_set_bsconv(bsconv_on ? &bsconv : 0);   /* every chunk of this call, through a stream or not; totals from zero */
+	if (qc_cov_on && !qc_on) { fprintf(stderr, "[E::%s] --qc-cov writes its tables beside those of --qc: it needs --qc PREFIX\n", "main_align"); return 1; }
+	if ((gc_bed[0] || gc_bed[1]) && !qc_cov_on) { fprintf(stderr, "[E::%s] --qc-topgc and --qc-botgc belong to --qc-cov\n", "main_align"); return 1; }
+	if ((gc_bed[0] != 0) != (gc_bed[1] != 0)) { fprintf(stderr, "[E::%s] --qc-topgc and --qc-botgc must be given together\n", "main_align"); return 1; }
+	if (qc_cov_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", QC_COV_RANKS_MSG); return 1; }
 	bsx_process_set_qc(qc_on);
+	bsx_process_set_qc_cov(qc_cov_on);
 	if (markdup_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; }
 	bsx_process_set_markdup(markdup_on);
 	if (optind >= argc) { usage(); fprintf(stderr, "Missing fai-index base\n"); return 1; }
@@ -535,6 +569,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	if (auto_alt) infer_alt(&idx->ref);
 	if (ignore_alt) for (i = 0; i < idx->ref.n_seqs; ++i) idx->ref.anns[i].is_alt = 0;
 	if (open_device) ud = 0;
+	for (i = 0; i < 2; ++i) if (gc_bed[i] && qc_cov_mask(i, gc_bed[i], idx) != BSX_OK) { rc = 1; goto cleanup; }
 	if (open_device && (rc = open_device(device, idx, &ud)) != BSX_OK) { fprintf(stderr, "[E::%s] %s\n", "main_align", bsx_strerror(rc)); ud = 0; rc = 1; goto cleanup; }
 	if (!seq1) {
 		if ((f1 = bsx_fq_open(argv[optind + 1])) == 0) { fprintf(stderr, "[E::%s] fail to open file `%s'.\n", "main_align", argv[optind + 1]); rc = 1; goto cleanup; }
@@ -732,7 +767,7 @@ loop_done:
 	if (bsconv_on && bsx_shard_world <= 1) bsconv_report();   /* (several ranks: rank 0 reports the sum, bsx_align_main_ranks_with) */
 	if (qc_on) { /* the device's counts are read while it is open; several ranks: kept for the sum */
 		g_qc_paired = (opt->flag & BSX_F_PE) ? 1 : 0;
-		if (bsx_shard_world <= 1) { if (rc == 0 && qc_report() != BSX_OK) rc = 1; }
+		if (bsx_shard_world <= 1) { if (rc == 0 && qc_report() != BSX_OK) rc = 1; if (rc == 0 && qc_cov_on && qc_cov_report() != BSX_OK) rc = 1; }
 		else if (bsx_process_qc_totals(0, 0) != BSX_OK) rc = 1;
 	}
 	if (markdup_on && bsx_verbose >= 3) {
@@ -743,6 +778,7 @@ loop_done:
 	}
 cleanup:
 	if (markdup_on) bsx_process_set_markdup(0);
+	if (qc_cov_on) bsx_process_set_qc_cov(0);
 	if (qc_on && bsx_shard_world <= 1) bsx_process_set_qc(0);
 	if (bsconv_on && bsx_shard_world <= 1) bsx_process_set_bsconv(0);
 	if (open_device && ud && g_close_device) g_close_device(ud);   /* the device this call opened: index replica, lanes, streams */
@@ -816,6 +852,7 @@ BSX_API int bsx_align_main_ranks_with(int argc, char **argv, bsx_process_fn proc
 	if (world <= 1 || bsx_emit_hook) return bsx_align_main_with(argc, argv, process, ud, open_device);   /* (a launcher with its own hook: multi_gpu.py) */
 	if (rank < 0 || rank >= world) { fprintf(stderr, "[E::%s] RANK %d of WORLD_SIZE %d\n", "main_align", rank, world); return 1; }
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 3 && strncmp("--markdup", argv[k], strlen(argv[k])) == 0) { /* (any abbreviation getopt_long takes: no other long option begins with --m) */ fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; } }   /* (before any transport is opened) */
+	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 6 && strncmp("--qc-cov", argv[k], strlen(argv[k])) == 0) { /* (--qc-c, --qc-co: what getopt_long takes for it) */ fprintf(stderr, "[E::%s] %s\n", "main_align", QC_COV_RANKS_MSG); return 1; } }
 	memset(&R, 0, sizeof(R));
 	if (id_env && *id_env) snprintf(id_path, sizeof(id_path), "%s", id_env);
 	else if (out_path && *out_path) snprintf(id_path, sizeof(id_path), "%s.ranks", out_path);

@@ -124,7 +124,7 @@ BSX_API int bsx_process_bsconv_totals(uint64_t out[8], uint64_t *n, uint64_t *n_
 }
 
 /* ------------------------------------------------------------------ BISCUITqc while aligning (qc.c): setting and totals of the process (a stream has its own) */
-static bsx_qc_state_t g_qc = {0, PTHREAD_MUTEX_INITIALIZER};
+static bsx_qc_state_t g_qc = {0, PTHREAD_MUTEX_INITIALIZER, .cov = {0, PTHREAD_MUTEX_INITIALIZER}};
 static int qc_state_totals(bsx_qc_state_t *q, bsx_qc_totals_t *out)
 {
 	int rc = bsx_qc_collect(q);
@@ -140,6 +140,17 @@ BSX_API int bsx_process_qc_totals(bsx_qc_totals_t *out, int reset)
 	if (reset) { pthread_mutex_lock(&g_qc.mu); memset(&g_qc.tot, 0, sizeof(g_qc.tot)); pthread_mutex_unlock(&g_qc.mu); }
 	return rc;
 }
+
+/* the coverage tables over the same records (cov.c): part of the QC state, set after it */
+static int qc_cov_set(bsx_qc_state_t *q, int on)
+{
+	if (on && !q->on) return BSX_E_ARG;
+	bsx_cov_state_set(&q->cov, on);
+	return BSX_OK;
+}
+BSX_API int bsx_process_set_qc_cov(int on) { return qc_cov_set(&g_qc, on); }
+BSX_API int bsx_process_set_qc_cov_mask(int which, int64_t n, const int64_t *beg_end) { return bsx_cov_state_mask(&g_qc.cov, which, n, beg_end); }
+BSX_API int bsx_process_qc_cov_tables(bsx_cov_tables_t *out) { return bsx_cov_state_tables(&g_qc.cov, out); }
 
 /* ------------------------------------------------------------------ duplicate marking while aligning (markdup.c): setting and totals of the process (a stream has its own) */
 static bsx_md_state_t g_md = BSX_MD_STATE_INIT;
@@ -1726,6 +1737,22 @@ BSX_API int bsx_stream_qc_totals(bsx_stream_t *s, bsx_qc_totals_t *out)
 	return qc_state_totals(s->qc.on ? &s->qc : &g_qc, out);
 }
 
+BSX_API int bsx_stream_set_qc_cov(bsx_stream_t *s, int on)
+{
+	if (!s || s->n_pushed) return BSX_E_ARG;
+	return qc_cov_set(&s->qc, on);
+}
+BSX_API int bsx_stream_set_qc_cov_mask(bsx_stream_t *s, int which, int64_t n, const int64_t *beg_end)
+{
+	if (!s) return BSX_E_ARG;
+	return bsx_cov_state_mask(&s->qc.cov, which, n, beg_end);
+}
+BSX_API int bsx_stream_qc_cov_tables(bsx_stream_t *s, bsx_cov_tables_t *out)
+{
+	if (!s) return BSX_E_ARG;
+	return bsx_cov_state_tables(s->qc.on ? &s->qc.cov : &g_qc.cov, out);
+}
+
 BSX_API int bsx_stream_set_markdup(bsx_stream_t *s, int on)
 {
 	if (!s || s->n_pushed) return BSX_E_ARG;
@@ -1803,5 +1830,6 @@ BSX_API void bsx_stream_close(bsx_stream_t *s)
 	if (!s) return;
 	(void)stream_drain(s);
 	bsx_md_state_end(&s->md);
+	bsx_cov_state_set(&s->qc.cov, 0);
 	free(s);
 }

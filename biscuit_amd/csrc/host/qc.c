@@ -9,8 +9,10 @@
 
 void bsx_qc_state_set(bsx_qc_state_t *q, int on)
 {
+	bsx_cov_state_set(&q->cov, 0);   /* (frees what an earlier run's state holds) */
 	memset(q, 0, sizeof(*q));
 	pthread_mutex_init(&q->mu, 0);
+	pthread_mutex_init(&q->cov.mu, 0);
 	q->on = on ? 1 : 0;
 }
 
@@ -85,6 +87,7 @@ int bsx_qc_slice(bsx_qc_state_t *q, const bsx_backend_t *be, const bsx_index_t *
 	size_t u, k, n_recs = 0, n_words = 0, nj = 0, nw = 0;
 	int rc = BSX_OK, i;
 	for (u = 0; u < n_units; ++u) { n_recs += ctx[u].qc_recs.n; n_words += ctx[u].qc_cig.n; }
+	if (q->cov.on && (rc = bsx_cov_attach(&q->cov, be, idx)) != BSX_OK) return rc;
 	if (n_recs == 0) return BSX_OK;
 	t = (bsx_qc_totals_t*)calloc(1, sizeof(*t));
 	jobs = (bsx_qc_job_t*)malloc(sizeof(*jobs) * n_recs);
@@ -104,13 +107,16 @@ int bsx_qc_slice(bsx_qc_state_t *q, const bsx_backend_t *be, const bsx_index_t *
 			++t->strandcnt[(r->flag & 0x40 ? 0 : 1) * 8 + (r->flag & 0x10 ? 1 : 0) * 4 + (int)BSX_QC_TAG(r->job.flags)];   /* bsstrand.c:154-155 */
 			jobs[nj] = r->job;
 			jobs[nj].cig_off = (uint32_t)nw + r->job.cig_off;
+			if (q->cov.on) jobs[nj].flags |= BSX_QC_COV | (r->mapq >= 40 ? BSX_QC_COV_Q40 : 0);   /* every record without 0x4 (`genomecov -ibam`); q40: `samtools view -q 40` */
 			++nj;
 		}
 		if (ctx[u].qc_cig.n) memcpy(pool + nw, ctx[u].qc_cig.a, 4 * ctx[u].qc_cig.n);
 		nw += ctx[u].qc_cig.n;
 	}
-	if (nj && be->qc_batch) rc = be->qc_batch(be->ctx, (int64_t)nj, jobs, pool, nw, 0, 0);
+	if (nj && be->qc_batch && q->cov.on && be->cov_batch) rc = be->cov_batch(be->ctx, BSX_COV_OP_QC_BATCH, (int64_t)nj, jobs, pool, nw, 0, 0);   /* one upload, k_qc and k_cov_add */
+	else if (nj && be->qc_batch) rc = be->qc_batch(be->ctx, (int64_t)nj, jobs, pool, nw, 0, 0);
 	else for (k = 0; k < nj; ++k) bsx_qc_walk_host(idx, reads, reads_len, &jobs[k], pool + jobs[k].cig_off, &t->dev);
+	if (rc == BSX_OK && q->cov.on && !(be->qc_batch && be->cov_batch)) rc = bsx_cov_slice(&q->cov, be, idx, (int64_t)nj, jobs, pool, nw);
 	if (rc == BSX_OK) {
 		pthread_mutex_lock(&q->mu);
 		counts_add(&q->tot.dev, &t->dev);

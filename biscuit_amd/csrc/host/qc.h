@@ -4,6 +4,7 @@
 
 #include <pthread.h>
 #include "pipeline.h"
+#include "cov.h"
 
 #define BSX_QC_MAX_BE 48
 typedef struct {
@@ -13,6 +14,7 @@ typedef struct {
 	/* backends whose table holds counts of this state that have not been collected yet (a device's lanes share one table) */
 	struct { int (*fn)(void*, int64_t, const bsx_qc_job_t*, const uint32_t*, size_t, bsx_qc_counts_t*, int); void *ctx; } be[BSX_QC_MAX_BE];
 	int n_be;
+	bsx_cov_state_t cov;   /* the coverage tables over the same records (cov.c): off unless set after this state was set on */
 } bsx_qc_state_t;
 
 void bsx_qc_state_set(bsx_qc_state_t *q, int on);

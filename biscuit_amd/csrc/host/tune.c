@@ -51,6 +51,8 @@ static knob_t g_knobs[] = {
 	{"msw_plan", "[0] 1: mate rescue's plan pass (which candidates need an alignment, over which window) by k_msw_plan over the lists on the device, its K5 batch run from device memory, instead of by the host's first replay pass (same SAM; measured slower, DESIGN.md section 4)", 0},
 	{"long_dedup", "[1] 0: reads with more than 32 regions are de-duplicated on the host (A/B against k_dedup_long)", 0},
 	{"markdup_slots", "[32 per key of the first batch, at least 65536] slots of the first table of template keys (--markdup), a power of two; it doubles before a batch would load it beyond one half", 0},
+	{"cov_lds_bins", "[512] depths below this are counted in a workgroup's LDS histograms by the coverage tables' last pass (--qc-cov), deeper ones in HBM directly; a power of two up to 512", 0},
+	{"cov_flush_tiles", "[524287] tests: tiles after which a workgroup of that pass adds its LDS histograms to the bins (32-bit cells: at most 2^32 / 4096 - 1)", 0},
 	{"markdup_hash_bits", "[64] tests: low bits kept of a template key's claim word (different keys then meet in one slot and take the next salt)", 0},
 };
 #define N_KNOBS ((int)(sizeof(g_knobs) / sizeof(g_knobs[0])))

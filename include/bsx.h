@@ -348,6 +348,37 @@ int bsx_qc_batch(bsx_device_t *dev, int64_t n, const bsx_qc_job_t *jobs, const u
 /* waits for the batches in flight and copies the table out; reset != 0 zeroes it */
 int bsx_qc_read(bsx_device_t *dev, bsx_qc_counts_t *out, int reset);
 
+/* BISCUITqc coverage tables (k_cov.hip): the depth of every reference position under the records written, kept on the device as a difference
+ * array over forward concatenated coordinates (l_pac + 1 entries of two signed 32-bit classes: every record, and records with MAPQ >= 40), and
+ * the twelve depth distributions scripts/QC.sh:136-421 derives from `bedtools genomecov -bga -split` and a CpG list.  The jobs are
+ * bsx_qc_job_t's: a job with BSX_QC_COV adds 1 to every column under an M run of its CIGAR (D, I, S and H cover nothing) in class `all`, and in
+ * class `q40` too when it has BSX_QC_COV_Q40; a job without BSX_QC_COV adds nothing.  k_qc ignores both bits.  The state is made (8 bytes per
+ * base, zeroed) by the first call that needs it and freed by bsx_cov_reset and bsx_device_close; BSX_E_NOMEM when it cannot be had. */
+#define BSX_QC_COV      0x80
+#define BSX_QC_COV_Q40  0x100
+#define BSX_COV_TILE    4096   /* positions a workgroup scans at a time in the final passes (k_cov.hip) */
+#define BSX_COV_N_TABLES 12
+#define BSX_COV_MASK_TOPGC 0
+#define BSX_COV_MASK_BOTGC 1
+/* table (region * 4 + class * 2 + kind): region 0 = the whole genome, 1 = the top-GC mask, 2 = the bottom-GC mask; class 0 = all, 1 = q40;
+ * kind 0 = bases, 1 = CpGs -- the order in which QC.sh writes the rows of its uniformity table.  count[d] = positions (CpGs) of depth d,
+ * n_bins = the largest `all` depth + 1 for every table there is; without both masks have_gc = 0 and tables 4..11 are empty (n_bins 0, count
+ * NULL).  A CpG is a forward C at i and G at i + 1 in one contig, neither in an N hole; its depth is min(depth[i], depth[i + 1]); it lies in
+ * a mask when either of its bases does. */
+typedef struct bsx_cov_table { uint64_t n_bins; uint64_t *count; } bsx_cov_table_t;
+typedef struct bsx_cov_tables { bsx_cov_table_t t[BSX_COV_N_TABLES]; int have_gc; } bsx_cov_tables_t;
+/* every job must lie inside the genome and the pool (fpos >= 0, fpos + reference length <= l_pac, cig_off + n_cigar <= cigar_pool_len):
+ * BSX_E_ARG otherwise, and nothing is launched.  Exact integer sums: the order of jobs and the split into batches do not matter. */
+int bsx_cov_batch(bsx_device_t *dev, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len);
+/* mask `which` (BSX_COV_MASK_*) = the union of n_intervals half-open intervals beg_end[2 i], beg_end[2 i + 1] of forward coordinates
+ * (0 <= beg <= end <= l_pac; they may overlap); it replaces the mask there was; n_intervals = 0 makes an empty mask */
+int bsx_cov_set_mask(bsx_device_t *dev, int which, int64_t n_intervals, const int64_t *beg_end);
+/* waits for the batches in flight and makes the tables; the depth state is only read: tables can be read again and more batches can follow.
+ * The arrays belong to the caller (bsx_cov_tables_free). */
+int bsx_cov_tables(bsx_device_t *dev, bsx_cov_tables_t *out);
+void bsx_cov_tables_free(bsx_cov_tables_t *t);
+int bsx_cov_reset(bsx_device_t *dev);   /* the depth state and both masks freed: all-zero depth, no masks (it waits for a batch or a tables call in flight) */
+
 /* Duplicate templates (k_markdup.hip): a table of template keys that stays on the device until bsx_markdup_reset or bsx_device_close.
  * A key is the ordered pair of the template's ends, w[0] = read 1 (or the single read), w[1] = read 2; an end that is not placed (its primary
  * record has 0x4) is 0, the second end of a single read is BSX_MD_SINGLE: a single read never equals a pair, not even one whose read 2 is not
@@ -535,6 +566,28 @@ int  bsx_process_qc_totals(bsx_qc_totals_t *out, int reset);        /* while the
 /* PREFIX_mapq_table.txt, _dup_report.txt, _strand_table.txt, _totalReadConversionRate.txt, _CpGRetentionByReadPos.txt, _CpHRetentionByReadPos.txt
  * and, with paired != 0, _isize_table.txt: the formatters of src/qc.c:29-110, byte for byte */
 int  bsx_qc_write(const char *prefix, const bsx_qc_totals_t *t, int paired);
+
+/* The BISCUITqc coverage tables while aligning (--qc-cov): with set_qc on, every record written without 0x4 -- secondary, supplementary and 0x400
+ * records too, as `bedtools genomecov -ibam` counts them; after --bsconv's filters -- goes to the depth state of the device it was aligned on
+ * (bsx_cov_batch; a backend without the seam keeps the state on the host, cov.c).  One depth state per device: one stream or one process call
+ * at a time.  set_qc_cov(1) needs set_qc(1) before it (BSX_E_ARG otherwise) and starts from all-zero depth; the masks (forward coordinates, as
+ * bsx_cov_set_mask; both or neither) are set after it and before the first push.  The tables: after bsx_stream_flush / while the device is open. */
+int  bsx_stream_set_qc_cov(bsx_stream_t *s, int on);
+int  bsx_stream_set_qc_cov_mask(bsx_stream_t *s, int which, int64_t n_intervals, const int64_t *beg_end);
+int  bsx_stream_qc_cov_tables(bsx_stream_t *s, bsx_cov_tables_t *out);
+int  bsx_process_set_qc_cov(int on);
+int  bsx_process_set_qc_cov_mask(int which, int64_t n_intervals, const int64_t *beg_end);
+int  bsx_process_qc_cov_tables(bsx_cov_tables_t *out);
+/* PREFIX_covdist_{all,q40}_{base,cpg}[_topgc|_botgc]_table.txt (the GC tables with have_gc) and PREFIX_cv_table.txt, titles and headers as
+ * scripts/QC.sh:153-415 prints them: a depth\tcount row per depth with a non-zero count, ascending; a uniformity row per table, in the
+ * script's order, where sum(count) > 0 and sum(count * depth) > 0: mu = sum(count * depth) / sum(count) from exact integer sums, sigma =
+ * sqrt(sum(count * (depth - mu)^2) / sum(count)) accumulated in double in ascending depth, and sigma / mu, each as %.6g (what awk's default
+ * output format prints for every value below 10^6) */
+int  bsx_cov_write(const char *prefix, const bsx_cov_tables_t *t);
+/* a BED file (plain or gzip; chrom start end, 0-based half-open, further columns ignored, blank lines, lines starting with '#' and lines whose first
+ * word is "track" or "browser" skipped) -> forward intervals, *beg_end malloc'd (2 * *n values).  BSX_E_IO: cannot be read; BSX_E_FORMAT: a malformed line, an
+ * interval outside its contig, a contig that is not in the index (message on stderr) */
+int  bsx_cov_read_bed(const char *path, const bsx_index_t *idx, int64_t *n, int64_t **beg_end);
 
 /* Duplicate marking while aligning (--markdup).  A template is one unit of the input, a pair or a single read; its ordinal is its 0-based index
  * in the input of the stream (or of the process) over all chunks.  Each end's primary record is the one with neither 0x100 nor 0x800; the
