@@ -1,6 +1,10 @@
 // ext_dp.hpp -- the wavefront-wide ksw_extend2 (lib/aln/ksw.c:380-479) as a device function shared by
 // k_extend (one job per wave) and k_regions (the chain->region state machine runs it inline).
 // H/E/qb point to this wave's LDS: H,E >= qlen+2 int32 each, qb >= qlen bytes.
+// Forms in this file: ext_dp (rows in LDS, any length), ext_dp_reg (rows in registers, 32-bit, a slot of 64 columns per register set: queries up
+// to 255 bases), ext_dp_win (a register window that follows the band: queries of any length).  ext_pk.hpp has the fourth, ext_dp_pk: the rows of
+// ext_dp_reg with two columns per lane in packed 16-bit, which the region kernels run instead of ext_dp_reg<2> and <4> when the scoring options
+// keep every intermediate inside 16 bits (ext_pk_bound.h; the launchers decide once per launch, the 32-bit forms here stay for the others).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dev_common.hpp"

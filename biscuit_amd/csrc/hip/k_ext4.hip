@@ -16,6 +16,9 @@
 //              is wave-uniform: band limits, scores and row counters are per-lane values equal across a job's 16 lanes, so four jobs
 //              in different rows of different bands advance with every trip, and the work between extensions (set-up, results, the
 //              next job) waits until two rows need it or nothing else is going on
+// (The rows here are 32-bit, sixteen columns per slot.  The wavefront-per-extension rows of the region kernels have a packed 16-bit form with two
+// columns per lane, ext_pk.hpp; the same layout for this kernel -- columns 32 c + l and 32 c + 16 + l in the halves of a register, NCQ 10 -> 5 --
+// has not been built: the scan cannot share its DPP steps with a packed maximum, so a packed slot saves less here than there)
 // k_c2r then runs the reference's loop and takes a chain's extension from the record (RgXExt) when the seed it reaches is the one
 // extended here; everything else (later seeds of a chain, the backup list, queries beyond this kernel's slots) it extends inline.
 #include <hip/hip_runtime.h>

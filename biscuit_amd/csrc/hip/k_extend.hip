@@ -14,6 +14,7 @@
 #include "wave.hpp"
 #include "kernels.h"
 #include "ext_dp.hpp"
+#include "ext_pk.hpp"
 
 template <int NC>
 __global__ void __launch_bounds__(256)
@@ -89,4 +90,31 @@ void launch_extwin_batch(hipStream_t st, int n_cu, const DevIndex &ix, const Dev
 	long long blocks = (n + 3) / 4;
 	if (blocks > (long long)n_cu * 8) blocks = (long long)n_cu * 8;
 	hipLaunchKernelGGL(k_extend_win, dim3((unsigned)(blocks > 0 ? blocks : 1)), dim3(256), 0, st, ix, sc, reads, jobs, n, res);
+}
+
+// tests: plain jobs of up to 255 query bases through the packed 16-bit row (ext_dp_pk, ext_pk.hpp: what the region kernels extend with when the
+// scoring options allow it) or, PK false, through the 32-bit row those kernels keep for the other options (ext_dp_reg), a wavefront per job.
+// The caller has checked ext_pk_exact() over the batch; a longer query is answered X4_DECLINED
+template <bool PK>
+__global__ void __launch_bounds__(256)
+k_extend_pk(DevIndex ix, DevScoring sc, const uint8_t *reads, const bsx_ext_job_t *jobs, long long n, bsx_ext_res_t *res)
+{
+	const int lane = wave_lane();
+	const int waves_per_block = blockDim.x >> 6, wave = threadIdx.x >> 6;
+	for (long long jj = (long long)blockIdx.x * waves_per_block + wave; jj < n; jj += (long long)gridDim.x * waves_per_block) {
+		const bsx_ext_job_t J = jobs[jj];
+		bsx_ext_res_t r;
+		if (J.qlen > EXT_PK_QMAX) { r.score = X4_DECLINED; r.qle = r.tle = r.gtle = r.gscore = r.max_off = 0; }
+		else if (!PK) r = ext_dp_reg<4>(ix, sc, reads, J, lane);
+		else if (J.qlen < 128) r = ext_dp_pk<1>(ix, sc, reads, J, lane);
+		else r = ext_dp_pk<2>(ix, sc, reads, J, lane);
+		if (lane == 0) res[jj] = r;
+	}
+}
+void launch_extpk_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t *jobs, bsx_ext_res_t *res, long long n, bool packed)
+{
+	long long blocks = (n + 3) / 4;
+	if (blocks > (long long)n_cu * 8) blocks = (long long)n_cu * 8;
+	if (packed) hipLaunchKernelGGL(k_extend_pk<true>, dim3((unsigned)(blocks > 0 ? blocks : 1)), dim3(256), 0, st, ix, sc, reads, jobs, n, res);
+	else hipLaunchKernelGGL(k_extend_pk<false>, dim3((unsigned)(blocks > 0 ? blocks : 1)), dim3(256), 0, st, ix, sc, reads, jobs, n, res);
 }

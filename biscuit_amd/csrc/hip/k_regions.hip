@@ -20,6 +20,7 @@
 #include "kernels.h"
 #include "tune.h"
 #include "ext_dp.hpp"
+#include "ext_pk.hpp"
 #include "rgx.hpp"
 
 #define RG_QCAP 256
@@ -452,7 +453,7 @@ __device__ int rg_export(Store &S, int t, int tot, float frac_rep, const RgXPool
 //   1 seeding overflowed   9 read longer than RG_QCAP or long enough for the seed-SW filter (memchain.c:544)   8 intervals > ICAP
 //   2 occurrences > SCAP or an interval beyond max_occ      3 chains > CCAP      4 two chains start at the same position
 //   6 regions > RCAP      10 an over-represented interval has to be walked past max_occ (memchain.c:325-326)
-template <typename Store, bool SPLIT = false, typename DP = RgDp>
+template <typename Store, bool SPLIT = false, typename DP = RgDp, bool PK = false>   // PK: extension rows of 64 columns and more in packed 16-bit (ext_pk.hpp); the launcher has checked ext_pk_exact_reads()
 __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads,
                        int l_query, int parent, uint32_t qoff, const DevIntv *src, int n_iv, const unsigned long long *posl, int lane,
                        unsigned long long *counters, const int *gap, const long long *ctg, const RgXPool *X = nullptr, int task_id = 0,
@@ -1228,6 +1229,10 @@ __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc
 						// most extensions of a 150 bp read are shorter than a wavefront is wide: one register entry per lane then,
 						// and none of the per-chunk band tests and carries of the wider form
 						if (J.qlen < 64) res = ext_dp_reg<1>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
+						else if constexpr (PK) { // two columns per lane: one packed slot up to 127 query bases, two up to 255
+							if (J.qlen < 128) res = ext_dp_pk<1>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
+							else res = ext_dp_pk<2>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
+						}
 						else if (J.qlen < 128) res = ext_dp_reg<2>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
 						else res = ext_dp_reg<RG_NC>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);   // qlen <= l_query - 1 <= 255: fits the 256 register entries
 						res.score = uni(res.score); res.qle = uni(res.qle); res.tle = uni(res.tle); res.gtle = uni(res.gtle);
@@ -1235,6 +1240,7 @@ __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc
 						R.score = res.score;
 						RG_STAGE(7);
 						++pf_ext; pf_rows += (unsigned int)(res.tle > res.gtle ? res.tle : res.gtle);
+						if (P.prof && J.qlen >= 64) RG_PF_ADD(D, 15, (unsigned long long)(res.tle > res.gtle ? res.tle : res.gtle) << (J.qlen >= 128 ? 32 : 0));   // rows by query class: [64, 128) | 128 and more
 						if (R.score == prev || res.max_off < (aw >> 1) + (aw >> 2)) break;
 					}
 					const int local = res.gscore <= 0 || res.gscore <= R.score - clip;
@@ -1347,7 +1353,7 @@ typedef RgC2rHT<RG_QCAP, RG_WIN, 1024, 1024> RgC2rH;   // 27 KB of LDS: five wor
 typedef RgC2rHT<RG_QCAP_LONG, 1536, 1024, 1024> RgC2rHL;   // reads up to a kilobase: what k_c2r<RgC2rL> declines (64 regions, 256 seeds a list) -- chained on the host until round 6
 typedef RgC2rT<RG_QCAP, RG_WIN, 256, 256> RgC2rB;   // reads inside repeat families: up to 256 regions of a strand search, 256 seeds of a chain (22 KB: seven waves per CU); for what k_c2r<RgC2r> declines   // reads up to a kilobase: a chain's window is the read plus its two gaps, a true chain has a few hundred seeds
 
-template <typename WT>
+template <bool PK = false, typename WT>   // PK: as in rg_task (tables for reads of up to 256 bases only)
 __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, int l_query, int parent, uint32_t qoff,
                       const RgXHdr *H, int lane, unsigned long long *counters, const int *gap, const long long *ctg)
 {
@@ -1515,6 +1521,10 @@ __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const Reg
 						if (P.prof) { const long long now_ = (long long)__builtin_readcyclecounter(); RG_PF_ADD(W, 6, now_ - pf_t); pf_t = now_; }
 						// rows in registers, 64 entries per lane slot: as few slots as the query needs (a row's cost grows with them)
 						if (J.qlen < 64) res = ext_dp_reg<1>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
+						else if constexpr (PK && WT::QCAP <= 256) {
+							if (J.qlen < 128) res = ext_dp_pk<1>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
+							else res = ext_dp_pk<2>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
+						}
 						else if (J.qlen < 128) res = ext_dp_reg<2>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
 						else if (WT::QCAP <= 256 || J.qlen < 256) res = ext_dp_reg<RG_NC>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
 						else if (P.ext_win && 2 * J.w + 1 <= 256 && (long long)J.h0 + (long long)J.qlen * (parent ? sc.mx_ct : sc.mx_ga) < (1 << 21))
@@ -1526,6 +1536,7 @@ __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const Reg
 						R.score = res.score;
 						if (P.prof) { const long long now_ = (long long)__builtin_readcyclecounter(); RG_PF_ADD(W, 7, now_ - pf_t); pf_t = now_; }
 						++pf_ext; pf_rows += (unsigned int)(res.tle > res.gtle ? res.tle : res.gtle);
+						if (P.prof && J.qlen >= 64) RG_PF_ADD(W, 15, (unsigned long long)(res.tle > res.gtle ? res.tle : res.gtle) << (J.qlen >= 128 ? 32 : 0));
 						if (R.score == prev || res.max_off < (aw >> 1) + (aw >> 2)) break;
 					}
 					const int local = res.gscore <= 0 || res.gscore <= R.score - clip;
@@ -1930,7 +1941,7 @@ k_seedsw_apply(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, co
 #ifndef C2R_WPB
 #define C2R_WPB 1    // waves per workgroup (a workgroup's slots come back when its last wave ends)
 #endif
-template <typename WT, int OCC>
+template <typename WT, int OCC, bool PK = false>
 __global__ void __launch_bounds__(64 * C2R_WPB, OCC)
 k_c2r(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const bsx_seed_task_t *tasks, RgXPool X,
       bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
@@ -1964,7 +1975,7 @@ k_c2r(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const bsx_s
 		const int l_query = uni(tasks[t].len), parent = uni(tasks[t].parent);
 		const uint32_t qoff = (uint32_t)uni((int)tasks[t].qoff);
 		const RgXHdr *H = (const RgXHdr*)(X.base + uni64(X.xoff[t]));
-		int status = rg_c2r(W, ix, sc, P, reads, l_query, parent, qoff, H, lane, counters, gap_tab, ctg_tab);
+		int status = rg_c2r<PK>(W, ix, sc, P, reads, l_query, parent, qoff, H, lane, counters, gap_tab, ctg_tab);
 		WAVE_SYNC();
 		if constexpr (WT::HBM) { // publish: hundreds of regions, all lanes copy
 			const int nr = status ? 0 : uni(W.n_regs);
@@ -2076,7 +2087,7 @@ k_regions(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const b
 
 // second and third tier: the same code over per-wave tables in HBM, for the strand searches of repeat-rich reads.
 // `list` names the tasks (null: 0..*count-1); what this tier declines for table size goes on next_list.
-template <typename Store, bool XSPLIT, typename DPT>
+template <typename Store, bool XSPLIT, typename DPT, bool PK = false>
 __global__ void __launch_bounds__(256, 3)
 k_regions_slab(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const bsx_seed_task_t *tasks,
                const DevIntv *seeds_dense, const long long *task_off, const int *task_n,
@@ -2111,7 +2122,7 @@ k_regions_slab(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, co
 		// status 10: an over-represented interval has to be walked past its first max_occ occurrences; again with eight times as many of it, ...
 		int bi[4], bl[4], nb = 0, status;
 		for (;;) {
-			status = rg_task<Store, XSPLIT, DPT>(S, D, ix, sc, P, reads, l_query, parent, qoff, seeds_dense + uni64(task_off[t]), n_iv, po >= 0 ? pos + po : nullptr, lane, counters, gap_tab, ctg_tab, &X, t, nb, bi, bl);
+			status = rg_task<Store, XSPLIT, DPT, PK>(S, D, ix, sc, P, reads, l_query, parent, qoff, seeds_dense + uni64(task_off[t]), n_iv, po >= 0 ? pos + po : nullptr, lane, counters, gap_tab, ctg_tab, &X, t, nb, bi, bl);
 			if (status != 10 || !Store::NODES || !P.walk_on) break;
 			WAVE_SYNC();
 			const int iv = uni(S.boost_iv);
@@ -2357,7 +2368,12 @@ void launch_c2r(hipStream_t st, int grid, const RgLaunch &G, const RgXPoolArg &X
 {
 	RgXPool X = rgx_pool(&XA);
 	// the forms with their tables in LDS: `grid` counts groups of four waves; in HBM: workgroups, with c2r_hbm_slab_bytes() of `slab` each
-#define RG_C2R_(TAB, OCC, GRID, SLAB) hipLaunchKernelGGL((k_c2r<TAB, OCC>), dim3(GRID), dim3(64 * C2R_WPB), 0, st, RG_COMMON_, X, RG_OUT_, cursor, next_list, next_count, G.counters, quota, (unsigned char*)(SLAB))
+#define RG_C2R_(TAB, OCC, GRID, SLAB, ...) hipLaunchKernelGGL((k_c2r<TAB, OCC, ##__VA_ARGS__>), dim3(GRID), dim3(64 * C2R_WPB), 0, st, RG_COMMON_, X, RG_OUT_, cursor, next_list, next_count, G.counters, quota, (unsigned char*)(SLAB))
+	// (G.ext_pk: the instantiations whose extension rows are packed 16-bit; the forms for long reads have none)
+	if (G.ext_pk && form == RG_C2R_H) RG_C2R_(RgC2rH, 2, grid, slab, true);
+	else if (G.ext_pk && form == RG_C2R_B) RG_C2R_(RgC2rB, 2, grid * (4 / C2R_WPB), nullptr, true);
+	else if (G.ext_pk && form == RG_C2R) RG_C2R_(RgC2r, 4, grid * (4 / C2R_WPB), nullptr, true);
+	else
 	switch (form) {
 	case RG_C2R_HL: RG_C2R_(RgC2rHL, 1, grid, slab); break;
 	case RG_C2R_H:  RG_C2R_(RgC2rH, 2, grid, slab); break;
@@ -2372,11 +2388,13 @@ void launch_regions_slab(hipStream_t st, int tier, int grid, const RgLaunch &G, 
 {
 	RgXPool X = rgx_pool(XA);
 	// XA given: the tier stops after the chain filter and exports (chunks with long reads or an active seed-SW filter)
-#define RG_SLAB_(TAB, EXPORTS, DP) hipLaunchKernelGGL((k_regions_slab<TAB, EXPORTS, DP>), dim3(grid), dim3(256), 0, st, RG_COMMON_, RG_LISTS_, \
+#define RG_SLAB_(TAB, EXPORTS, DP, ...) hipLaunchKernelGGL((k_regions_slab<TAB, EXPORTS, DP, ##__VA_ARGS__>), dim3(grid), dim3(256), 0, st, RG_COMMON_, RG_LISTS_, \
 	                                              RG_OUT_, list, count, cursor, (TAB*)slabs, next_list, next_count, RG_POS_, X)
 	if (tier == 2 && XA) RG_SLAB_(RgBig, true, RgDpLiteL);
+	else if (tier == 2 && G.ext_pk) RG_SLAB_(RgBig, false, RgDp, true);
 	else if (tier == 2) RG_SLAB_(RgBig, false, RgDp);
 	else if (XA) RG_SLAB_(RgHuge, true, RgDpLiteL);
+	else if (G.ext_pk) RG_SLAB_(RgHuge, false, RgDp, true);
 	else RG_SLAB_(RgHuge, false, RgDp);
 #undef RG_SLAB_
 }

@@ -80,6 +80,9 @@ void launch_md_rehash(hipStream_t st, const MdSlot *old, unsigned long long n_ol
 #define X4_DECLINED (-0x7fffffff)
 // tests: plain jobs through ext_dp_win (ext_dp.hpp: rows in a register window that follows the band, queries of any length), a wavefront per job
 void launch_extwin_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t *jobs, bsx_ext_res_t *res, long long n);
+// tests: plain jobs of up to 255 query bases through ext_dp_pk (ext_pk.hpp: two columns per lane in packed 16-bit) when `packed`, a wavefront per
+// job; else through the 32-bit row the region kernels keep for scoring options beyond ext_pk_exact() (ext_pk_bound.h)
+void launch_extpk_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t *jobs, bsx_ext_res_t *res, long long n, bool packed);
 int x4_max_query(int ncq);
 size_t x4_job_bytes(void);
 struct RgXPoolArg; struct RgLaunch;
@@ -108,6 +111,7 @@ struct RgLaunch {
 	long long *reg_off; int *reg_n;
 	unsigned long long *counters;            // the lane's counter block (ctr_layout.hpp)
 	long long *pos_off; unsigned long long *pos;   // launch_occ fills them, the region kernels read them
+	bool ext_pk = false;                     // extension rows in packed 16-bit (ext_pk.hpp): the scoring options pass ext_pk_exact_reads()
 };
 void launch_regions(hipStream_t st, int grid, const RgLaunch &G, unsigned int *task_cursor, int *retry_list, unsigned int *retry_count, int quota,
                     const unsigned char *cls, const RgXPoolArg &X, bool long_reads = false);   // cls[t] != 0: not for this tier (launch_occ)

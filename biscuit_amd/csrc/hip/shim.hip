@@ -11,10 +11,12 @@
 #include <algorithm>
 #include <vector>
 #include <mutex>
+#include <atomic>
 #include "devbuf.hpp"
 #include "kernels.h"
 #include "index_build.h"
 #include "tune.h"
+#include "ext_pk_bound.h"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[bsx-hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return BSX_E_NODEVICE; } } while (0)
 
@@ -573,6 +575,25 @@ extern "C" BSX_API int bsx_device_seed_passes(bsx_device_t *d, uint64_t w[6], do
 	return BSX_OK;
 }
 
+// Which extension rows the launches took: the packed 16-bit ones (ext_pk.hpp) where the scoring options and the batch pass ext_pk_exact()
+// (ext_pk_bound.h), else the 32-bit ones.  The setting ext_pk=0 forces the 32-bit forms.
+static std::atomic<uint64_t> g_ext_forms[2];
+static bool ext_pk_wanted(void) { return bsx_tune_long("ext_pk", 1) != 0; }
+static bool ext_pk_scoring(const DevScoring &sc, long long hmax, int qmax, bool per_read)
+{
+	int mn = 0;
+	for (int k = 0; k < 25; ++k) mn = std::min<int>(mn, std::min<int>(sc.ctmat[k], sc.gamat[k]));
+	const int mx = std::max(sc.mx_ct, sc.mx_ga);
+	if (per_read) return ext_pk_exact_reads(sc.a, mx, mn, sc.o_del, sc.e_del, sc.o_ins, sc.e_ins, qmax);
+	return ext_pk_exact(mx, mn, sc.o_del, sc.e_del, sc.o_ins, sc.e_ins, hmax, qmax);
+}
+extern "C" BSX_API int bsx_ext_forms(uint64_t c[2], int reset)
+{
+	if (!c) return BSX_E_ARG;
+	for (int k = 0; k < 2; ++k) { c[k] = g_ext_forms[k].load(); if (reset) g_ext_forms[k].store(0); }
+	return BSX_OK;
+}
+
 extern "C" BSX_API int bsx_device_region_work(bsx_device_t *d, uint64_t w[5], int reset)
 {
 	if (!d || !w) return BSX_E_ARG;
@@ -926,6 +947,9 @@ static int rg_plan(RgBatch &B)
 	G.seeds_dense = (const DevIntv*)L.out.p;
 	G.out = (bsx_region_t*)L.regs.p; G.out_cap = B.regs_cap; G.out_cursor = &SH->region_cursor;
 	G.counters = dev_counters(L); G.pos = (unsigned long long*)L.pos.p;
+	// once per chunk: reads of at most 256 bases under scoring options whose extension rows fit 16 bits take the packed instantiations
+	G.ext_pk = !B.long_reads && ext_pk_wanted() && ext_pk_scoring(L.sc, 0, B.max_len, true);
+	++g_ext_forms[G.ext_pk ? 0 : 1];
 	M.X.base = (unsigned char*)L.xpool.p; M.X.cap = B.xcap; M.X.cursor = &SH->xpool_cursor; M.X.xcount = &M.c->front.x_count;
 	M.X.ext = B.use_x4 && !B.export_all ? 1 : 0;
 	return BSX_OK;
@@ -1061,6 +1085,8 @@ static int tier_mark(RgBatch &B, const TierSeq &S, const char *name)
 	HIPCHK(hipMemcpy(ds, ctr + CTR_HANDON, sizeof(ds), hipMemcpyDeviceToHost)); HIPCHK(hipMemset(ctr + CTR_HANDON, 0, sizeof(ds)));
 	if (ds[2] | ds[3] | ds[4] | ds[6] | ds[8] | ds[10]) fprintf(stderr, "[M::regions_batch] %s hands on: %llu for their intervals, %llu for their occurrences (or a list too long), %llu chains, %llu tied chain starts, %llu regions, %llu an interval to be walked further\n", name, ds[8], ds[2], ds[3], ds[4], ds[6], ds[10]);
 	if (pf[11]) fprintf(stderr, "[M::regions_batch] %s: seed loops: %llu seeds reached, %llu skipped as contained, %llu took the extension made ahead, %llu extended in place (%llu extensions, %llu rows)\n", name, pf[11], pf[12], pf[13], pf[14], pf[8], pf[9]);
+	if (pf[9]) fprintf(stderr, "[M::regions_batch] %s: extension rows in place by query length: %llu below 64 | %llu of 64..127 | %llu of 128 and more\n", name,
+	                   pf[9] - (pf[15] & 0xffffffffull) - (pf[15] >> 32), pf[15] & 0xffffffffull, pf[15] >> 32);
 	double tot = 0; for (int k = 0; k < 8; ++k) tot += (double)pf[k];
 	if (tot > 0) fprintf(stderr, "[M::regions_batch] %s: intervals %.1f%% occurrences %.1f%% chaining %.1f%% weights+order %.1f%% sort %.1f%% filter %.1f%% prologues+seed tests %.1f%% extension %.1f%% of %.0f M wave cycles\n", name,
 	                     100 * pf[0] / tot, 100 * pf[1] / tot, 100 * pf[2] / tot, 100 * pf[3] / tot, 100 * pf[4] / tot, 100 * pf[5] / tot, 100 * pf[6] / tot, 100 * pf[7] / tot, tot * 1e-6);
@@ -1573,6 +1599,20 @@ static int lane_extend_batch(bsx_device_t *d, int lane, int64_t n, const bsx_ext
 		int rc, max_q = 0;
 		for (int64_t i = 0; i < n; ++i) max_q = std::max(max_q, jobs[i].qlen);
 		if ((max_q > x4_max_query(16) && bsx_tune_long("ext4", 0) != 3) || n > 0x7fffffff) return BSX_E_ARG;
+		if (bsx_tune_long("ext4", 0) == 4) { // ... or the wavefront-per-job form of the region kernels' inline extensions: packed 16-bit rows (ext_dp_pk) when the batch passes the guard, else 32-bit
+			long long hmax = 0;
+			for (int64_t i = 0; i < n; ++i) hmax = std::max(hmax, (long long)jobs[i].h0 + (long long)jobs[i].qlen * (jobs[i].parent ? L.sc.mx_ct : L.sc.mx_ga));
+			const bool packed = ext_pk_wanted() && ext_pk_scoring(L.sc, hmax, max_q, false);
+			if ((rc = L.jobs.reserve((size_t)n * sizeof(bsx_ext_job_t))) != BSX_OK) return rc;
+			if ((rc = L.res.reserve((size_t)n * sizeof(bsx_ext_res_t))) != BSX_OK) return rc;
+			HIPCHK(hipMemcpyAsync(L.jobs.p, jobs, (size_t)n * sizeof(bsx_ext_job_t), hipMemcpyHostToDevice, L.st));
+			launch_extpk_batch(L.st, d->n_cu, d->ix, L.sc, (const uint8_t*)L.reads.p, (const bsx_ext_job_t*)L.jobs.p, (bsx_ext_res_t*)L.res.p, (long long)n, packed);
+			++g_ext_forms[packed ? 0 : 1];
+			HIPCHK(hipGetLastError());
+			D2H(L.st, res, L.res.p, (size_t)n * sizeof(bsx_ext_res_t));
+			for (int64_t i = 0; i < n; ++i) if (res[i].score == X4_DECLINED) return BSX_E_ARG;
+			return BSX_OK;
+		}
 		if ((rc = L.jobs.reserve((size_t)n * sizeof(bsx_ext_job_t))) != BSX_OK) return rc;
 		if ((rc = L.res.reserve((size_t)n * sizeof(bsx_ext_res_t))) != BSX_OK) return rc;
 		if ((rc = L.aux.reserve(64)) != BSX_OK) return rc;

@@ -450,6 +450,9 @@ void bsx_chunk_slice_offset(int64_t first);
  * w[0] strand searches, w[1] SA intervals read (32 B each), w[2] seed occurrences whose position was looked up (8 B each),
  * w[3] alignment regions written (56 B each), w[4] read bases of the strand searches -- the terms of the family's algorithmic bytes */
 int bsx_device_region_work(bsx_device_t *dev, uint64_t w[5], int reset);
+/* launches since the last reset whose extension rows were c[0] packed 16-bit (two columns per lane; the scoring options keep every
+ * intermediate inside 16 bits) / c[1] 32-bit: a chunk of bsx_regions_batch or a bsx_extend_batch under the setting ext4=4 counts once */
+int bsx_ext_forms(uint64_t c[2], int reset);
 /* the seeding kernel's table of k-mer intervals: entries read since the last reset, depth K of the resident table (0: none) */
 int bsx_device_seed_table(bsx_device_t *dev, uint64_t *lookups, int *depth, int reset);
 /* average GPU time (ms, HIP events on the launch stream) and launch count of each kernel since
