@@ -88,7 +88,7 @@ class GlbTag(C.Structure):
 
 class Backend(C.Structure):  # bsx_backend_t (csrc/host/bsx_core.h)
     _fields_ = [("ctx", C.c_void_p), ("name", C.c_char_p)] + [(n, C.c_void_p) for n in
-                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p)]
+                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p), ("sort_batch", C.c_void_p)]
 
 
 class GlbCtx(C.Structure):  # bsx_glb_ctx_t: [strand hypothesis][A, C, G, T, N context][retained, converted]
@@ -128,6 +128,15 @@ class MarkdupKey(C.Structure):  # bsx_markdup_key_t: w[0] = read 1 (or the singl
 
 
 MD_PLACED, MD_REVERSE, MD_YD, MD_U5_BIAS, MD_SINGLE = 1 << 63, 1 << 62, 1 << 61, 1 << 32, 1
+
+
+SORT_TILE = 2048      # BSX_SORT_TILE: the keys of one workgroup of k_sort.hip; up to that many are sorted in LDS by a single workgroup
+SORT_NO_RANK = 0xffffffff
+
+
+def sort_key(rank, pos, rev):
+    """BSX_SORT_KEY"""
+    return (int(rank) << 32) | (int(pos) << 1) | (1 if rev else 0)
 
 
 class MarkdupTotals(C.Structure):  # bsx_markdup_totals_t

@@ -3,6 +3,8 @@ import ctypes as C
 import numpy as np
 from . import _lib as B
 
+SORT_TILE = B.SORT_TILE      # BSX_SORT_TILE (include/bsx.h): the sizes around it are where Device.sort_run changes kernels
+
 SEED_DT = np.dtype(B.SeedTask)
 SA_DT = np.dtype(B.SaJob)
 EXT_DT = np.dtype(B.ExtJob)
@@ -340,6 +342,43 @@ class Device(Batches):
         f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         B.check(f(self.h, C.byref(n), C.byref(u)), "bsx_markdup_table_info")
         return n.value, u.value
+
+    def sort_run(self, keys):
+        """bsx_sort_run: keys = uint64[n] (_lib.sort_key) -> uint32[n], perm[i] = index of the i-th key in stable order; the sorted keys stay on the
+        device as the next run"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(-1)
+        perm = np.zeros(len(keys), np.uint32)
+        f = B.lib().bsx_sort_run
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        B.check(f(self.h, len(keys), _p(keys) if len(keys) else None, _p(perm) if len(keys) else None), "bsx_sort_run")
+        return perm
+
+    def sort_schedule(self):
+        """bsx_sort_schedule -> uint32[total], the run every position of the stable sort of all retained keys (runs concatenated in run order) comes from"""
+        n, out = C.c_int64(0), C.c_void_p()
+        f = B.lib().bsx_sort_schedule
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]
+        B.check(f(self.h, C.byref(n), C.byref(out)), "bsx_sort_schedule")
+        if not out.value:
+            return np.zeros(0, np.uint32)
+        try:
+            return np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint32)), shape=(n.value,)).copy()
+        finally:
+            _libc_free(out)
+
+    def sort_info(self):
+        """bsx_sort_info -> (runs, keys) retained on the device"""
+        r, k = C.c_uint64(), C.c_uint64()
+        f = B.lib().bsx_sort_info
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        B.check(f(self.h, C.byref(r), C.byref(k)), "bsx_sort_info")
+        return r.value, k.value
+
+    def sort_reset(self):
+        """bsx_sort_reset: every retained run freed"""
+        f = B.lib().bsx_sort_reset
+        f.argtypes = [C.c_void_p]
+        B.check(f(self.h), "bsx_sort_reset")
 
     def counters(self, reset=False):
         c = (C.c_uint64 * 4)()

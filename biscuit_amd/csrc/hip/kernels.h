@@ -72,6 +72,17 @@ void launch_md_round(hipStream_t st, MdSlot *T, unsigned long long n_slots, cons
                      unsigned salt, int bits, uint8_t *res, unsigned long long *slot, unsigned long long *ctr);
 // every taken slot of `old` into T (initialised, at least twice the slots); ctr[2] += slots that found no room (none)
 void launch_md_rehash(hipStream_t st, const MdSlot *old, unsigned long long n_old, MdSlot *T, unsigned long long n_slots, unsigned long long *ctr);
+// k_sort.hip: the stable radix sort of bsx_sort_run / bsx_sort_schedule, 8 bits a pass (n below 2^31).  launch_sort_bits: *bits (zeroed before) |=
+// key ^ keys[0] over all keys.  launch_sort_pass: one pass on the byte at `shift` from (keys_in, pay_in) to (keys_out, pay_out); pay_in == nullptr:
+// the payload is the key's index; counts: 256 x sort_n_tiles(n) words, btot: sort_n_scan_blocks(n) words.  launch_sort_small: n <= BSX_SORT_TILE,
+// every pass that moves something, in one workgroup's LDS.
+#define SORT_SCAN_BLOCK 2048
+size_t sort_n_tiles(long long n);
+size_t sort_n_scan_blocks(long long n);
+void launch_sort_bits(hipStream_t st, const unsigned long long *keys, long long n, unsigned long long *bits);
+void launch_sort_pass(hipStream_t st, const unsigned long long *keys_in, const unsigned int *pay_in, unsigned long long *keys_out, unsigned int *pay_out,
+                      long long n, int shift, unsigned int *counts, unsigned int *btot);
+void launch_sort_small(hipStream_t st, const unsigned long long *keys_in, const unsigned int *pay_in, unsigned long long *keys_out, unsigned int *pay_out, long long n);
 // K4 four to a wavefront (k_ext4.hip): a row of 16 lanes per job, persistent rows taking jobs off *cursor (zero at launch).
 // launch_x4: the extensions of the best seed of every chain the tiers exported (records with has_ext), written into the records ahead of
 // launch_c2r; jobs = room for job_cap jobs of x4_job_bytes(), ctr32[0..3]: job counts and cursor (zeroed by the call).

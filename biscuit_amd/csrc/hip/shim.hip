@@ -91,6 +91,12 @@ struct bsx_device {
 	// the table of template keys (k_markdup.hip): made by the first bsx_markdup_batch, doubled as it fills, kept until bsx_markdup_reset / close
 	MdSlot *md = nullptr; uint64_t md_slots = 0, md_used = 0;
 	std::mutex md_mu;
+	// the sorted runs of record keys (k_sort.hip): one block per bsx_sort_run, kept until bsx_sort_reset / close; the sort's own stream (the writer
+	// thread sorts a finished chunk while the lanes align the next ones) and its working buffers
+	std::vector<std::pair<uint64_t*, int64_t>> sort_runs;
+	hipStream_t sort_st = nullptr;
+	DevBuf sort_k[2], sort_p[2], sort_counts, sort_btot;
+	std::mutex sort_mu;
 	Lane lane[BSX_LANES];   // scoring matrices and penalties are per lane (Lane::sc): chunks with different options may be in flight together
 	// Front halves of consecutive chunks are chained stage by stage (the seeding launch of chunk k+1 waits for that of chunk k, the
 	// region launches likewise): four chunks that share the device evenly all finish at the same moment, and the device then idles
@@ -185,6 +191,15 @@ static void cov_release(bsx_device *d)
 	for (int w = 0; w < 2; ++w) if (d->cov_mask[w]) { (void)hipFree(d->cov_mask[w]); d->cov_mask[w] = nullptr; }
 }
 
+static void sort_release(bsx_device *d)
+{
+	for (auto &r : d->sort_runs) (void)hipFree(r.first);
+	d->sort_runs.clear();
+	for (int i = 0; i < 2; ++i) { d->sort_k[i].release(); d->sort_p[i].release(); }
+	d->sort_counts.release(); d->sort_btot.release();
+	if (d->sort_st) { (void)hipStreamDestroy(d->sort_st); d->sort_st = nullptr; }
+}
+
 extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 {
 	if (!d) return;
@@ -194,6 +209,7 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 	d->pac.release(); d->ctg.release(); d->holes.release(); d->qc.release();
 	if (d->md) { (void)hipFree(d->md); d->md = nullptr; d->md_slots = d->md_used = 0; }
 	cov_release(d);
+	sort_release(d);
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
 		L.reads.release(); L.qpack.release(); L.gath.release(); L.jobs.release(); L.res.release(); L.scratch.release(); L.scratch2.release(); L.out.release(); L.aux.release(); L.pool.release();
@@ -2340,6 +2356,129 @@ extern "C" BSX_API int bsx_markdup_table_info(bsx_device_t *d, uint64_t *n_slots
 	return BSX_OK;
 }
 
+// ---- coordinate order (k_sort.hip) ----
+// The passes over (sort_k[0], sort_p[0]) -- n keys; iota: the payload is the key's index and sort_p[0] holds nothing yet.  *cur = the buffer pair the
+// sorted keys and their payloads are in; *have_pay = 0 only when iota and every key was equal (nothing ran: the payload is the identity).
+static int sort_passes(bsx_device *d, int64_t n, bool iota, int *cur, int *have_pay, int *n_passes)
+{
+	hipStream_t st = d->sort_st;
+	uint64_t *k[2] = {(uint64_t*)d->sort_k[0].p, (uint64_t*)d->sort_k[1].p};
+	uint32_t *p[2] = {(uint32_t*)d->sort_p[0].p, (uint32_t*)d->sort_p[1].p};
+	*cur = 0; *have_pay = !iota; *n_passes = 0;
+	if (n <= BSX_SORT_TILE) {
+		launch_sort_small(st, (const unsigned long long*)k[0], iota ? nullptr : p[0], (unsigned long long*)k[1], p[1], n);
+		HIPCHK(hipGetLastError());
+		*cur = 1; *have_pay = 1;
+		return BSX_OK;
+	}
+	int rc;
+	if ((rc = d->sort_counts.reserve(sort_n_tiles(n) * 256 * 4)) != BSX_OK) return rc;
+	if ((rc = d->sort_btot.reserve(sort_n_scan_blocks(n) * 4 + 16)) != BSX_OK) return rc;
+	unsigned long long *bits_d = (unsigned long long*)((char*)d->sort_btot.p + ((sort_n_scan_blocks(n) * 4 + 7) & ~(size_t)7)), bits = 0;
+	HIPCHK(hipMemsetAsync(bits_d, 0, 8, st));
+	launch_sort_bits(st, (const unsigned long long*)k[0], n, bits_d);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(&bits, bits_d, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	for (int shift = 0; shift < 64; shift += 8) {
+		if (((bits >> shift) & 255) == 0) continue;   // every key has the same digit here: the pass would move nothing
+		launch_sort_pass(st, (const unsigned long long*)k[*cur], *have_pay ? p[*cur] : nullptr, (unsigned long long*)k[*cur ^ 1], p[*cur ^ 1], n, shift,
+		                 (unsigned int*)d->sort_counts.p, (unsigned int*)d->sort_btot.p);
+		HIPCHK(hipGetLastError());
+		*cur ^= 1; *have_pay = 1; ++*n_passes;
+	}
+	return BSX_OK;
+}
+static int sort_buffers(bsx_device *d, int64_t n)
+{
+	int rc;
+	if (!d->sort_st) HIPCHK(hipStreamCreateWithFlags(&d->sort_st, hipStreamNonBlocking));
+	for (int i = 0; i < 2; ++i) {
+		if ((rc = d->sort_k[i].reserve((size_t)n * 8)) != BSX_OK) return rc;
+		if ((rc = d->sort_p[i].reserve((size_t)n * 4)) != BSX_OK) return rc;
+	}
+	return BSX_OK;
+}
+static int dev_sort_run(bsx_device_t *d, int64_t n, const uint64_t *keys, uint32_t *perm_out)
+{
+	if (!d) return BSX_E_NODEVICE;
+	if (n < 0 || n >= ((int64_t)1 << 31) || (n > 0 && (!keys || !perm_out))) return BSX_E_ARG;
+	if (n == 0) return BSX_OK;
+	std::lock_guard<std::mutex> lock(d->sort_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc, cur, have_pay, n_passes;
+	if ((rc = sort_buffers(d, n)) != BSX_OK) return rc;
+	uint64_t *run = nullptr;
+	if (hipMalloc((void**)&run, (size_t)n * 8) != hipSuccess) { (void)hipGetLastError(); fprintf(stderr, "[bsx-hip] sort: no device memory for a run of %lld keys\n", (long long)n); return BSX_E_NOMEM; }
+	rc = BSX_E_NODEVICE;
+	do {
+		if (hipMemcpyAsync(d->sort_k[0].p, keys, (size_t)n * 8, hipMemcpyHostToDevice, d->sort_st) != hipSuccess) break;
+		if ((rc = sort_passes(d, n, true, &cur, &have_pay, &n_passes)) != BSX_OK) break;
+		rc = BSX_E_NODEVICE;
+		if (hipMemcpyAsync(run, d->sort_k[cur].p, (size_t)n * 8, hipMemcpyDeviceToDevice, d->sort_st) != hipSuccess) break;
+		if (have_pay && hipMemcpyAsync(perm_out, d->sort_p[cur].p, (size_t)n * 4, hipMemcpyDeviceToHost, d->sort_st) != hipSuccess) break;
+		if (hipStreamSynchronize(d->sort_st) != hipSuccess) break;
+		rc = BSX_OK;
+	} while (0);
+	if (rc != BSX_OK) { fprintf(stderr, "[bsx-hip] sort: %s\n", hipGetErrorString(hipGetLastError())); (void)hipFree(run); return rc; }
+	if (!have_pay) for (int64_t i = 0; i < n; ++i) perm_out[i] = (uint32_t)i;
+	if (bsx_phases()) fprintf(stderr, "[M::sort] run %zu: %lld keys, %d passes\n", d->sort_runs.size(), (long long)n, n_passes);
+	d->sort_runs.push_back(std::make_pair(run, n));
+	return BSX_OK;
+}
+static int dev_sort_schedule(bsx_device_t *d, int64_t *n_total, uint32_t **run_of)
+{
+	if (!d) return BSX_E_NODEVICE;
+	if (!n_total || !run_of) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->sort_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	int64_t n = 0;
+	*n_total = 0; *run_of = nullptr;
+	for (auto &r : d->sort_runs) n += r.second;
+	if (n == 0) return BSX_OK;
+	if (n >= ((int64_t)1 << 31)) { fprintf(stderr, "[bsx-hip] sort: %lld records; the schedule holds fewer than 2^31\n", (long long)n); return BSX_E_ARG; }
+	int rc, cur, have_pay, n_passes;
+	if ((rc = sort_buffers(d, n)) != BSX_OK) return rc;
+	int64_t off = 0;
+	for (size_t r = 0; r < d->sort_runs.size(); ++r) { // the concatenation in run order, each key's payload its run
+		const int64_t m = d->sort_runs[r].second;
+		HIPCHK(hipMemcpyAsync((uint64_t*)d->sort_k[0].p + off, d->sort_runs[r].first, (size_t)m * 8, hipMemcpyDeviceToDevice, d->sort_st));
+		HIPCHK(hipMemsetD32Async((hipDeviceptr_t)((uint32_t*)d->sort_p[0].p + off), (int)r, (size_t)m, d->sort_st));
+		off += m;
+	}
+	if ((rc = sort_passes(d, n, false, &cur, &have_pay, &n_passes)) != BSX_OK) return rc;
+	uint32_t *out = (uint32_t*)malloc((size_t)n * 4);
+	if (!out) return BSX_E_NOMEM;
+	if (hipMemcpyAsync(out, d->sort_p[cur].p, (size_t)n * 4, hipMemcpyDeviceToHost, d->sort_st) != hipSuccess || hipStreamSynchronize(d->sort_st) != hipSuccess) {
+		fprintf(stderr, "[bsx-hip] sort: %s\n", hipGetErrorString(hipGetLastError())); free(out); return BSX_E_NODEVICE;
+	}
+	if (bsx_phases()) fprintf(stderr, "[M::sort] schedule: %zu runs, %lld keys, %d passes\n", d->sort_runs.size(), (long long)n, n_passes);
+	*n_total = n; *run_of = out;
+	return BSX_OK;
+}
+static int dev_sort_reset(bsx_device_t *d)
+{
+	if (!d) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->sort_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (d->sort_st) HIPCHK(hipStreamSynchronize(d->sort_st));
+	sort_release(d);
+	return BSX_OK;
+}
+extern "C" BSX_API int bsx_sort_run(bsx_device_t *d, int64_t n, const uint64_t *keys, uint32_t *perm_out) { return dev_sort_run(d, n, keys, perm_out); }
+extern "C" BSX_API int bsx_sort_schedule(bsx_device_t *d, int64_t *n_total, uint32_t **run_of) { return dev_sort_schedule(d, n_total, run_of); }
+extern "C" BSX_API int bsx_sort_reset(bsx_device_t *d) { return d ? dev_sort_reset(d) : BSX_E_NODEVICE; }
+extern "C" BSX_API int bsx_sort_info(bsx_device_t *d, uint64_t *n_runs, uint64_t *n_keys)
+{
+	if (!d) return BSX_E_NODEVICE;
+	std::lock_guard<std::mutex> lock(d->sort_mu);
+	uint64_t n = 0;
+	for (auto &r : d->sort_runs) n += (uint64_t)r.second;
+	if (n_runs) *n_runs = d->sort_runs.size();
+	if (n_keys) *n_keys = n;
+	return BSX_OK;
+}
+
 // the seams as one vtable for the host pipeline; ctx = (device, lane)
 #define LR(c) ((LaneRef*)(c))->d, ((LaneRef*)(c))->lane
 static int be_set_opt(void *c, const bsx_opt_t *o) { return lane_set_opt(LR(c), o); }
@@ -2391,6 +2530,15 @@ static int be_cov(void *c, int op, int64_t n, const bsx_qc_job_t *j, const uint3
 	return BSX_E_ARG;
 }
 
+static int be_sort(void *c, int op, int64_t n, const uint64_t *keys, uint32_t *perm_out, int64_t *n_total, uint32_t **run_of)
+{
+	bsx_device_t *d = ((LaneRef*)c)->d;
+	if (op == BSX_SORT_OP_RUN) return dev_sort_run(d, n, keys, perm_out);
+	if (op == BSX_SORT_OP_SCHEDULE) return dev_sort_schedule(d, n_total, run_of);
+	if (op == BSX_SORT_OP_RESET) return dev_sort_reset(d);
+	return BSX_E_ARG;
+}
+
 static LaneRef g_lane_ref[8][BSX_LANES];   // ctx storage for the vtables (by device ordinal)
 
 extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *out)
@@ -2402,7 +2550,7 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	memset(out, 0, sizeof(*out));
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
-	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov;
+	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov; out->sort_batch = be_sort;
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

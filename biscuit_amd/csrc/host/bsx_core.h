@@ -202,7 +202,12 @@ typedef struct bsx_backend {
 	 * from one upload: what a slice with both options calls).  Without it the host keeps the state (cov.c). */
 	int (*cov_batch)(void *ctx, int op, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len,
 	                 const int64_t *beg_end, bsx_cov_tables_t *out);
+	/* optional (may be NULL; a backend that clears the struct has it NULL): the backend's sort of record keys for --sort, by op: BSX_SORT_OP_RUN
+	 * (bsx_sort_run: n keys, perm_out), BSX_SORT_OP_SCHEDULE (bsx_sort_schedule into *n_total, *run_of), BSX_SORT_OP_RESET (bsx_sort_reset).
+	 * Without it the host sorts (sortout.c: a stable merge sort, the same results). */
+	int (*sort_batch)(void *ctx, int op, int64_t n, const uint64_t *keys, uint32_t *perm_out, int64_t *n_total, uint32_t **run_of);
 } bsx_backend_t;
+enum { BSX_SORT_OP_RUN = 0, BSX_SORT_OP_SCHEDULE = 1, BSX_SORT_OP_RESET = 2 };
 enum { BSX_COV_OP_BATCH = 0, BSX_COV_OP_MASK = 1 /* + which: 1, 2 */, BSX_COV_OP_TABLES = 3, BSX_COV_OP_RESET = 4, BSX_COV_OP_QC_BATCH = 5 };
 /* what msw_plan says about a pair: base = its first job in res (-1: the pair is left to the host's own plan), n_c[i] = candidates of read i it
  * looked at, mask[i] = which of them have a job (bit j: candidate j), in job order: read 0's, then read 1's */

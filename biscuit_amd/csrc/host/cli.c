@@ -2,6 +2,7 @@
  * same getopt string, option -> field mapping, -A rescaling, -x presets, header, chunk size
  * (chunk_size x n_threads bases, align.c:576) and chunk order.  SAM goes to stdout. */
 #include <unistd.h>
+#include <errno.h>
 #include <ctype.h>
 #include <math.h>
 #include <getopt.h>
@@ -10,6 +11,9 @@
 #include "tune.h"
 #include "fastq.h"
 #include "pipeline.h"
+#include "sortout.h"
+#include <signal.h>
+#include <sys/time.h>
 
 const uint8_t *bsx_nt4_table(void);
 BSX_API char *bsx_pg_line = 0;
@@ -72,6 +76,10 @@ static int usage(void)
 		"              --qc-topgc FILE --qc-botgc FILE  (both or neither; BED, plain or gzip) also the eight _topgc / _botgc tables\n"
 		"  markdup   : --markdup  0x400 on every record of a template (a pair, or a single read) whose ends' unclipped 5' positions, strands and YD\n"
 		"              equal those of an earlier template of the input; one process only (refused with WORLD_SIZE > 1)\n"
+		"  sort      : --sort  the records in coordinate order: by the rank of RNAME among the header's @SQ lines ('*' last), POS, then forward before\n"
+		"              reverse; equal keys in the order of the unsorted output; @HD ... SO:coordinate first in the header.  The order is computed on the\n"
+		"              device, the records wait in one temporary file; one process only (refused with WORLD_SIZE > 1)\n"
+		"              --sort-tmp DIR  where that file is made (default: /tmp); it has no name while it exists\n"
 		"  device    : $BSX_DEVICE selects the HIP device ordinal (default 0)\n\n");
 	return 1;
 }
@@ -204,6 +212,7 @@ static int g_use_stream = 0;
 /* set by the product entry: how to release what its open_device callback made */
 static void (*g_close_device)(void *ud) = 0;
 
+static void hip_close(void *ud);
 typedef int (*process_fn)(void *ud, const bsx_opt_t *opt, const bsx_index_t *idx, int64_t n_processed, int n, bsx_read_t *reads, const bsx_pestat_t *pes0);
 
 /* shared by the product entry (HIP) and the test-only entry that injects another backend */
@@ -236,6 +245,9 @@ static int cq_get(chunk_q_t *Q, chunk_rec_t *r)   /* 0 when the queue is closed 
 }
 static void emit_chunk(bsx_read_t *seqs, int n, int64_t chunk_idx, int ok);
 static volatile int g_write_error = 0;   /* a write to stdout failed (the reference aborts there: err_fputs, utils.c:214) */
+/* --sort: finished chunks go to the sorter instead of the output; what it holds leaves at the end of the call, behind the header */
+static bsx_sorter_t *g_sorter = 0;
+static volatile int g_sort_error = 0;   /* a chunk could not be sorted or kept: nothing is written */
 /* Several ranks over plain files: a scanner thread lists the chunk boundaries without building records (fastq.c) and this rank
  * parses only its own chunks r, r+N, ..., seeking to each.  Compressed or piped input: every rank inflates everything (threads of
  * fastq.c, ahead of the parser), parses its own chunks and walks the others' by the record grammar without building records (the chunk
@@ -309,6 +321,19 @@ static void *writer_main(void *arg)
 static void emit_chunk(bsx_read_t *seqs, int n, int64_t chunk_idx, int ok)
 {
 	int i;
+	if (g_sorter) {
+		if (ok && !g_sort_error) {
+			size_t tot = 0, at = 0; char *all;
+			for (i = 0; i < n; ++i) if (seqs[i].sam) tot += strlen(seqs[i].sam);
+			all = (char*)malloc(tot + 1);
+			for (i = 0; i < n; ++i) if (seqs[i].sam) { size_t l = strlen(seqs[i].sam); memcpy(all + at, seqs[i].sam, l); at += l; }
+			if ((i = bsx_sorter_add(g_sorter, all, tot)) != BSX_OK) { fprintf(stderr, "[E::%s] --sort: chunk %ld could not be sorted (%s)\n", "main_align", (long)chunk_idx, bsx_strerror(i)); g_sort_error = 1; }
+			free(all);
+		}
+		for (i = 0; i < n; ++i) bsx_read_free(&seqs[i]);
+		free(seqs);
+		return;
+	}
 	if (ok && bsx_emit_hook) {
 		size_t tot = 0, at = 0; char *all;
 		for (i = 0; i < n; ++i) if (seqs[i].sam) tot += strlen(seqs[i].sam);
@@ -337,6 +362,17 @@ static void bsconv_report(void)
 
 /* --markdup needs one table for the whole input: the tables of several devices would have to be one */
 #define MARKDUP_RANKS_MSG "--markdup marks duplicates over the whole input in one table on one device: it cannot run with WORLD_SIZE > 1"
+
+/* --sort orders the records of the whole input: the runs of several devices would have to be merged */
+#define SORT_RANKS_MSG "--sort orders the whole input through one device and one temporary file: it cannot run with WORLD_SIZE > 1"
+typedef struct { int64_t piece; } sort_sink_t;
+static int sort_sink(void *ud, const char *text, size_t len)
+{
+	sort_sink_t *k = (sort_sink_t*)ud;
+	if (bsx_emit_hook) { bsx_emit_hook(bsx_emit_ud, k->piece++, text, len); return 0; }
+	return fwrite(text, 1, len, stdout) == len ? 0 : 1;
+}
+static double now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.tv_sec + tv.tv_usec * 1e-6; }
 
 /* --qc-cov needs the depth of every position over the whole input: the histograms of several devices do not add up to it */
 #define QC_COV_RANKS_MSG "--qc-cov keeps the depth of the whole input on one device: it cannot run with WORLD_SIZE > 1"
@@ -390,11 +426,16 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		{"bsconv-max-cpc", required_argument, 0, 1003}, {"bsconv-max-cpt", required_argument, 0, 1004}, {"bsconv-max-cpy", required_argument, 0, 1005},
 		{"bsconv-max-cph-frac", required_argument, 0, 1006}, {"bsconv-max-cpy-frac", required_argument, 0, 1007},
 		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {"qc", required_argument, 0, 1010}, {"markdup", no_argument, 0, 1011},
-		{"qc-cov", no_argument, 0, 1012}, {"qc-topgc", required_argument, 0, 1013}, {"qc-botgc", required_argument, 0, 1014}, {0, 0, 0, 0}
+		{"qc-cov", no_argument, 0, 1012}, {"qc-topgc", required_argument, 0, 1013}, {"qc-botgc", required_argument, 0, 1014},
+		{"sort", no_argument, 0, 1015}, {"sort-tmp", required_argument, 0, 1016}, {0, 0, 0, 0}
 	};
 	bsx_bsconv_conf_t bsconv;
 	int bsconv_on = 0, qc_on = 0, markdup_on = 0, qc_cov_on = 0;
-	const char *gc_bed[2] = {0, 0};
+	const char *gc_bed[2] = {0, 0}, *sort_tmp = 0;
+	int sort_on = 0;
+	char *sort_hdr = 0;
+	double t_start = 0;
+	void (*old_xfsz)(int) = SIG_DFL;
 
 	bsx_bsconv_conf_init(&bsconv);
 	g_write_error = 0;   /* per call: a failed write of an earlier call in this process must not fail this one */
@@ -409,6 +450,8 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		else if (c == 1011) markdup_on = 1;
 		else if (c == 1012) qc_cov_on = 1;
 		else if (c == 1013 || c == 1014) gc_bed[c - 1013] = optarg;
+		else if (c == 1015) sort_on = 1;
+		else if (c == 1016) sort_tmp = optarg;
 		else if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
 			bsconv_on = 1;
 			if (c == 1000) bsconv.annotate = 1;
@@ -563,6 +606,13 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	bsx_process_set_qc(qc_on);
 	bsx_process_set_qc_cov(qc_cov_on);
 	if (markdup_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; }
+	if (sort_tmp && !sort_on) { fprintf(stderr, "[E::%s] --sort-tmp names the directory of --sort's temporary file: it needs --sort\n", "main_align"); return 1; }
+	if (sort_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", SORT_RANKS_MSG); return 1; }
+	if (sort_on && (opt->flag & BSX_F_ALN_REG)) { fprintf(stderr, "[E::%s] --sort orders SAM records: it cannot be combined with -F\n", "main_align"); return 1; }
+	if (sort_on && bsx_sorter_dir_ok(sort_tmp) != BSX_OK) { /* before any read is aligned */
+		fprintf(stderr, "[E::%s] --sort: no temporary file can be made in %s (%s)\n", "main_align", sort_tmp ? sort_tmp : "/tmp", strerror(errno));
+		return 1;
+	}
 	bsx_process_set_markdup(markdup_on);
 	if (optind >= argc) { usage(); fprintf(stderr, "Missing fai-index base\n"); return 1; }
 	if ((rc = bsx_index_load(argv[optind], &idx)) != BSX_OK) { fprintf(stderr, "[E::%s] fail to locate the index files (%s)\n", "main_align", bsx_strerror(rc)); return 1; }
@@ -581,6 +631,17 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 			}
 		}
 	}
+	if (sort_on) { /* the header waits with the records: nothing that looks like a complete file leaves a run that fails */
+		char *h = bsx_sam_header(idx, hdr_line, bsx_pg_line);
+		sort_hdr = bsx_sort_header(h);
+		g_sort_error = 0;
+		/* the product entry sorts on its device; another backend's records are ordered by the host's merge sort */
+		rc = g_close_device == hip_close ? bsx_sorter_open((bsx_device_t*)ud, h, sort_tmp, &g_sorter) : bsx_sorter_open_backend(0, h, sort_tmp, &g_sorter);
+		free(h);
+		if (rc != BSX_OK || !sort_hdr) { fprintf(stderr, "[E::%s] --sort: %s\n", "main_align", bsx_strerror(rc != BSX_OK ? rc : BSX_E_NOMEM)); g_sorter = 0; rc = 1; goto cleanup; }
+		old_xfsz = signal(SIGXFSZ, SIG_IGN);   /* a file size limit met by the temporary file is a write error with a message, not a signal */
+		t_start = now_s();
+	} else
 	if (!(opt->flag & BSX_F_ALN_REG) && bsx_shard_rank == 0) {
 		char *h = bsx_sam_header(idx, hdr_line, bsx_pg_line);
 		if (bsx_emit_hook) bsx_emit_hook(bsx_emit_ud, -1, h, strlen(h)); else if (fputs(h, stdout) == EOF) g_write_error = 1;
@@ -762,6 +823,25 @@ loop_done:
 		bsx_fq_scan_close(scan);
 	}
 	if (bsx_fq_error(f1) || bsx_fq_error(f2)) { fprintf(stderr, "[E::%s] damaged or truncated compressed input: the SAM is incomplete\n", "main_align"); rc = 1; }
+	if (g_sorter) { /* every chunk is in the temporary file: the header, then the records in the order of the schedule */
+		const double t_aligned = now_s();
+		if (g_sort_error) rc = 1;
+		if (rc == 0) {
+			sort_sink_t k = {0};
+			int src;
+			if (bsx_emit_hook) bsx_emit_hook(bsx_emit_ud, -1, sort_hdr, strlen(sort_hdr)); else if (fputs(sort_hdr, stdout) == EOF) g_write_error = 1;
+			if (!g_write_error && (src = bsx_sorter_finish(g_sorter, sort_sink, &k)) != BSX_OK) {
+				if (src == BSX_E_IO && ferror(stdout)) g_write_error = 1;
+				else fprintf(stderr, "[E::%s] --sort: merging the sorted chunks failed (%s): the SAM is incomplete\n", "main_align", bsx_strerror(src));
+				rc = 1;
+			}
+		} else fprintf(stderr, "[E::%s] --sort: nothing is written after an error\n", "main_align");
+		if (bsx_verbose >= 3) {
+			uint64_t nr = 0, nrec = 0;
+			bsx_sorter_counts(g_sorter, &nr, &nrec);
+			fprintf(stderr, "[M::%s] sort: %llu runs, %llu records (aligned in %.2f s, merged in %.2f s)\n", "main_align", (unsigned long long)nr, (unsigned long long)nrec, t_aligned - t_start, now_s() - t_aligned);
+		}
+	}
 	if (fflush(stdout) != 0 || ferror(stdout)) g_write_error = 1;
 	if (g_write_error) { fprintf(stderr, "[E::%s] failed to write the output: the SAM is incomplete\n", "main_align"); rc = 1; }
 	if (bsconv_on && bsx_shard_world <= 1) bsconv_report();   /* (several ranks: rank 0 reports the sum, bsx_align_main_ranks_with) */
@@ -777,6 +857,8 @@ loop_done:
 		        (unsigned long long)t.n_keyed, (unsigned long long)t.n_dup);
 	}
 cleanup:
+	if (g_sorter) { bsx_sorter_close(g_sorter); g_sorter = 0; signal(SIGXFSZ, old_xfsz); }   /* (before the device it sorts on is closed) */
+	free(sort_hdr);
 	if (markdup_on) bsx_process_set_markdup(0);
 	if (qc_cov_on) bsx_process_set_qc_cov(0);
 	if (qc_on && bsx_shard_world <= 1) bsx_process_set_qc(0);
@@ -853,6 +935,7 @@ BSX_API int bsx_align_main_ranks_with(int argc, char **argv, bsx_process_fn proc
 	if (rank < 0 || rank >= world) { fprintf(stderr, "[E::%s] RANK %d of WORLD_SIZE %d\n", "main_align", rank, world); return 1; }
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 3 && strncmp("--markdup", argv[k], strlen(argv[k])) == 0) { /* (any abbreviation getopt_long takes: no other long option begins with --m) */ fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; } }   /* (before any transport is opened) */
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 6 && strncmp("--qc-cov", argv[k], strlen(argv[k])) == 0) { /* (--qc-c, --qc-co: what getopt_long takes for it) */ fprintf(stderr, "[E::%s] %s\n", "main_align", QC_COV_RANKS_MSG); return 1; } }
+	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strncmp(argv[k], "--s", 3) == 0) { /* (--sort, --sort-tmp and every abbreviation: no other long option begins with --s) */ fprintf(stderr, "[E::%s] %s\n", "main_align", SORT_RANKS_MSG); return 1; } }
 	memset(&R, 0, sizeof(R));
 	if (id_env && *id_env) snprintf(id_path, sizeof(id_path), "%s", id_env);
 	else if (out_path && *out_path) snprintf(id_path, sizeof(id_path), "%s.ranks", out_path);
@@ -935,6 +1018,15 @@ static int hip_process(void *ud, const bsx_opt_t *opt, const bsx_index_t *idx, i
 }
 
 static void hip_close(void *ud) { bsx_device_close((bsx_device_t*)ud); }
+
+BSX_API int bsx_sorter_open(bsx_device_t *dev, const char *header, const char *tmp_dir, bsx_sorter_t **out)
+{
+	bsx_backend_t be;
+	int rc;
+	if (!dev) return bsx_sorter_open_backend(0, header, tmp_dir, out);
+	if ((rc = bsx_hip_backend(dev, &be)) != BSX_OK) return rc;
+	return bsx_sorter_open_backend(&be, header, tmp_dir, out);
+}
 
 BSX_API int bsx_align_main(int argc, char **argv)
 {

@@ -415,6 +415,41 @@ int bsx_markdup_reset(bsx_device_t *dev);   /* an empty table of the initial cap
 int bsx_markdup_table_info(bsx_device_t *dev, uint64_t *n_slots, uint64_t *n_used);
 uint64_t bsx_markdup_hash(const bsx_markdup_key_t *key, uint32_t salt, int bits);
 
+/* Coordinate order (k_sort.hip): a stable radix sort of 64-bit keys on the device, and the keys of every sorted run kept there until
+ * bsx_sort_reset or bsx_device_close.  A record's key is BSX_SORT_KEY(rank, POS, FLAG & 0x10): rank = the 0-based index of its RNAME among the
+ * @SQ lines of the header as written, 0xffffffff for RNAME '*'; POS below 2^31.
+ * bsx_sort_run: perm_out[i] = the index, in this call's keys, of the i-th key in stable order (equal keys in input order); the sorted keys stay
+ * on the device as the next run (runs number from 0).  n == 0 adds no run; n of 2^31 or more is BSX_E_ARG.
+ * bsx_sort_schedule: the stable sort of all retained keys taken as the concatenation of the runs in run order, as the run every output position
+ * comes from: (*run_of)[i] for i < *n_total, malloc'd, the caller frees it (NULL when there is no key).  Equal keys come from the lower run
+ * first, and within a run in its order: following run_of with one cursor per run merges the runs.  The runs stay as they are.
+ * Device memory that cannot be had is BSX_E_NOMEM; nothing is ever sorted on the host by these calls.  BSX_SORT_TILE: the keys of one
+ * workgroup; up to that many are sorted by a single workgroup in LDS, more by tiled passes over HBM. */
+#define BSX_SORT_TILE 2048
+#define BSX_SORT_KEY(rank, pos, rev)  ((uint64_t)(rank) << 32 | (uint64_t)(pos) << 1 | ((rev) != 0))   /* RNAME '*': rank 0xffffffff */
+int bsx_sort_run(bsx_device_t *dev, int64_t n, const uint64_t *keys, uint32_t *perm_out);
+int bsx_sort_schedule(bsx_device_t *dev, int64_t *n_total, uint32_t **run_of);   /* caller frees */
+int bsx_sort_info(bsx_device_t *dev, uint64_t *n_runs, uint64_t *n_keys);
+int bsx_sort_reset(bsx_device_t *dev);
+
+/* Coordinate-sorted SAM (--sort; csrc/host/sortout.c).  The sorter takes the SAM body chunk by chunk (whole lines), gets each chunk's order
+ * from the device (bsx_sort_run; dev == NULL: the host's own stable merge sort, same result), appends the chunk's lines in that order to one
+ * temporary file in tmp_dir (NULL: /tmp; made with mkstemp and unlinked at once) and, at the end, follows bsx_sort_schedule through
+ * one pread cursor per run: the host never compares two records.  header: the header text as written (its @SQ lines give the ranks).
+ * bsx_sorter_finish hands the sorted body to `sink` in pieces of whole lines (a non-zero return stops it: BSX_E_IO).  "sort_buf_bytes"
+ * (bsx_tune_set): the read buffer of every run; a record longer than the buffer still works.  A failed write to the temporary file is
+ * BSX_E_IO from bsx_sorter_add and from everything after it.  bsx_sorter_dir_ok: BSX_OK when a temporary file can be made in the directory.
+ * bsx_sort_header: the header of a sorted file, malloc'd -- "@HD\tVN:1.6\tSO:coordinate" first when the text has no @HD line, else its @HD line
+ * moved to the front with SO:coordinate set (or appended); every other line as it is. */
+typedef struct bsx_sorter bsx_sorter_t;
+int  bsx_sorter_dir_ok(const char *tmp_dir);
+int  bsx_sorter_open(bsx_device_t *dev, const char *header, const char *tmp_dir, bsx_sorter_t **out);
+int  bsx_sorter_add(bsx_sorter_t *s, const char *text, size_t len);
+int  bsx_sorter_finish(bsx_sorter_t *s, int (*sink)(void *ud, const char *text, size_t len), void *ud);
+void bsx_sorter_counts(const bsx_sorter_t *s, uint64_t *n_runs, uint64_t *n_records);
+void bsx_sorter_close(bsx_sorter_t *s);
+char *bsx_sort_header(const char *header);
+
 /* Settings of the library that never change its output (launch shapes, table sizes, which of two equivalent paths runs: what the tests and
  * the A/B tools switch).  One registry (csrc/host/tune.c has the table of names): bsx_tune_set(name, value) between calls of the library
  * (value NULL: back to the default; BSX_E_ARG for an unknown name), or "$BSX_TUNE=name=value,name=value" for a whole process.  bsx_phases():
