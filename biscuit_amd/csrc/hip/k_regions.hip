@@ -1577,6 +1577,7 @@ __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const Reg
 // memchain.c:501-535); seeds below the threshold leave the list, the others carry their score into mem_chain2region1's best-first
 // order.  One wavefront per strand search, the lists compacted in place ahead of k_c2r.
 #include "sw_pass.hpp"
+#include "ssw16_bound.h"
 #define RG_SHORT_EXT 50
 #define RG_SHORT_LEN 200
 // Round 5: the alignments of a chunk's seeds are one batch.  A kilobase read has a few dozen seeds to score on its own strand (and the other
@@ -1828,8 +1829,31 @@ k_swl16(DevIndex ix, DevScoring sc, const uint8_t *reads, const SswJob *jobs, co
 	}
 }
 
+// the one launch of k_swl16: by the seed filter (launch_seedsw) and by the test seam (launch_swl16_batch)
+static void launch_swl16(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const SswJob *jobs, const unsigned int *job_count,
+                         unsigned int job_cap, int *scores)
+{
+	if (sc.o_del == sc.o_ins && sc.e_del == sc.e_ins) hipLaunchKernelGGL(k_swl16<true>, dim3(n_cu * 8), dim3(256), 0, st, ix, sc, reads, jobs, job_count, job_cap, scores);
+	else hipLaunchKernelGGL(k_swl16<false>, dim3(n_cu * 8), dim3(256), 0, st, ix, sc, reads, jobs, job_count, job_cap, scores);
+}
+
+// the alignment of a seed that found no room in the chunk's job list (or whose scoring options k_swl16 cannot hold): a wavefront for the one
+// window, 32-bit arithmetic (sw_pass, the form of rounds 3-4), the register slots by the padded query.  qat: where the window's query starts
+// in reads.  Called by k_seedsw_apply and by the test seam k_ssw32_batch
+__device__ __forceinline__ int ssw_align32(const DevIndex &ix, const DevScoring &sc, const int8_t *mat, const uint8_t *reads, size_t qat, int qlen,
+                                           long long rb, int tlen, int lane)
+{
+	const int Q = ((qlen + 7) >> 3) << 3;
+	int sc1 = -1;
+#define SEEDSW_RUN(NC_) do { int qv[NC_]; _Pragma("unroll") for (int c = 0; c < NC_; ++c) { const int jj = (c << 6) + lane; qv[c] = jj < qlen ? (int)reads[qat + jj] : 5; } \
+		const SwPass r = sw_pass<NC_>(ix, mat, 0, qlen, qv, tlen, rb, 1, -1, sc.o_del, sc.e_del, sc.o_ins, sc.e_ins, 0, nullptr, lane); sc1 = uni(r.score); } while (0)
+	if (Q <= 128) SEEDSW_RUN(2); else if (Q <= 192) SEEDSW_RUN(3); else SEEDSW_RUN(4);
+#undef SEEDSW_RUN
+	return sc1;
+}
+
 // one seed's score for k_seedsw_apply: from the batch, or -- no room in the chunk's job list -- aligned here, a wavefront for the one
-// alignment (the form of rounds 3-4).  Wave-uniform control flow; `have`: this lane holds a seed.
+// alignment.  Wave-uniform control flow; `have`: this lane holds a seed.
 __device__ __forceinline__ int ssw_score_of(const DevIndex &ix, const DevScoring &sc, const int8_t *mat, const uint8_t *reads, uint32_t qoff, int l_query,
                                             bool have, const RgXSeed &sd, const int *scores, unsigned int &n_sw, int lane)
 {
@@ -1844,12 +1868,7 @@ __device__ __forceinline__ int ssw_score_of(const DevIndex &ix, const DevScoring
 		todo &= todo - 1;
 		const long long s_rbeg = uni64(__shfl((long long)sd.rbeg, src)); const int s_qbeg = uni(__shfl((int)sd.qbeg, src)), s_len1 = uni(__shfl((int)sd.len, src));
 		int qb, qlen, tlen; long long rb; int sc1 = -1;
-		if (ssw_window(ix, l_query, s_rbeg, s_qbeg, s_len1, qb, qlen, rb, tlen)) {
-			const int Q = ((qlen + 7) >> 3) << 3;
-#define SEEDSW_RUN(NC_) do { int qv[NC_]; _Pragma("unroll") for (int c = 0; c < NC_; ++c) { const int jj = (c << 6) + lane; qv[c] = jj < qlen ? (int)reads[(size_t)qoff + qb + jj] : 5; } \
-				const SwPass r = sw_pass<NC_>(ix, mat, 0, qlen, qv, tlen, rb, 1, -1, sc.o_del, sc.e_del, sc.o_ins, sc.e_ins, 0, nullptr, lane); sc1 = uni(r.score); } while (0)
-			if (Q <= 128) SEEDSW_RUN(2); else if (Q <= 192) SEEDSW_RUN(3); else SEEDSW_RUN(4);
-		}
+		if (ssw_window(ix, l_query, s_rbeg, s_qbeg, s_len1, qb, qlen, rb, tlen)) sc1 = ssw_align32(ix, sc, mat, reads, (size_t)qoff + qb, qlen, rb, tlen, lane);
 		if (lane == src) score = sc1;
 	}
 	n_sw += (unsigned int)__popcll(__ballot(pending));
@@ -2406,22 +2425,66 @@ void launch_seedsw(hipStream_t st, int grid, int n_cu, const RgLaunch &G, const 
 	RgXPool X = rgx_pool(&XA);
 	SswJob *J = (SswJob*)jobs;
 	int *scores = (int*)(J + job_cap);
-	{ // k_swl16 keeps two jobs' scores in the 16-bit halves of a register (wrapping adds, signed 16-bit maxima) and its profile as biased bytes:
-	  // exact while the largest score of a job -- at most 199 columns of the matrix's maximum -- plus the bias and the gap terms added to it
-	  // stays below 2^15, and a biased matrix entry fits a byte.  Scoring options beyond that (an -A in the hundreds) leave the job list empty:
-	  // every seed then takes the no-room path of k_seedsw_apply (sw_pass: a wavefront per alignment in 32-bit arithmetic), which is exact.
-		int mx = 0, bias = 0;
-		for (int i = 0; i < 25; ++i) {
-			mx = sc.ctmat[i] > mx ? sc.ctmat[i] : mx; mx = sc.gamat[i] > mx ? sc.gamat[i] : mx;
-			bias = -(int)sc.ctmat[i] > bias ? -(int)sc.ctmat[i] : bias; bias = -(int)sc.gamat[i] > bias ? -(int)sc.gamat[i] : bias;
-		}
-		const int oe = (sc.o_del + sc.e_del > sc.o_ins + sc.e_ins ? sc.o_del + sc.e_del : sc.o_ins + sc.e_ins), e = sc.e_del > sc.e_ins ? sc.e_del : sc.e_ins;
-		if (199LL * mx + 7LL * 25 * e + 2LL * oe + bias >= 32768 || mx + bias > 255 || oe >= 32768) job_cap = 0;
-	}
+	// k_swl16 keeps two jobs' scores in the 16-bit halves of a register (wrapping adds, signed 16-bit maxima) and its profile as biased bytes:
+	// exact under the rule of ssw16_bound.h.  Scoring options beyond that (an -A in the hundreds) leave the job list empty: every seed then
+	// takes the no-room path of k_seedsw_apply (ssw_align32: a wavefront per alignment in 32-bit arithmetic), which is exact.
+	if (!ssw16_exact_mats(sc.ctmat, sc.gamat, sc.o_del, sc.e_del, sc.o_ins, sc.e_ins)) job_cap = 0;
 	hipLaunchKernelGGL(k_seedsw_prep, dim3(grid), dim3(64), 0, st, ix, G.tasks, X, cursor, J, job_cap, count_cursor);
-	if (sc.o_del == sc.o_ins && sc.e_del == sc.e_ins) hipLaunchKernelGGL(k_swl16<true>, dim3(n_cu * 8), dim3(256), 0, st, ix, sc, G.reads, (const SswJob*)J, (const unsigned int*)count_cursor, job_cap, scores);
-	else hipLaunchKernelGGL(k_swl16<false>, dim3(n_cu * 8), dim3(256), 0, st, ix, sc, G.reads, (const SswJob*)J, (const unsigned int*)count_cursor, job_cap, scores);
+	launch_swl16(st, n_cu, ix, sc, G.reads, (const SswJob*)J, (const unsigned int*)count_cursor, job_cap, scores);
 	hipLaunchKernelGGL(k_seedsw_apply, dim3(grid), dim3(64), 0, st, ix, sc, *G.P, G.reads, G.tasks, X, count_cursor + 1, (const int*)scores, G.counters);
+}
+
+// ---- the test seam of bsx_sw_batch (setting sw_form): plain jobs through the seed filter's two alignments.  k_ssw_jobs turns the batch into
+// SswJobs in the order given (a filler, qlen = 0, becomes the empty job ssw_take leaves) and writes the count where k_swl16 reads it
+__global__ void __launch_bounds__(256)
+k_ssw_jobs(const bsx_sw_job_t *in, unsigned int n, SswJob *jobs, unsigned int *job_count)
+{
+	const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i == 0) *job_count = n;
+	if (i >= n) return;
+	const bsx_sw_job_t j = in[i];
+	SswJob J; J.rb = 0; J.qoff = 0; J.qlen = 0; J.tlen = 0;
+	if (j.qlen > 0) { J.rb = j.tpos; J.qoff = j.qoff | (j.use_ct ? 0x80000000u : 0u); J.qlen = (short)j.qlen; J.tlen = (short)j.tlen; }
+	jobs[i] = J;
+}
+__global__ void __launch_bounds__(256)
+k_ssw_res(const int *scores, unsigned int n, bsx_sw_res_t *res)
+{
+	const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	bsx_sw_res_t r; r.score = scores[i]; r.te = r.qe = r.score2 = r.te2 = r.tb = r.qb = -1;
+	res[i] = r;
+}
+// a wavefront per job through ssw_align32
+__global__ void __launch_bounds__(64, 4)
+k_ssw32_batch(DevIndex ix, DevScoring sc, const uint8_t *reads, const bsx_sw_job_t *jobs, unsigned int n, bsx_sw_res_t *res)
+{
+	const int lane = wave_lane();
+	for (unsigned int i = blockIdx.x; i < n; i += gridDim.x) {
+		const long long tpos = uni64(jobs[i].tpos);
+		const uint32_t qoff = (uint32_t)uni((int)jobs[i].qoff);
+		const int qlen = uni(jobs[i].qlen), tlen = uni(jobs[i].tlen), use_ct = uni((int)jobs[i].use_ct);
+		const int score = qlen > 0 ? ssw_align32(ix, sc, use_ct ? sc.ctmat : sc.gamat, reads, (size_t)qoff, qlen, tpos, tlen, lane) : 0;
+		if (lane == 0) { bsx_sw_res_t r; r.score = score; r.te = r.qe = r.score2 = r.te2 = r.tb = r.qb = -1; res[i] = r; }
+	}
+}
+bool launch_swl16_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_sw_job_t *jobs, bsx_sw_res_t *res,
+                        unsigned int n, void *work)
+{   // work: n * seedsw_job_bytes() + 16 bytes -- the jobs, their scores, the count
+	if (!ssw16_exact_mats(sc.ctmat, sc.gamat, sc.o_del, sc.e_del, sc.o_ins, sc.e_ins)) return false;
+	SswJob *J = (SswJob*)work;
+	int *scores = (int*)(J + n);
+	unsigned int *count = (unsigned int*)(scores + n);
+	const unsigned int blocks = (n + 255) / 256;
+	hipLaunchKernelGGL(k_ssw_jobs, dim3(blocks), dim3(256), 0, st, jobs, n, J, count);
+	launch_swl16(st, n_cu, ix, sc, reads, (const SswJob*)J, (const unsigned int*)count, n, scores);
+	hipLaunchKernelGGL(k_ssw_res, dim3(blocks), dim3(256), 0, st, (const int*)scores, n, res);
+	return true;
+}
+void launch_ssw32_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_sw_job_t *jobs, bsx_sw_res_t *res, unsigned int n)
+{
+	const unsigned int grid = n < (unsigned int)n_cu * 32 ? n : (unsigned int)n_cu * 32;
+	hipLaunchKernelGGL(k_ssw32_batch, dim3(grid), dim3(64), 0, st, ix, sc, reads, jobs, n, res);
 }
 #undef RG_COMMON_
 #undef RG_LISTS_

@@ -147,6 +147,13 @@ size_t c2r_hbm_slab_bytes(void);
 void launch_seedsw(hipStream_t st, int grid, int n_cu, const RgLaunch &G, const RgXPoolArg &XA, unsigned int *cursor, unsigned int *count_cursor,
                    void *jobs, unsigned int job_cap);
 size_t seedsw_job_bytes(void);
+// tests (setting sw_form): plain score-only jobs of up to 199 x 199 through the seed filter's two alignments.  launch_swl16_batch: the
+// k_swl16 launch of launch_seedsw over the jobs in the order given, sixteen consecutive ones to a wavefront (qlen = 0: an empty job); work:
+// n * seedsw_job_bytes() + 16 bytes; false, nothing launched: scoring options ssw16_exact (ssw16_bound.h) refuses.  launch_ssw32_batch: a
+// wavefront per job through the 32-bit alignment k_seedsw_apply makes for a seed without room in the job list
+bool launch_swl16_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_sw_job_t *jobs, bsx_sw_res_t *res,
+                        unsigned int n, void *work);
+void launch_ssw32_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_sw_job_t *jobs, bsx_sw_res_t *res, unsigned int n);
 int regions_long_max_query(void);
 void launch_regions_slab(hipStream_t st, int tier, int grid, const RgLaunch &G, const int *list, const unsigned int *count, unsigned int *cursor,
                          void *slabs, int *next_list, unsigned int *next_count, const RgXPoolArg *X = nullptr);   // X: export the chains (as the LDS tiers do) instead of making the regions

@@ -1709,6 +1709,28 @@ static int lane_sw_batch(bsx_device_t *d, int lane, int64_t n, const bsx_sw_job_
 	if (n == 0) return BSX_OK;
 	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
 	HIPCHK(hipSetDevice(d->ordinal));
+	if (bsx_tune_is_set("sw_form")) { // tests: score-only jobs of up to 199 x 199 through the seed filter's alignments (k_regions.hip), in the order given
+		const char *form = bsx_tune_str("sw_form");
+		const bool f16 = strcmp(form, "ssw16") == 0;
+		if ((!f16 && strcmp(form, "ssw32") != 0) || n > 0x7fffffff || L.n_reads == 0) return BSX_E_ARG;
+		for (int64_t i = 0; i < n; ++i) {
+			const bsx_sw_job_t &j = jobs[i];
+			if (j.qdir != 1 || j.tdir != 1 || j.qcomp != 0 || j.qlen < 0 || j.qlen > 199 || j.tlen < 0 || j.tlen > 199) return BSX_E_ARG;
+			if (j.qlen == 0) continue;   // an empty job: nothing of it is read
+			if (j.tpos < 0 || j.tpos + j.tlen > 2 * d->ix.l_pac || (j.qoff >> 31) || (size_t)j.qoff + (size_t)j.qlen > L.n_reads) return BSX_E_ARG;
+		}
+		int rc;
+		if ((rc = L.jobs.reserve((size_t)n * sizeof(bsx_sw_job_t))) != BSX_OK) return rc;
+		if ((rc = L.res.reserve((size_t)n * sizeof(bsx_sw_res_t))) != BSX_OK) return rc;
+		if ((rc = L.scratch.reserve((size_t)n * seedsw_job_bytes() + 16)) != BSX_OK) return rc;
+		H2D(L.st_hi, L.jobs.p, jobs, (size_t)n * sizeof(bsx_sw_job_t));
+		if (!f16) launch_ssw32_batch(L.st_hi, d->n_cu, d->ix, L.sc, (const uint8_t*)L.reads.p, (const bsx_sw_job_t*)L.jobs.p, (bsx_sw_res_t*)L.res.p, (unsigned int)n);
+		else if (!launch_swl16_batch(L.st_hi, d->n_cu, d->ix, L.sc, (const uint8_t*)L.reads.p, (const bsx_sw_job_t*)L.jobs.p, (bsx_sw_res_t*)L.res.p, (unsigned int)n, L.scratch.p))
+			return BSX_E_ARG;   // scoring options the packed kernel cannot hold (ssw16_bound.h): nothing was launched
+		HIPCHK(hipGetLastError());
+		D2H(L.st_hi, res, L.res.p, (size_t)n * sizeof(bsx_sw_res_t));
+		return BSX_OK;
+	}
 	// byte-sized jobs (KSW_XBYTE, queries of up to 256 columns: mate rescue of ordinary reads) go four to a wavefront through the striped
 	// kernel (k_swl.hip), ordered by stripe count and then by target length, longest first, so that the four jobs of a wavefront are alike;
 	// the others a wavefront each (k_sw.hip), by padded query length: up to 256, 1024, 3072 columns
