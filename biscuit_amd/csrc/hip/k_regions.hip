@@ -1350,7 +1350,10 @@ struct RgC2rHT {
 	static constexpr size_t slab_bytes() { return (size_t)XRG * sizeof(bsx_region_t); }
 };
 typedef RgC2rHT<RG_QCAP, RG_WIN, 1024, 1024> RgC2rH;   // 27 KB of LDS: five workgroups of one wave per CU
-typedef RgC2rHT<RG_QCAP_LONG, 1536, 1024, 1024> RgC2rHL;   // reads up to a kilobase: what k_c2r<RgC2rL> declines (64 regions, 256 seeds a list) -- chained on the host until round 6
+// (8192 regions: in a sequence whose every tier exports this launch is the last maker of regions, and the last HBM tier exports up to RgHuge::CCAP
+// chains -- with 1024, a strand search of 1025 regions under the seed filter, or of a kilobase read, was left to the caller; only the slab grows)
+typedef RgC2rHT<RG_QCAP_LONG, 1536, 1024, 8192> RgC2rHL;   // reads up to a kilobase: what k_c2r<RgC2rL> declines (64 regions, 256 seeds a list) -- chained on the host until round 6
+static_assert(RgC2rHL::XREGS == RgHuge::CCAP, "the last chains -> regions launch of an exporting sequence holds a region for every chain the last tier can export");
 typedef RgC2rT<RG_QCAP, RG_WIN, 256, 256> RgC2rB;   // reads inside repeat families: up to 256 regions of a strand search, 256 seeds of a chain (22 KB: seven waves per CU); for what k_c2r<RgC2r> declines   // reads up to a kilobase: a chain's window is the read plus its two gaps, a true chain has a few hundred seeds
 
 template <bool PK = false, typename WT>   // PK: as in rg_task (tables for reads of up to 256 bases only)
@@ -2345,7 +2348,7 @@ void launch_order_list(hipStream_t st, int *list, const unsigned int *count, con
 }
 
 size_t regions_slab_bytes(int tier) { return tier == 2 ? sizeof(RgBig) : sizeof(RgHuge); }
-size_t c2r_hbm_slab_bytes(void) { return RgC2rH::slab_bytes() * C2R_WPB; }   // per workgroup of launch_c2r(.., RG_C2R_H / RG_C2R_HL)
+size_t c2r_hbm_slab_bytes(bool long_form) { return (long_form ? RgC2rHL::slab_bytes() : RgC2rH::slab_bytes()) * C2R_WPB; }   // per workgroup of launch_c2r(.., RG_C2R_H) / (.., RG_C2R_HL)
 
 // the launchers unpack the common arguments (RgLaunch) into the kernels' parameter lists
 #define RG_COMMON_ *G.ix, *G.sc, *G.P, G.reads, G.tasks
@@ -2386,7 +2389,7 @@ void launch_c2r(hipStream_t st, int grid, const RgLaunch &G, const RgXPoolArg &X
                 int quota, RgC2rForm form, void *slab)
 {
 	RgXPool X = rgx_pool(&XA);
-	// the forms with their tables in LDS: `grid` counts groups of four waves; in HBM: workgroups, with c2r_hbm_slab_bytes() of `slab` each
+	// the forms with their tables in LDS: `grid` counts groups of four waves; in HBM: workgroups, with c2r_hbm_slab_bytes(form == RG_C2R_HL) of `slab` each
 #define RG_C2R_(TAB, OCC, GRID, SLAB, ...) hipLaunchKernelGGL((k_c2r<TAB, OCC, ##__VA_ARGS__>), dim3(GRID), dim3(64 * C2R_WPB), 0, st, RG_COMMON_, X, RG_OUT_, cursor, next_list, next_count, G.counters, quota, (unsigned char*)(SLAB))
 	// (G.ext_pk: the instantiations whose extension rows are packed 16-bit; the forms for long reads have none)
 	if (G.ext_pk && form == RG_C2R_H) RG_C2R_(RgC2rH, 2, grid, slab, true);

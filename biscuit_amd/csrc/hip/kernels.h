@@ -138,11 +138,11 @@ void launch_regions_mid(hipStream_t st, int grid, const RgLaunch &G, const int *
 enum RgC2rForm { RG_C2R,      // RgC2r: ordinary chunks
                  RG_C2R_L,    // RgC2rL: chunks with long reads or the seed filter
                  RG_C2R_B,    // RgC2rB: larger LDS tables, for what RG_C2R declines
-                 RG_C2R_H,    // RgC2rH: the large tables in HBM (`slab` = grid x c2r_hbm_slab_bytes()), for what RG_C2R_B declines
-                 RG_C2R_HL }; // RgC2rHL: the same for what RG_C2R_L declines
+                 RG_C2R_H,    // RgC2rH: the large tables in HBM (`slab` = grid x c2r_hbm_slab_bytes(false)), for what RG_C2R_B declines
+                 RG_C2R_HL }; // RgC2rHL: the same for what RG_C2R_L declines (`slab` = grid x c2r_hbm_slab_bytes(true))
 void launch_c2r(hipStream_t st, int grid, const RgLaunch &G, const RgXPoolArg &X, unsigned int *cursor, int *next_list, unsigned int *next_count,
                 int quota, RgC2rForm form = RG_C2R, void *slab = nullptr);
-size_t c2r_hbm_slab_bytes(void);
+size_t c2r_hbm_slab_bytes(bool long_form);
 // C3 between the tiers and launch_c2r: the seed-SW filter of the exported strand searches it applies to (mem_flt_chained_seeds, memchain.c:537-568)
 void launch_seedsw(hipStream_t st, int grid, int n_cu, const RgLaunch &G, const RgXPoolArg &XA, unsigned int *cursor, unsigned int *count_cursor,
                    void *jobs, unsigned int job_cap);

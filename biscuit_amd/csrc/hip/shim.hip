@@ -928,7 +928,8 @@ static int rg_plan(RgBatch &B)
 	TRY(L.qpack.reserve(seedt_pack_bytes(n)));
 	TRY(L.regs.reserve((size_t)B.regs_cap * sizeof(bsx_region_t)));
 	TRY(L.regmeta.reserve((size_t)n * 49 + 64));
-	TRY(L.c2rslab.reserve((size_t)B.c2rh_grid * c2r_hbm_slab_bytes()));
+	// (an exporting sequence's last chains -> regions launch, RG_C2R_HL on 2 workgroups per CU, has the larger slabs)
+	TRY(L.c2rslab.reserve(std::max((size_t)B.c2rh_grid * c2r_hbm_slab_bytes(false), B.export_all ? (size_t)d->n_cu * 2 * c2r_hbm_slab_bytes(true) : (size_t)0)));
 	TRY(L.slabs.reserve((size_t)B.big_grid * 6 * regions_slab_bytes(2)));   // (the exporting form runs three workgroups per CU)
 	TRY(L.slabs3.reserve((size_t)B.huge_grid * 4 * regions_slab_bytes(3)));
 	// one u64 per seed occurrence of the chunk: ~125 per strand search against an hg38-sized genome (a 3-letter 19-mer has random

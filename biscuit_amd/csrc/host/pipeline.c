@@ -1344,6 +1344,52 @@ out:
 	return rc;
 }
 
+/* test hook: the front half's host path -- what every declined strand search takes -- over the given backend, for strand searches given as the
+ * batch seams take them (views into the read buffer buf): host_path with the identity map, every task seeded here.  Regions of task t, in list
+ * order, as the device's record: out[off[t] .. off[t] + cnt[t]); returns BSX_OK, or BSX_E_ARG when out (cap records) is too short -- off[n]
+ * is then the number needed */
+BSX_API int bsx_hook_front_regions(const bsx_backend_t *be, const bsx_opt_t *opt, const bsx_index_t *idx, const uint8_t *buf, size_t n_buf,
+                                   int n_tasks, const bsx_seed_task_t *tasks, bsx_region_t *out, int64_t cap, int64_t *off, int32_t *cnt)
+{
+	chunk_t *C = (chunk_t*)calloc(1, sizeof(chunk_t));
+	int rc, t;
+	int64_t at = 0;
+	size_t k;
+	C->be_copy = *be; C->be = &C->be_copy; C->opt = opt; C->idx = idx; C->nt = bsx_host_threads(opt); C->arena_set = -1;
+	C->be_copy.regions_batch = 0;      /* (host_path calls the batch seams only; its diagnostic lines read a regions batch's statuses, which do not exist here) */
+	C->n_tasks = n_tasks;
+	C->tasks = (c2r_t*)calloc((size_t)n_tasks + 1, sizeof(c2r_t));
+	C->stasks = (bsx_seed_task_t*)malloc(sizeof(bsx_seed_task_t) * ((size_t)n_tasks + 1));
+	C->hmap = (int*)malloc(sizeof(int) * ((size_t)n_tasks + 1));
+	for (t = 0; t < n_tasks; ++t) {
+		c2r_t *T = &C->tasks[t];
+		C->stasks[t] = tasks[t]; C->hmap[t] = t;
+		T->read_idx = t; T->parent = tasks[t].parent; T->qoff = tasks[t].qoff; T->l_query = tasks[t].len; T->query = buf + tasks[t].qoff;
+	}
+	C->n_host = n_tasks;
+	rc = be->set_opt(be->ctx, opt);
+	if (rc == BSX_OK) rc = be->set_reads(be->ctx, buf, n_buf);
+	if (rc == BSX_OK) rc = host_path(C, n_tasks, 0, 0);
+	for (t = 0; t < n_tasks; ++t) {
+		c2r_t *T = &C->tasks[t];
+		off[t] = at; cnt[t] = (int32_t)T->regs.n;
+		for (k = 0; k < T->regs.n; ++k, ++at) {
+			const reg_t *r = &T->regs.a[k];
+			bsx_region_t *d;
+			if (rc != BSX_OK || at >= cap) continue;
+			d = &out[at];
+			memset(d, 0, sizeof(*d));
+			d->rb = r->rb; d->re = r->re; d->qb = r->qb; d->qe = r->qe; d->rid = r->rid; d->score = r->score; d->truesc = r->truesc;
+			d->w = r->w; d->seedcov = r->seedcov; d->seedlen0 = r->seedlen0; d->frac_rep = r->frac_rep; d->bss = r->bss; d->parent = r->parent;
+		}
+		bsx_cvec_free(T->regs);
+	}
+	off[n_tasks] = at;
+	if (rc == BSX_OK && at > cap) rc = BSX_E_ARG;
+	free(C->tasks); free(C->stasks); free(C->hmap); free(C);
+	return rc;
+}
+
 static int chunk_merge(chunk_t *C);
 /* front half: clipping, strand searches, seeding .. regions of every strand search (mem_align1_core's first part,
  * lib/aln/bwamem.c:183-208, for the whole chunk) */

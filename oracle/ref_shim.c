@@ -367,3 +367,77 @@ API int ref_sam_hdr(int n_seqs, const char **names, const int *lens, const char 
 	fclose(tmp);
 	return (int)sz;
 }
+
+/* ---------------- seeds -> chains -> regions of one strand search (memchain.c) ---------------- */
+#include "memchain.h"
+
+/* bwa_idx_load (bwa.c:556): both FM indices, annotation and pac from <prefix>.{par,dau}.{bwt,sa} + <prefix>.bis.{ann,amb,pac} */
+API void *ref_idx_load(const char *prefix) { return bwa_idx_load(prefix, BWA_IDX_ALL); }
+API void ref_idx_free(void *h) { bwa_idx_destroy((bwaidx_t*)h); }
+
+/* every bwt_sa call of memchain.o arrives here (-Wl,--wrap=bwt_sa, oracle/Makefile): mem_chain looks one occurrence up per call
+ * (memchain.c:334), so the count is the number of occurrences it visited */
+extern bwtint_t __real_bwt_sa(const bwt_t *bwt, bwtint_t k);
+static int64_t g_sa_calls;
+bwtint_t __wrap_bwt_sa(const bwt_t *bwt, bwtint_t k) { ++g_sa_calls; return __real_bwt_sa(bwt, k); }
+
+/* The body of mem_align1_core (bwamem.c:183-208) for one read and one parent, with the reference's own functions: bseq_bsconvert,
+ * mem_chain (memchain.c:268), mem_chain_flt (:406), mem_flt_chained_seeds (:537), mem_chain2region (:874).  opt = mem_opt_init()
+ * with min_seed_len, min_chain_weight and max_occ replaced.
+ *   regs: up to cap regions x 12 int64 = rb, re, qb, qe, rid, score, truesc, w, seedcov, seedlen0, bits of frac_rep, bss
+ *   cnt[10] = regions, intervals, occurrences visited (bwt_sa calls of mem_chain), sum over intervals of min(x[2], max_occ),
+ *             chains before the filter, chains with more than one seed or with seeds_extra, chains after the filter,
+ *             two chains share a start (0/1), most seeds in one list of a chain, intervals with x[2] > max_occ
+ * returns the number of regions (all of them counted, the first cap written) */
+API int ref_regions(void *h, int l_seq, const uint8_t *seq, int parent, int min_seed_len, int min_chain_weight, int max_occ,
+                    int64_t *regs, int cap, int64_t cnt[10])
+{
+	bwaidx_t *idx = (bwaidx_t*)h;
+	mem_opt_t *o = mem_opt_init();
+	bwtintv_cache_t *cache = bwtintv_cache_init();
+	bseq1_t s;
+	mem_chain_v ch;
+	mem_alnreg_v rv;
+	size_t i;
+	memset(&s, 0, sizeof(s)); memset(&rv, 0, sizeof(rv)); memset(cnt, 0, 10 * sizeof(int64_t));
+	o->min_seed_len = min_seed_len; o->min_chain_weight = min_chain_weight; o->max_occ = max_occ;
+	s.l_seq = l_seq; s.seq = (uint8_t*)seq; s.name = (char*)"r";
+	bseq_bsconvert(&s, (uint8_t)parent);
+	g_sa_calls = 0;
+	ch = mem_chain(o, idx->bwt, idx->bns, &s, cache, (uint8_t)parent);
+	cnt[2] = g_sa_calls;
+	cnt[1] = (int64_t)cache->mem.n;
+	if (l_seq < min_seed_len) cnt[1] = 0;      /* mem_chain returned before seeding (memchain.c:280): the cache is untouched */
+	for (i = 0; i < (size_t)cnt[1]; ++i) {
+		uint64_t n = cache->mem.a[i].x[2];
+		cnt[3] += (int64_t)(n < (uint64_t)max_occ ? n : (uint64_t)max_occ);
+		cnt[9] += n > (uint64_t)max_occ;
+	}
+	cnt[4] = (int64_t)ch.n;
+	for (i = 0; i < ch.n; ++i) {
+		const mem_chain_t *c = &ch.a[i];
+		cnt[5] += c->seeds.n > 1 || c->seeds_extra.n > 0;
+		if (i && ch.a[i - 1].pos == c->pos) cnt[7] = 1;      /* (the B-tree's in-order walk: equal starts are neighbours) */
+		if ((int64_t)c->seeds.n > cnt[8]) cnt[8] = (int64_t)c->seeds.n;
+		if ((int64_t)c->seeds_extra.n > cnt[8]) cnt[8] = (int64_t)c->seeds_extra.n;
+	}
+	mem_chain_flt(o, &ch);
+	cnt[6] = (int64_t)ch.n;
+	mem_flt_chained_seeds(o, idx->bns, idx->pac, &s, &ch, (uint8_t)parent);
+	mem_chain2region(o, idx->bns, idx->pac, &s, (uint8_t)parent, &ch, &rv);
+	cnt[0] = (int64_t)rv.n;
+	for (i = 0; i < rv.n && (int)i < cap; ++i) {
+		const mem_alnreg_t *r = &rv.a[i];
+		int64_t *p = regs + 12 * i;
+		uint32_t fb;
+		memcpy(&fb, &r->frac_rep, 4);
+		p[0] = r->rb; p[1] = r->re; p[2] = r->qb; p[3] = r->qe; p[4] = r->rid; p[5] = r->score; p[6] = r->truesc; p[7] = r->w;
+		p[8] = r->seedcov; p[9] = r->seedlen0; p[10] = (int64_t)fb; p[11] = r->bss;
+	}
+	free_mem_chain_v(ch);
+	free(rv.a);
+	free(s.bisseq[0]); free(s.bisseq[1]);
+	bwtintv_cache_destroy(cache);
+	free(o);
+	return (int)rv.n;
+}
