@@ -654,6 +654,52 @@ static void seed_asm_worker(void *data, long i, int tid)
 	if (n > 1) std::sort(dst, dst + n, intv_info_lt);
 }
 
+// The first seeding pass of a chunk: list lengths, where the lists go, budget, quota, grid and slabs -- what rg_plan gives the chunk-wide launch of
+// bsx_regions_batch, and what bsx_seed_batch launches with under the setting seed_batch_form=chunk (tests: the production launch, list for list).
+struct SeedPlan {
+	int mem_cap, list_cap; bool direct;
+	unsigned long long direct_n, dense_cap;
+	int quota, trip_budget, budget2_mul, n_slabs, grid;
+	size_t scratch_bytes;
+};
+static SeedPlan seed_plan(const bsx_device_t *d, int64_t n, int max_len)
+{
+	SeedPlan S;
+	// $BSX_SEED_MEM_CAP (tests): a short first-pass list, so that ordinary reads take the seeded-again path too
+	S.mem_cap = bsx_tune_is_set("seed_mem_cap") ? std::max(4, (int)bsx_tune_long("seed_mem_cap", 64)) : std::max(64, max_len); S.list_cap = max_len + 2;
+	const unsigned long long lf = (unsigned long long)std::max(1, (max_len + 149) / 150);   // pools are sized per 150 bases of read
+	// the interval lists: strand search t's own stretch of mem_cap entries (k_seedt writes them where they stay), then room for the lists of the
+	// strand searches seeded again with longer lists, which go one behind the other from the cursor
+	S.direct = bsx_tune_long("seed_direct", 1) != 0 && !bsx_tune_is_set("seed_form")
+	           && (unsigned long long)n * (unsigned long long)S.mem_cap <= (768ull << 20);   // (24 GB of lists: a chunk of short reads with one very long one keeps the lists one behind the other)   // ($BSX_SEED_DIRECT=0: one list behind the other, copied there when a strand search is done)
+	S.direct_n = S.direct ? (unsigned long long)n * (unsigned long long)S.mem_cap : 0;
+	S.dense_cap = S.direct_n + (unsigned long long)n * (S.direct ? 16 : 96) * lf + (1u << 20);
+	// workgroups with a bounded life (a few tasks per lane / wave), many more of them than fit on the chip
+	S.quota = (int)bsx_tune_long("seed_quota", bsx_tune_is_set("seed_form") ? 1 : 0);   // strand searches per lane, 0 = lanes take them until none is left.  The table form (k_seedt.hip) runs persistent lanes: a lane that is done takes the next strand search in the same trip (measured at hg38 scale: 68 ms against 97 with one per lane and 86 with four); the kernel without the table does best with one (292 ms against 335 with two and 359 persistent: its lanes then move through the seeding passes together)
+	// extensions after which the first seeding pass hands a strand search to the second one (0: never)
+	// (4096 for reads of 150 bases, which need ~1.2 k; in proportion for longer ones)
+	S.trip_budget = std::max(0, (int)bsx_tune_long("seed_trip_budget", 4096));   // (the kernel scales it per 256 bases of read)
+	S.budget2_mul = std::max(1, (int)bsx_tune_long("seed_budget2", 8));   // the second pass's budget, in first-pass budgets
+	S.n_slabs = d->n_cu * 16;
+	const int seed_wpc = 16;   // quota 0 = persistent waves, sixteen per CU
+	S.grid = S.quota > 0 ? (int)((n + 256LL * S.quota - 1) / (256LL * S.quota))
+	                     : (int)((std::min<int64_t>((n + 63) / 64, (int64_t)d->n_cu * seed_wpc) + 3) / 4);
+	S.scratch_bytes = (size_t)S.n_slabs * 64 * seed_lane_bytes(S.mem_cap, S.list_cap);
+	return S;
+}
+
+// a seeding pass over n2 strand searches whose lists overflowed: a lane each, lists eight times as long
+struct SeedAgain { int grid; long long cap; size_t scratch; bool fits; };
+static SeedAgain seed_again_size(size_t n2, int mem_cap, int list_cap, int n_slabs)
+{
+	SeedAgain s;
+	s.grid = (int)((n2 + 255) / 256);
+	s.cap = std::max<long long>((long long)mem_cap * 8, 1024);
+	s.scratch = (size_t)s.grid * 256 * seed_lane_bytes(s.cap, list_cap);
+	s.fits = s.grid * 4 <= n_slabs && s.scratch <= ((size_t)24 << 30);   // (one slab per four waves of the pass: n_slabs bounds it)
+	return s;
+}
+
 static int lane_seed_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int64_t n, const bsx_seed_task_t *tasks,
                            bsx_intv_t **out, int64_t *out_cap, int64_t *out_off)
 {
@@ -681,36 +727,61 @@ static int lane_seed_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int6
 	std::vector<int64_t> redo_index;
 	const bsx_intv_t *h_dense = nullptr;
 	std::vector<bsx_intv_t> dense_sub;
+	// seed_batch_form=chunk (tests): the first launch as the chunk-wide one of bsx_regions_batch (seed_plan: its list length, lists written where
+	// they stay, budget, quota, grid and slabs), what it leaves seeded again as that call's later passes do it (a lane each, lists eight times as
+	// long; the second pass with seed_budget2 first-pass budgets, the ones after it without a budget), the direct lists fetched through
+	// launch_gather_lists
+	const char *form = bsx_tune_str("seed_batch_form");
+	if (form && strcmp(form, "chunk") && strcmp(form, "batch")) { fprintf(stderr, "[bsx-hip] seed_batch_form=%s: batch or chunk\n", form); return BSX_E_ARG; }
+	const bool chunk = form && !strcmp(form, "chunk");
+	const SeedPlan SP = seed_plan(d, n, max_len);
+	unsigned long long *const ctr0 = dev_counters(L);
 
 	for (int round = 0; round < 6; ++round) {
 		const bsx_seed_task_t *cur = tasks; int64_t cn = n;
+		const int prev_cap = mem_cap;
 		if (round > 0) {
 			if (todo.empty()) break;
 			sub.resize(todo.size());
 			for (size_t i = 0; i < todo.size(); ++i) sub[i] = tasks[todo[i]];
 			cur = sub.data(); cn = (int64_t)sub.size();
-			mem_cap *= 8; dense_cap = (unsigned long long)cn * mem_cap + 4096;
+			if (!chunk) { mem_cap *= 8; dense_cap = (unsigned long long)cn * mem_cap + 4096; }
 		}
 		int list_cap = max_len + 2;
-		int waves = (int)std::min<int64_t>((cn + 63) / 64, (int64_t)d->n_cu * 16);
-		const size_t per_lane = seed_lane_bytes(mem_cap, list_cap);
-		waves = (int)std::max<size_t>(4, std::min<size_t>((size_t)waves, ((size_t)8 << 30) / (64 * per_lane)));   // (long reads seeded again with long lists: fewer waves, not tens of GB)
-		int grid = (waves + 3) / 4;
-		size_t lanes = (size_t)grid * 256;
-		size_t scratch_bytes = lanes * per_lane;
+		int grid, n_slabs, quota = 0, budget = 0; size_t scratch_bytes; bool direct = false; unsigned long long cursor0 = 0;
+		if (!chunk) {
+			int waves = (int)std::min<int64_t>((cn + 63) / 64, (int64_t)d->n_cu * 16);
+			const size_t per_lane = seed_lane_bytes(mem_cap, list_cap);
+			waves = (int)std::max<size_t>(4, std::min<size_t>((size_t)waves, ((size_t)8 << 30) / (64 * per_lane)));   // (long reads seeded again with long lists: fewer waves, not tens of GB)
+			grid = (waves + 3) / 4; n_slabs = grid * 4;
+			scratch_bytes = (size_t)grid * 256 * per_lane;
+		} else if (round == 0) {
+			mem_cap = SP.mem_cap; list_cap = SP.list_cap; dense_cap = SP.dense_cap; direct = SP.direct; cursor0 = SP.direct_n;
+			grid = SP.grid; n_slabs = SP.n_slabs; quota = SP.quota; budget = SP.trip_budget; scratch_bytes = SP.scratch_bytes;
+		} else {
+			const SeedAgain sa = seed_again_size((size_t)cn, prev_cap, list_cap, SP.n_slabs);
+			if (!sa.fits || sa.cap > 0x7fffffff) { fprintf(stderr, "[bsx-hip] seed_batch: %lld strand searches to be seeded again with lists of %lld entries do not fit\n", (long long)cn, sa.cap); return BSX_E_NOMEM; }
+			mem_cap = (int)sa.cap; dense_cap = (unsigned long long)cn * mem_cap + 4096;
+			grid = sa.grid; n_slabs = sa.grid * 4; scratch_bytes = sa.scratch;
+			budget = round == 1 ? SP.trip_budget * SP.budget2_mul : 0;
+		}
 		if ((rc = L.scratch.reserve(scratch_bytes)) != BSX_OK) return rc;
 		if ((rc = L.jobs.reserve((size_t)cn * sizeof(bsx_seed_task_t))) != BSX_OK) return rc;
 		if ((rc = L.out.reserve((size_t)dense_cap * sizeof(DevIntv))) != BSX_OK) return rc;
 		if ((rc = L.aux.reserve((size_t)cn * 12 + 64)) != BSX_OK) return rc;
 		if ((rc = L.qpack.reserve(seedt_pack_bytes(cn))) != BSX_OK) return rc;
 		long long *d_off = (long long*)L.aux.p; int *d_n = (int*)((char*)L.aux.p + (size_t)cn * 8);
-		unsigned long long *ctr = dev_counters(L); CtrShared::Seed *sc = &ctr_shared(L)->seed;
+		unsigned long long *ctr = ctr0; CtrShared::Seed *sc = &ctr_shared(L)->seed;
 		HIPCHK(hipMemcpyAsync(L.jobs.p, cur, (size_t)cn * sizeof(bsx_seed_task_t), hipMemcpyHostToDevice, L.st));
 		HIPCHK(hipMemsetAsync(sc, 0, sizeof(*sc), L.st));   // the interval cursor and the task cursor
+		if (chunk) {
+			HIPCHK(hipMemsetAsync(ctr + CTR_OVERFLOW, 0, 8, L.st));   // (this pass's count of strand searches to be seeded again)
+			if (cursor0) H2D(L.st, &sc->intv_cursor, &cursor0, 8);   // the cursor starts behind the strand searches' own stretches
+		}
 		HIPCHK(hipEventRecord(L.ev_timed_begin, L.st));
 		launch_seed(L.st, grid, d->ix, (const uint8_t*)L.reads.p, (const bsx_seed_task_t*)L.jobs.p, (int)cn, P,
 		            (DevIntv*)L.scratch.p, list_cap, mem_cap, (DevIntv*)L.out.p, dense_cap, &sc->intv_cursor, d_off, d_n,
-		            &sc->task_cursor, ctr, 0, (unsigned int*)L.slabflags.p, grid * 4, 0, 0, (uint32_t*)L.qpack.p);
+		            &sc->task_cursor, ctr, quota, (unsigned int*)L.slabflags.p, n_slabs, budget, 0, (uint32_t*)L.qpack.p, direct ? 0ull : ~0ull);
 		HIPCHK(hipEventRecord(L.ev_timed_end, L.st));
 		if ((rc = finish_timed(L, KT_SEED_OTHER)) != BSX_OK) return rc;   // the batch form, for what the host chains: not the chunk-wide launch of KT_SEED
 		std::vector<long long> r_off((size_t)cn); std::vector<int> r_n((size_t)cn);
@@ -719,11 +790,37 @@ static int lane_seed_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int6
 		D2H(L.st, r_n.data(), d_n, (size_t)cn * 4);
 		D2H(L.st, &used, &sc->intv_cursor, 8);
 		if (used > dense_cap) used = dense_cap;
+		if (chunk && bsx_phases()) {
+			unsigned long long n_over = 0;
+			D2H(L.st, &n_over, ctr + CTR_OVERFLOW, 8);
+			fprintf(stderr, "[M::seed_batch] chunk form, pass %d: %lld strand searches, lists of %d entries%s, budget %d, quota %d, %d workgroups, %d slabs: %llu left to be seeded again\n",
+			        round + 1, (long long)cn, mem_cap, direct ? " written where they stay" : "", budget, quota, grid, n_slabs, n_over);
+		}
+		if (direct) { // the lists lie a strand search's stretch apart: gathered on the device, one copy (rg_declined does the same)
+			std::vector<long long> which, doff;
+			long long tot = 0;
+			for (int64_t i = 0; i < cn; ++i) if (r_n[i] > 0) { which.push_back(i); doff.push_back(tot); tot += r_n[i]; }
+			if (tot > 0) {
+				const size_t nb = which.size() * 8;
+				if ((rc = L.gath.reserve(2 * nb + (size_t)tot * sizeof(bsx_intv_t) + 64)) != BSX_OK) return rc;
+				H2D(L.st, L.gath.p, which.data(), nb);
+				H2D(L.st, (char*)L.gath.p + nb, doff.data(), nb);
+				DevIntv *gd = (DevIntv*)((char*)L.gath.p + 2 * nb);
+				launch_gather_lists(L.st, (const DevIntv*)L.out.p, d_off, d_n, (const long long*)L.gath.p, (const long long*)((char*)L.gath.p + nb), (long long)which.size(), gd);
+				if ((rc = L.hstage.reserve((size_t)tot * sizeof(bsx_intv_t) + 64)) != BSX_OK) return rc;
+				D2H(L.st, L.hstage.p, gd, (size_t)tot * sizeof(bsx_intv_t));
+				for (size_t j = 0; j < which.size(); ++j) r_off[which[j]] = doff[j];
+			}
+			h_dense = (const bsx_intv_t*)L.hstage.p;
+			used = 0;   // (nothing more to fetch from the pool)
+		}
 		std::vector<int64_t> next;
 		if (round == 0) {
-			if ((rc = L.hstage.reserve((size_t)used * sizeof(bsx_intv_t) + 64)) != BSX_OK) return rc;
-			if (used) D2H(L.st, L.hstage.p, L.out.p, (size_t)used * sizeof(bsx_intv_t));
-			h_dense = (const bsx_intv_t*)L.hstage.p;
+			if (!direct) {
+				if ((rc = L.hstage.reserve((size_t)used * sizeof(bsx_intv_t) + 64)) != BSX_OK) return rc;
+				if (used) D2H(L.st, L.hstage.p, L.out.p, (size_t)used * sizeof(bsx_intv_t));
+				h_dense = (const bsx_intv_t*)L.hstage.p;
+			}
 			for (int64_t i = 0; i < n; ++i) { h_off[i] = r_off[i]; h_n[i] = r_n[i]; if (r_n[i] < 0) next.push_back(i); }
 		} else {
 			dense_sub.resize((size_t)used);
@@ -790,18 +887,6 @@ static void seq_carve(TierSeq &S, size_t n, Bump &lists, Bump &meta, Bump &xmeta
 	S.G.pos_off = posoff.take<long long>(n);
 	S.cls = meta.take<unsigned char>(n);
 	S.G.task_off = S.offs; S.G.task_n = S.cnts; S.G.n_tasks = (int)n;
-}
-
-// a seeding pass over n2 strand searches whose lists overflowed: a lane each, lists eight times as long
-struct SeedAgain { int grid; long long cap; size_t scratch; bool fits; };
-static SeedAgain seed_again_size(size_t n2, int mem_cap, int list_cap, int n_slabs)
-{
-	SeedAgain s;
-	s.grid = (int)((n2 + 255) / 256);
-	s.cap = std::max<long long>((long long)mem_cap * 8, 1024);
-	s.scratch = (size_t)s.grid * 256 * seed_lane_bytes(s.cap, list_cap);
-	s.fits = s.grid * 4 <= n_slabs && s.scratch <= ((size_t)24 << 30);   // (one slab per four waves of the pass: n_slabs bounds it)
-	return s;
 }
 
 // what the stages of one lane_regions_batch call pass along: the call's arguments, the plan (sizes, caps, grids, the tune settings read once),
@@ -876,30 +961,19 @@ static int rg_params(RgBatch &B)
 static int rg_plan(RgBatch &B)
 {
 	Lane &L = B.L; bsx_device_t *d = B.d; const int64_t n = B.n; const int max_len = B.max_len;
-	// $BSX_SEED_MEM_CAP (tests): a short first-pass list, so that ordinary reads take the seeded-again path too
-	B.mem_cap = bsx_tune_is_set("seed_mem_cap") ? std::max(4, (int)bsx_tune_long("seed_mem_cap", 64)) : std::max(64, max_len); B.list_cap = max_len + 2;
+	// the first seeding pass (seed_plan): list lengths, where the lists go, budgets, quota, grid and slabs
+	const SeedPlan SP = seed_plan(d, n, max_len);
+	B.mem_cap = SP.mem_cap; B.list_cap = SP.list_cap;
 	// room for the interval lists (32 B each) and regions (56 B each) of the whole chunk; repeat-rich genomes average
 	// dozens of intervals per strand search, and HBM is not the scarce resource here
 	const unsigned long long lf = (unsigned long long)std::max(1, (max_len + 149) / 150);   // pools are sized per 150 bases of read
-	// the interval lists: strand search t's own stretch of mem_cap entries (k_seedt writes them where they stay), then room for the lists of the
-	// strand searches seeded again with longer lists, which go one behind the other from the cursor
-	B.seed_direct = bsx_tune_long("seed_direct", 1) != 0 && !bsx_tune_is_set("seed_form")
-	                && (unsigned long long)n * (unsigned long long)B.mem_cap <= (768ull << 20);   // (24 GB of lists: a chunk of short reads with one very long one keeps the lists one behind the other)   // ($BSX_SEED_DIRECT=0: one list behind the other, copied there when a strand search is done)
-	B.direct_n = B.seed_direct ? (unsigned long long)n * (unsigned long long)B.mem_cap : 0;
-	B.dense_cap = B.direct_n + (unsigned long long)n * (B.seed_direct ? 16 : 96) * lf + (1u << 20); B.regs_cap = (unsigned long long)n * 24 + 65536;   // (a read inside a repeat family has dozens of regions: 6 per strand search overflowed on an hg38-like genome)
-	// workgroups with a bounded life (a few tasks per lane / wave), many more of them than fit on the chip
-	B.seed_quota = (int)bsx_tune_long("seed_quota", bsx_tune_is_set("seed_form") ? 1 : 0);   // strand searches per lane, 0 = lanes take them until none is left.  The table form (k_seedt.hip) runs persistent lanes: a lane that is done takes the next strand search in the same trip (measured at hg38 scale: 68 ms against 97 with one per lane and 86 with four); the kernel without the table does best with one (292 ms against 335 with two and 359 persistent: its lanes then move through the seeding passes together)
-	// extensions after which the first seeding pass hands a strand search to the second one (0: never)
-	// (4096 for reads of 150 bases, which need ~1.2 k; in proportion for longer ones)
-	B.trip_budget = std::max(0, (int)bsx_tune_long("seed_trip_budget", 4096));   // (the kernel scales it per 256 bases of read)
-	B.budget2_mul = std::max(1, (int)bsx_tune_long("seed_budget2", 8));   // the second pass's budget, in first-pass budgets
+	B.seed_direct = SP.direct; B.direct_n = SP.direct_n;
+	B.dense_cap = SP.dense_cap; B.regs_cap = (unsigned long long)n * 24 + 65536;   // (a read inside a repeat family has dozens of regions: 6 per strand search overflowed on an hg38-like genome)
+	B.seed_quota = SP.quota; B.trip_budget = SP.trip_budget; B.budget2_mul = SP.budget2_mul;
 	B.merge_min = bsx_tune_long("redo_merge_min", 4096);   // (tests: 1 = always merged, a huge number or a negative one = never)
 	B.reg_quota = std::max(1, (int)bsx_tune_long("regions_quota", 16));
-	B.n_slabs = d->n_cu * 16;
-	const int seed_wpc = 16;   // quota 0 = persistent waves, sixteen per CU
-	B.grid = B.seed_quota > 0 ? (int)((n + 256LL * B.seed_quota - 1) / (256LL * B.seed_quota))
-	                          : (int)((std::min<int64_t>((n + 63) / 64, (int64_t)d->n_cu * seed_wpc) + 3) / 4);
-	const size_t scratch_bytes = (size_t)B.n_slabs * 64 * seed_lane_bytes(B.mem_cap, B.list_cap);
+	B.n_slabs = SP.n_slabs; B.grid = SP.grid;
+	const size_t scratch_bytes = SP.scratch_bytes;
 	// the HBM tiers: workgroups of four waves over per-wave slabs; they are bound by the latency of their slabs, so what counts is waves in flight:
 	// three workgroups per CU for the first (its kernel is held to 168 VGPRs for that and spills: 710 -> 578 ms per chunk on the hg38-like genome
 	// all the same), one per CU for the second (1.3 MB of slab a wave; 222 -> 167 ms: a launch lasts as long as its largest strand search)

@@ -12,6 +12,7 @@ static knob_t g_knobs[] = {
 	{"seed_tab_k", "[from the text's size: 18 at 3.1 Gbp] levels of the table of k-mer intervals; 0: none", 0},
 	{"seed_mem_cap", "[max(64, longest read)] entries of a strand search's first-pass interval list (tests: short lists, so that ordinary reads are seeded again)", 0},
 	{"seed_direct", "[1] 0: interval lists copied behind each other instead of written where they stay", 0},
+	{"seed_batch_form", "[batch] chunk: bsx_seed_batch launches as the chunk-wide seeding pass of bsx_regions_batch does (its list length, lists written where they stay, budget, quota, grid and slabs; what is left seeded again with lists eight times as long) -- tests: the production launch, list for list", 0},
 	{"seed_quota", "[0 = persistent lanes; 1 for seed_form=classic] strand searches a lane of the seeding kernel takes", 0},
 	{"tier3_early", "[1] the last HBM tier's launch for what is known to need it when the occurrences are counted: on a stream of its own beside the other tiers; 0: behind them", 0},
 	{"tier3_order", "[1] the last HBM tier takes its strand searches longest first (by occurrences to visit); 0: in the order the tier before handed them on", 0},

@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, HERE)
 import simdata  # noqa: E402
 import oracle_lib  # noqa: E402
 from biscuit_amd.api import Index  # noqa: E402
@@ -248,45 +249,11 @@ for par in (0, 1):
 out["fm_k"] = ks
 
 # ---- K1+K2 as a whole: mem_collect_intv (memchain.c:50-106) is static in a file that does not build here, so its 20-line
-# driver is restated below over the REAL bwt_smem1a / bwt_seed_strategy1 (all FM work is the reference's); the result is
+# driver is restated (ref_collect.py) over the REAL bwt_smem1a / bwt_seed_strategy1 (all FM work is the reference's); the result is
 # what the seeding kernel must return for the read, interval for interval.  Default options (mem_opt_init).
-def collect_intv(par, conv, min_seed_len=19, split_factor=1.5, split_width=10, max_mem_intv=20, start_width=1):
-    L_ = len(conv)
-    split_len = int(min_seed_len * split_factor + .499)
-    mem = []
-    o1 = np.zeros(4 * 1024, np.uint64); r1 = C.c_int()
+from ref_collect import collect_intv  # noqa: E402  (tests/golden/ref_collect.py: shared with make_vectors_seed.py)
 
-    def smem1(x, mi):
-        n1 = R.ref_bwt_smem1a(H[par], H[1 - par], L_, P(conv, u8p), x, mi, C.c_uint64(0), P(o1, u64p), 1024, C.byref(r1))
-        assert n1 <= 1024
-        return [tuple(int(v) for v in o1[4 * i:4 * i + 4]) for i in range(n1)], r1.value
-    x = 0
-    while x < L_:                                    # pass 1 (memchain.c:65-73)
-        if conv[x] < 4:
-            got, x = smem1(x, start_width)
-            mem += [m for m in got if (m[3] & 0xffffffff) - (m[3] >> 32) >= min_seed_len]
-        else:
-            x += 1
-    for k in range(len(mem)):                        # pass 2 (memchain.c:76-85)
-        st, en = mem[k][3] >> 32, mem[k][3] & 0xffffffff
-        if en - st < split_len or mem[k][2] > split_width:
-            continue
-        got, _ = smem1((st + en) >> 1, mem[k][2] + 1)
-        mem += [m for m in got if (m[3] & 0xffffffff) - (m[3] >> 32) >= min_seed_len]
-    x = 0
-    a1 = np.zeros(4, np.uint64)
-    while x < L_:                                    # pass 3 (memchain.c:88-103)
-        if conv[x] < 4:
-            x = R.ref_bwt_seed_strategy1(H[par], H[1 - par], L_, P(conv, u8p), x, min_seed_len, max_mem_intv, P(a1, u64p))
-            if int(a1[2]) > 0:
-                mem.append(tuple(int(v) for v in a1))
-        else:
-            x += 1
-    mem.sort(key=lambda m: m[3])                     # ks_introsort(mem_intv): records with equal info are identical
-    return np.array(mem, np.uint64).reshape(-1, 4)
-
-
-fm_all = [collect_intv(int(fm_par[i][0]), fm_reads[i]) for i in range(len(fm_reads))]
+fm_all = [collect_intv(R, H, int(fm_par[i][0]), fm_reads[i]) for i in range(len(fm_reads))]
 out["fm_collect"], out["fm_coff"] = ragged([a.reshape(-1) for a in fm_all], np.uint64)
 
 # ---- I1: the record grammar (kseq_read, kseq.h:182-222, as instantiated by the reference in utils.c:53) on awkward inputs, the

@@ -103,7 +103,10 @@ def test_seed_overflow_path(small_index, port, device):
     """a poly-A read against a genome with a long A run is pathological; capacity retry must agree"""
     opt = default_opt()
     opt.max_mem_intv = 1 << 30
-    seqs = _reads(small_index, n_pairs=50, read_len=100, seed=9)
+    import seed_cases
+    homo = seed_cases.genome()[1]["homo"]      # the run of As of the designed seeding genome (tests/seed_cases.py)
+    seqs = _reads(small_index, n_pairs=50, read_len=100, seed=9) + [homo[:100].copy(), homo[:150].copy()]
+    assert (seqs[-1] == 0).all() and len(seqs[-1]) == 150
     buf, offs = simdata.read_buffer(seqs)
     tasks = _tasks(seqs, offs)
     for be in (port, device):
