@@ -182,7 +182,9 @@ k_global(DevIndex ix, DevScoring sc, const uint8_t *reads, const bsx_glb_job_t *
 			const bool staged = tlen <= tcap;
 			const int parent = J.use_ct, rev = J.tdir < 0;
 			#define MD_BASE(r) ((r) > 3 ? 'N' : (int)(((rev ? 0x41434754u : 0x54474341u) >> ((r) << 3)) & 0xffu))   /* "ACGT" / "TGCA" (bwa.c:297,345) */
-			#define MD_DIGITS(v) ((v) >= 10000 ? 5 : (v) >= 1000 ? 4 : (v) >= 100 ? 3 : (v) >= 10 ? 2 : 1)
+			/* decimal digits of any non-negative int, as kputw writes them (a run of matches is as long as the read: a hundred kilobases and more in the last class) */
+			#define MD_DIGITS(v) ((v) < 10 ? 1 : (v) < 100 ? 2 : (v) < 1000 ? 3 : (v) < 10000 ? 4 : (v) < 100000 ? 5 : (v) < 1000000 ? 6 : (v) < 10000000 ? 7 : \
+				(v) < 100000000 ? 8 : (v) < 1000000000 ? 9 : 10)
 			__threadfence_block();   // the CIGAR lane 0 wrote, read back below
 			WAVE_SYNC();
 			if (n_cigar > 0 && staged) {
@@ -261,7 +263,7 @@ k_global(DevIndex ix, DevScoring sc, const uint8_t *reads, const bsx_glb_job_t *
 					for (int pass = 0; pass < 2; ++pass) {
 						int x = 0, y = 0, u = 0, l = 0, n_mm = 0, n_gap = 0, n_conv = 0, n_ret = 0;
 						// decimal of the pending run of matches, then one character
-						#define MD_NUM(v) do { int v_ = (v), nd_ = v_ >= 10000 ? 5 : v_ >= 1000 ? 4 : v_ >= 100 ? 3 : v_ >= 10 ? 2 : 1; \
+						#define MD_NUM(v) do { int v_ = (v), nd_ = MD_DIGITS(v_); \
 							if (dst) { int t_ = v_; for (int d_ = nd_ - 1; d_ >= 0; --d_) { dst[l + d_] = (char)('0' + t_ % 10); t_ /= 10; } } l += nd_; } while (0)
 						#define MD_CHR(c) do { if (dst) dst[l] = (char)(c); ++l; } while (0)
 						for (int k = 0; k < n_cigar; ++k) {

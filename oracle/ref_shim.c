@@ -2,13 +2,15 @@
  *
  * Thin ctypes-friendly entry points onto the *real* reference functions of
  * zhou-lab/biscuit, compiled from the sources where they lie under
- * /root/reference/lib/aln (see oracle/Makefile).  Only reference files that
- * build without any stand-in header are used:
+ * /root/reference/lib/aln (see oracle/Makefile).  These reference files build
+ * without any stand-in header:
  *   bwt.c ksw.c utils.c is.c bwa.c bwamem.c  (+ ksort.h / kbtree.h templates)
- * memchain.c, mem_alnreg.c, mem_pair.c, mem_alnreg_format.c, bntseq.c,
- * bwtindex.c and align.c include un-vendored headers (wzmisc.h / encode.h,
- * huishenlab/utils@5f4aeab) and are therefore NOT buildable here; nothing in
- * this shim stands in for them.
+ * memchain.c and bntseq.c include un-vendored headers (wzmisc.h / encode.h,
+ * huishenlab/utils@5f4aeab) and are compiled over the two headers of
+ * oracle/standin/ (min on two ints for memchain.c; bntseq.c uses nothing of
+ * its header); ref_idx_load, ref_regions and ref_gen_cigar2 are their users.
+ * mem_alnreg.c, mem_pair.c, mem_alnreg_format.c, bwtindex.c and align.c are
+ * NOT built; nothing in this shim stands in for them.
  *
  * Nothing here computes anything itself: every function forwards to a
  * reference symbol (cited) and flattens its result into plain buffers.
@@ -440,4 +442,29 @@ API int ref_regions(void *h, int l_seq, const uint8_t *seq, int parent, int min_
 	bwtintv_cache_destroy(cache);
 	free(o);
 	return (int)rv.n;
+}
+
+/* ---------------- global alignment of a region with its tags (bwa.c) ---------------- */
+/* bis_bwa_gen_cigar2 (bwa.c:290) over the handle's pac and l_pac: banded global alignment of query against [rb, re) of the forward-reverse
+ * space, then NM / MD / ZC / ZR / bss_u from the CIGAR.  The reference appends the MD string (NUL-terminated) after the CIGAR words it
+ * returns: both are copied out.  out = {score, n_cigar, NM, ZC, ZR, bss_u, strlen(MD)}; the first cigar_cap words and md_cap bytes are
+ * written; returns 0, or -1 when the reference returned no CIGAR */
+API int ref_gen_cigar2(void *h, const int8_t *mat, int o_del, int e_del, int o_ins, int e_ins, int w_, int l_query, uint8_t *query,
+                       int64_t rb, int64_t re, int parent, int64_t out[7], uint32_t *cigar, int cigar_cap, char *md, int64_t md_cap)
+{
+	bwaidx_t *idx = (bwaidx_t*)h;
+	int score = 0, n_cigar = 0, NM = -1, bss_u = -1, i;
+	uint32_t ZC = 0, ZR = 0, *cg;
+	const char *s;
+	size_t l;
+	cg = bis_bwa_gen_cigar2(mat, o_del, e_del, o_ins, e_ins, w_, idx->bns->l_pac, idx->pac, l_query, query, rb, re, &score, &n_cigar, &NM, &ZC, &ZR, &bss_u, (uint8_t)parent);
+	out[0] = score; out[1] = n_cigar; out[2] = NM; out[3] = ZC; out[4] = ZR; out[5] = bss_u; out[6] = -1;
+	if (!cg) return -1;
+	for (i = 0; i < n_cigar && i < cigar_cap; ++i) cigar[i] = cg[i];
+	s = (const char*)(cg + n_cigar);
+	l = strlen(s);
+	out[6] = (int64_t)l;
+	if (md_cap > 0) { size_t c = l + 1 < (size_t)md_cap ? l + 1 : (size_t)md_cap; memcpy(md, s, c); }
+	free(cg);
+	return 0;
 }
