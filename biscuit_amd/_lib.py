@@ -88,7 +88,7 @@ class GlbTag(C.Structure):
 
 class Backend(C.Structure):  # bsx_backend_t (csrc/host/bsx_core.h)
     _fields_ = [("ctx", C.c_void_p), ("name", C.c_char_p)] + [(n, C.c_void_p) for n in
-                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p), ("sort_batch", C.c_void_p)]
+                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p), ("sort_batch", C.c_void_p), ("meth_batch", C.c_void_p)]
 
 
 class GlbCtx(C.Structure):  # bsx_glb_ctx_t: [strand hypothesis][A, C, G, T, N context][retained, converted]
@@ -112,6 +112,15 @@ class CovTable(C.Structure):  # bsx_cov_table_t
 
 class CovTables(C.Structure):  # bsx_cov_tables_t: [region * 4 + class * 2 + kind]; region: whole genome, top GC, bottom GC; class: all, q40; kind: bases, CpGs
     _fields_ = [("t", CovTable * 12), ("have_gc", C.c_int)]
+
+
+class MethJob(C.Structure):  # bsx_meth_job_t: what QcJob has (flags: QC_REVERSE, QC_READ2, the YD tag << 2), the quality mask's word offset in the pool, the mate overlap
+    _fields_ = [("fpos", C.c_int64), ("roff", C.c_uint32), ("rskip", C.c_int32), ("rlen", C.c_uint32), ("cig_off", C.c_uint32), ("n_cigar", C.c_uint32), ("flags", C.c_uint32),
+                ("qm_off", C.c_uint32), ("pad", C.c_uint32), ("ov_beg", C.c_int64), ("ov_end", C.c_int64)]
+
+
+class MethTables(C.Structure):  # bsx_meth_tables_t: per context CA, CC, CG, CT, CN the reported sites and the sum of their betas in thousandths
+    _fields_ = [("k", C.c_uint64 * 5), ("s", C.c_uint64 * 5)]
 
 
 class QcCounts(C.Structure):  # bsx_qc_counts_t: [CpG, CpH][read][position][converted, retained], the eight totals, confusion[tag * 4 + inferred]

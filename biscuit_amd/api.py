@@ -319,6 +319,37 @@ class Device(Batches):
         f.argtypes = [C.c_void_p]
         B.check(f(self.h), "bsx_cov_reset")
 
+    def meth_batch(self, jobs, pool):
+        """bsx_meth_batch: the columns of the jobs (array of _lib.MethJob's layout; pool: their CIGAR words and quality masks) added to the device's
+        four counters per position; the reads are those of set_reads"""
+        jobs = np.ascontiguousarray(jobs, dtype=np.dtype(B.MethJob))
+        pool = np.ascontiguousarray(pool, dtype=np.uint32)
+        f = B.lib().bsx_meth_batch
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t]
+        B.check(f(self.h, len(jobs), _p(jobs), _p(pool), pool.size), "bsx_meth_batch")
+
+    def meth_read(self, fpos, n):
+        """bsx_meth_read -> int64[n, 4]: ret, conv, opp_ref, opp_alt of the positions [fpos, fpos + n)"""
+        out = np.zeros((int(n), 4), np.uint32)
+        f = B.lib().bsx_meth_read
+        f.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        B.check(f(self.h, int(fpos), int(n), _p(out)), "bsx_meth_read")
+        return out.astype(np.int64)
+
+    def meth_tables(self):
+        """bsx_meth_tables -> (K[5], S[5]) as int64 arrays: reported sites and the sum of their betas in thousandths for CA, CC, CG, CT, CN"""
+        t = B.MethTables()
+        f = B.lib().bsx_meth_tables
+        f.argtypes = [C.c_void_p, C.c_void_p]
+        B.check(f(self.h, C.byref(t)), "bsx_meth_tables")
+        return np.array(t.k, dtype=np.int64), np.array(t.s, dtype=np.int64)
+
+    def meth_reset(self):
+        """bsx_meth_reset: the counters freed"""
+        f = B.lib().bsx_meth_reset
+        f.argtypes = [C.c_void_p]
+        B.check(f(self.h), "bsx_meth_reset")
+
     def markdup_batch(self, keys, first_ordinal):
         """bsx_markdup_batch: keys = uint64[n, 2] (_lib.MarkdupKey's layout; both words all ones: skipped), the template with ordinal
         first_ordinal + i at keys[i] -> uint8[n], 1 where an equal key with a lower ordinal is in the device's table or earlier in the batch"""

@@ -62,6 +62,16 @@ void launch_cov_sums(hipStream_t st, int n_cu, const void *diff, long long n_til
 void launch_cov_max(hipStream_t st, int n_cu, const DevIndex &ix, const void *diff, const void *carry, long long n_tiles, int *gmax);
 void launch_cov_count(hipStream_t st, int n_cu, const DevIndex &ix, const void *diff, const void *carry, long long n_tiles, const uint32_t *m_top,
                       const uint32_t *m_bot, int lds_bins, int flush_tiles, unsigned long long *bins, long long nb);
+// k_meth.hip: the base-averaged conversion table.  state: meth_state_entries(l_pac) entries of two 64-bit words (ret | conv << 32, opp_ref |
+// opp_alt << 32), zero past entry l_pac.  launch_meth_add: the columns of n jobs (bsx_meth_job_t: CIGAR words and quality masks in pool) added
+// to it, the reads those of the lane.  launch_meth_tables: out = 2 x BSX_METH_N_CTX zeroed 64-bit cells, the sites per context and then the sums
+// of their thousandths; 1 <= flush_tiles <= METH_FLUSH_TILES_MAX; ix.pac readable as launch_cov_count needs it
+#define METH_FLUSH_TILES_MAX 1024
+size_t meth_n_tiles(long long l_pac);
+size_t meth_state_entries(long long l_pac);
+void launch_meth_add(hipStream_t st, const DevIndex &ix, const uint8_t *reads, long long reads_len, const bsx_meth_job_t *jobs, long long n,
+                     const uint32_t *pool, long long pool_len, void *state, int n_cu);
+void launch_meth_tables(hipStream_t st, int n_cu, const DevIndex &ix, const void *state, long long n_tiles, int flush_tiles, unsigned long long *out);
 // k_markdup.hip: the device's table of template keys (bsx_markdup_batch).  A slot: claim word (0: empty), lowest ordinal, the key (all ones: none yet)
 struct MdSlot { unsigned long long claim, ord, k0, k1; };
 enum { MD_CTR_TAKEN = 0, MD_CTR_OPEN = 1, MD_CTR_LOST = 2 };   // ctr[] of the two launchers below

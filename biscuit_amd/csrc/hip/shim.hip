@@ -88,6 +88,10 @@ struct bsx_device {
 	// until bsx_cov_reset / close
 	void *cov_diff = nullptr; uint32_t *cov_mask[2] = {nullptr, nullptr};
 	std::mutex cov_mu;
+	// the counters of the base-averaged conversion table (k_meth.hip): two 64-bit words per position, made and zeroed on first use, kept until
+	// bsx_meth_reset / close
+	void *meth_st = nullptr;
+	std::mutex meth_mu;
 	// the table of template keys (k_markdup.hip): made by the first bsx_markdup_batch, doubled as it fills, kept until bsx_markdup_reset / close
 	MdSlot *md = nullptr; uint64_t md_slots = 0, md_used = 0;
 	std::mutex md_mu;
@@ -209,6 +213,7 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 	d->pac.release(); d->ctg.release(); d->holes.release(); d->qc.release();
 	if (d->md) { (void)hipFree(d->md); d->md = nullptr; d->md_slots = d->md_used = 0; }
 	cov_release(d);
+	if (d->meth_st) { (void)hipFree(d->meth_st); d->meth_st = nullptr; }
 	sort_release(d);
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
@@ -2349,6 +2354,99 @@ extern "C" BSX_API int bsx_cov_tables(bsx_device_t *d, bsx_cov_tables_t *out) { 
 extern "C" BSX_API int bsx_cov_reset(bsx_device_t *d) { return dev_cov_reset(d); }
 
 // ------------------------------------------------------------------------------------------
+// BISCUITqc base-averaged conversion table (k_meth.hip)
+// ------------------------------------------------------------------------------------------
+static int meth_state_locked(bsx_device_t *d)   // the counters, made on first use; the caller holds meth_mu
+{
+	if (d->meth_st) return BSX_OK;
+	const size_t bytes = meth_state_entries(d->ix.l_pac) * 16;
+	if (hipMalloc(&d->meth_st, bytes) != hipSuccess) {
+		size_t fr = 0, tot = 0; (void)hipGetLastError(); (void)hipMemGetInfo(&fr, &tot);
+		fprintf(stderr, "[bsx-hip] base-averaged conversion table: no room for the counters, %zu bytes (%zu of %zu bytes free)\n", bytes, fr, tot);
+		d->meth_st = nullptr; return BSX_E_NOMEM;
+	}
+	// the lanes' streams do not wait for the null stream: the zeroes are there before anything is launched on one of them
+	if (hipMemsetAsync(d->meth_st, 0, bytes, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d->meth_st); d->meth_st = nullptr; return BSX_E_NODEVICE; }
+	return BSX_OK;
+}
+static int lane_meth_batch(bsx_device_t *d, int lane, int64_t n, const bsx_meth_job_t *jobs, const uint32_t *pool, size_t pool_len)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (n == 0) return BSX_OK;
+	if (n < 0 || !jobs || !pool) return BSX_E_ARG;
+	Lane &L = d->lane[lane];
+	for (int64_t i = 0; i < n; ++i) { // every column of every job inside the genome, every CIGAR and mask word inside the pool
+		const bsx_meth_job_t &j = jobs[i];
+		if ((size_t)j.cig_off + j.n_cigar > pool_len || j.rlen < 1 || j.rlen > (1u << 30) || (size_t)j.qm_off + (j.rlen + 31) / 32 > pool_len || j.fpos < 0 || j.fpos >= d->ix.l_pac) {
+			fprintf(stderr, "[bsx-hip] meth job %lld: invalid\n", (long long)i); return BSX_E_ARG;
+		}
+		uint64_t span = 0, rspan = 0;
+		for (uint32_t k = 0; k < j.n_cigar; ++k) { const uint32_t c = pool[j.cig_off + k], op = c & 0xf; if (op > 4) return BSX_E_ARG; span += c >> 4; if (op == 0 || op == 2) rspan += c >> 4; }
+		if (span > (1u << 30)) return BSX_E_ARG;
+		if ((uint64_t)j.fpos + rspan > (uint64_t)d->ix.l_pac) { fprintf(stderr, "[bsx-hip] meth job %lld: beyond the reference\n", (long long)i); return BSX_E_ARG; }
+	}
+	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
+	std::lock_guard<std::mutex> lock(d->meth_mu);   // until the launch is done: bsx_meth_reset frees the state under the same lock
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc;
+	if ((rc = meth_state_locked(d)) != BSX_OK) return rc;
+	if ((rc = L.qcjobs.reserve((size_t)n * sizeof(bsx_meth_job_t))) != BSX_OK) return rc;
+	if ((rc = L.qcpool.reserve(pool_len * 4 + 64)) != BSX_OK) return rc;
+	H2D(L.st_hi, L.qcjobs.p, jobs, (size_t)n * sizeof(bsx_meth_job_t));
+	H2D(L.st_hi, L.qcpool.p, pool, pool_len * 4);
+	launch_meth_add(L.st_hi, d->ix, (const uint8_t*)L.reads.p, (long long)L.n_reads, (const bsx_meth_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p,
+	                (long long)pool_len, d->meth_st, d->n_cu);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(L.st_hi));   // the staging buffers are the next batch's, the lane's read buffer the next chunk's
+	return BSX_OK;
+}
+static int dev_meth_read(bsx_device_t *d, int64_t fpos, int64_t n, uint32_t *out)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (fpos < 0 || n < 0 || fpos > d->ix.l_pac || n > d->ix.l_pac - fpos || (n && !out)) return BSX_E_ARG;
+	if (n == 0) return BSX_OK;
+	std::lock_guard<std::mutex> lock(d->meth_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!d->meth_st) { memset(out, 0, (size_t)n * 16); return BSX_OK; }
+	HIPCHK(hipDeviceSynchronize());   // every lane's batches
+	HIPCHK(hipMemcpy(out, (const char*)d->meth_st + (size_t)fpos * 16, (size_t)n * 16, hipMemcpyDeviceToHost));   // (little endian: ret, conv, opp_ref, opp_alt)
+	return BSX_OK;
+}
+static int dev_meth_tables(bsx_device_t *d, bsx_meth_tables_t *out)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (!out) return BSX_E_ARG;
+	memset(out, 0, sizeof(*out));
+	const long flush_tiles = bsx_tune_long("meth_flush_tiles", METH_FLUSH_TILES_MAX);
+	if (flush_tiles < 1 || flush_tiles > METH_FLUSH_TILES_MAX) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->meth_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!d->meth_st) return BSX_OK;   // no batch yet: no site
+	HIPCHK(hipDeviceSynchronize());   // every lane's batches
+	unsigned long long *cells = nullptr;
+	if (hipMalloc((void**)&cells, sizeof(*out)) != hipSuccess) { (void)hipGetLastError(); return BSX_E_NOMEM; }
+	hipError_t e = hipMemset(cells, 0, sizeof(*out));
+	if (e == hipSuccess) { launch_meth_tables(0, d->n_cu, d->ix, d->meth_st, (long long)meth_n_tiles(d->ix.l_pac), (int)flush_tiles, cells); e = hipGetLastError(); }
+	if (e == hipSuccess) e = hipMemcpy(out, cells, sizeof(*out), hipMemcpyDeviceToHost);
+	(void)hipFree(cells);
+	HIPCHK(e);
+	return BSX_OK;
+}
+static int dev_meth_reset(bsx_device_t *d)
+{
+	if (!d) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->meth_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (d->meth_st) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(d->meth_st); d->meth_st = nullptr; }
+	return BSX_OK;
+}
+static_assert(sizeof(bsx_meth_tables_t) == 2 * BSX_METH_N_CTX * 8, "k_meth_walk's cells are bsx_meth_tables_t");
+extern "C" BSX_API int bsx_meth_batch(bsx_device_t *d, int64_t n, const bsx_meth_job_t *jobs, const uint32_t *pool, size_t pool_len) { return lane_meth_batch(d, 0, n, jobs, pool, pool_len); }
+extern "C" BSX_API int bsx_meth_read(bsx_device_t *d, int64_t fpos, int64_t n, uint32_t *out) { return dev_meth_read(d, fpos, n, out); }
+extern "C" BSX_API int bsx_meth_tables(bsx_device_t *d, bsx_meth_tables_t *out) { return dev_meth_tables(d, out); }
+extern "C" BSX_API int bsx_meth_reset(bsx_device_t *d) { return dev_meth_reset(d); }
+
+// ------------------------------------------------------------------------------------------
 // duplicate templates (k_markdup.hip)
 // ------------------------------------------------------------------------------------------
 static int md_alloc(bsx_device_t *d, hipStream_t st, uint64_t n_slots, MdSlot **out)   // an empty table of n_slots
@@ -2627,6 +2725,15 @@ static int be_cov(void *c, int op, int64_t n, const bsx_qc_job_t *j, const uint3
 	return BSX_E_ARG;
 }
 
+static int be_meth(void *c, int op, int64_t n, const bsx_meth_job_t *j, const uint32_t *pool, size_t len, bsx_meth_tables_t *out)
+{
+	bsx_device_t *d = ((LaneRef*)c)->d;
+	if (op == BSX_METH_OP_BATCH) return lane_meth_batch(LR(c), n, j, pool, len);
+	if (op == BSX_METH_OP_TABLES) return dev_meth_tables(d, out);
+	if (op == BSX_METH_OP_RESET) return dev_meth_reset(d);
+	return BSX_E_ARG;
+}
+
 static int be_sort(void *c, int op, int64_t n, const uint64_t *keys, uint32_t *perm_out, int64_t *n_total, uint32_t **run_of)
 {
 	bsx_device_t *d = ((LaneRef*)c)->d;
@@ -2647,7 +2754,7 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	memset(out, 0, sizeof(*out));
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
-	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov; out->sort_batch = be_sort;
+	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov; out->sort_batch = be_sort; out->meth_batch = be_meth;
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

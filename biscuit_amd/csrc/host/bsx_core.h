@@ -206,7 +206,12 @@ typedef struct bsx_backend {
 	 * (bsx_sort_run: n keys, perm_out), BSX_SORT_OP_SCHEDULE (bsx_sort_schedule into *n_total, *run_of), BSX_SORT_OP_RESET (bsx_sort_reset).
 	 * Without it the host sorts (sortout.c: a stable merge sort, the same results). */
 	int (*sort_batch)(void *ctx, int op, int64_t n, const uint64_t *keys, uint32_t *perm_out, int64_t *n_total, uint32_t **run_of);
+	/* optional (may be NULL; a backend that clears the struct has it NULL): the backend's counters of the base-averaged conversion table, by op:
+	 * BSX_METH_OP_BATCH (bsx_meth_batch over n jobs, the reads those of set_reads), BSX_METH_OP_TABLES (bsx_meth_tables into out),
+	 * BSX_METH_OP_RESET (bsx_meth_reset).  Without it the host keeps the counters (meth.c). */
+	int (*meth_batch)(void *ctx, int op, int64_t n, const bsx_meth_job_t *jobs, const uint32_t *pool, size_t pool_len, bsx_meth_tables_t *out);
 } bsx_backend_t;
+enum { BSX_METH_OP_BATCH = 0, BSX_METH_OP_TABLES = 1, BSX_METH_OP_RESET = 2 };
 enum { BSX_SORT_OP_RUN = 0, BSX_SORT_OP_SCHEDULE = 1, BSX_SORT_OP_RESET = 2 };
 enum { BSX_COV_OP_BATCH = 0, BSX_COV_OP_MASK = 1 /* + which: 1, 2 */, BSX_COV_OP_TABLES = 3, BSX_COV_OP_RESET = 4, BSX_COV_OP_QC_BATCH = 5 };
 /* what msw_plan says about a pair: base = its first job in res (-1: the pair is left to the host's own plan), n_c[i] = candidates of read i it

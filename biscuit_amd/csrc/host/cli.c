@@ -74,6 +74,9 @@ static int usage(void)
 		"              PREFIX_cv_table.txt (depth under the M runs of every record without 0x4; q40: MAPQ >= 40; CpGs from the reference, depth\n"
 		"              the smaller of the two bases'); one process only (refused with WORLD_SIZE > 1)\n"
 		"              --qc-topgc FILE --qc-botgc FILE  (both or neither; BED, plain or gzip) also the eight _topgc / _botgc tables\n"
+		"  qc-meth   : --qc-meth  with --qc PREFIX: BISCUITqc's PREFIX_totalBaseConversionRate.txt over the same records, as `biscuit pileup`, `biscuit vcf2bed\n"
+		"              -e -t c` and the script's awk make it at their defaults: per cytosine context the mean over the callable cytosines of retained /\n"
+		"              (retained + converted) to three places, -1 below 20 cytosines; one process only (refused with WORLD_SIZE > 1)\n"
 		"  markdup   : --markdup  0x400 on every record of a template (a pair, or a single read) whose ends' unclipped 5' positions, strands and YD\n"
 		"              equal those of an earlier template of the input; one process only (refused with WORLD_SIZE > 1)\n"
 		"  sort      : --sort  the records in coordinate order: by the rank of RNAME among the header's @SQ lines ('*' last), POS, then forward before\n"
@@ -377,6 +380,9 @@ static double now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.t
 /* --qc-cov needs the depth of every position over the whole input: the histograms of several devices do not add up to it */
 #define QC_COV_RANKS_MSG "--qc-cov keeps the depth of the whole input on one device: it cannot run with WORLD_SIZE > 1"
 
+/* --qc-meth needs the four counters of every position over the whole input: a cytosine's beta does not add across devices */
+#define QC_METH_RANKS_MSG "--qc-meth keeps the counts of every cytosine of the whole input on one device: it cannot run with WORLD_SIZE > 1"
+
 /* --qc: the tables of `biscuit qc` (src/qc.c) over this call's records; with several ranks rank 0 writes the sum (bsx_align_main_ranks_with) */
 static char g_qc_prefix[4096];
 static int g_qc_paired;
@@ -387,6 +393,14 @@ static int qc_cov_report(void)
 	if (rc == BSX_OK) rc = bsx_cov_write(g_qc_prefix, &t);
 	if (rc != BSX_OK) fprintf(stderr, "[E::%s] writing the coverage tables failed (%s)\n", "main_align", bsx_strerror(rc));
 	bsx_cov_tables_free(&t);
+	return rc;
+}
+static int qc_meth_report(void)
+{
+	bsx_meth_tables_t t;
+	int rc = bsx_process_qc_meth_tables(&t);
+	if (rc == BSX_OK) rc = bsx_meth_write(g_qc_prefix, &t);
+	if (rc != BSX_OK) fprintf(stderr, "[E::%s] writing the base-averaged conversion table failed (%s)\n", "main_align", bsx_strerror(rc));
 	return rc;
 }
 /* the BED file of --qc-topgc / --qc-botgc as mask `which` of this call's coverage tables */
@@ -427,10 +441,10 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		{"bsconv-max-cph-frac", required_argument, 0, 1006}, {"bsconv-max-cpy-frac", required_argument, 0, 1007},
 		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {"qc", required_argument, 0, 1010}, {"markdup", no_argument, 0, 1011},
 		{"qc-cov", no_argument, 0, 1012}, {"qc-topgc", required_argument, 0, 1013}, {"qc-botgc", required_argument, 0, 1014},
-		{"sort", no_argument, 0, 1015}, {"sort-tmp", required_argument, 0, 1016}, {0, 0, 0, 0}
+		{"sort", no_argument, 0, 1015}, {"sort-tmp", required_argument, 0, 1016}, {"qc-meth", no_argument, 0, 1017}, {0, 0, 0, 0}
 	};
 	bsx_bsconv_conf_t bsconv;
-	int bsconv_on = 0, qc_on = 0, markdup_on = 0, qc_cov_on = 0;
+	int bsconv_on = 0, qc_on = 0, markdup_on = 0, qc_cov_on = 0, qc_meth_on = 0;
 	const char *gc_bed[2] = {0, 0}, *sort_tmp = 0;
 	int sort_on = 0;
 	char *sort_hdr = 0;
@@ -452,6 +466,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		else if (c == 1013 || c == 1014) gc_bed[c - 1013] = optarg;
 		else if (c == 1015) sort_on = 1;
 		else if (c == 1016) sort_tmp = optarg;
+		else if (c == 1017) qc_meth_on = 1;
 		else if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
 			bsconv_on = 1;
 			if (c == 1000) bsconv.annotate = 1;
@@ -603,8 +618,11 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	if ((gc_bed[0] || gc_bed[1]) && !qc_cov_on) { fprintf(stderr, "[E::%s] --qc-topgc and --qc-botgc belong to --qc-cov\n", "main_align"); return 1; }
 	if ((gc_bed[0] != 0) != (gc_bed[1] != 0)) { fprintf(stderr, "[E::%s] --qc-topgc and --qc-botgc must be given together\n", "main_align"); return 1; }
 	if (qc_cov_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", QC_COV_RANKS_MSG); return 1; }
+	if (qc_meth_on && !qc_on) { fprintf(stderr, "[E::%s] --qc-meth writes its table beside those of --qc: it needs --qc PREFIX\n", "main_align"); return 1; }
+	if (qc_meth_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", QC_METH_RANKS_MSG); return 1; }
 	bsx_process_set_qc(qc_on);
 	bsx_process_set_qc_cov(qc_cov_on);
+	bsx_process_set_qc_meth(qc_meth_on);
 	if (markdup_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; }
 	if (sort_tmp && !sort_on) { fprintf(stderr, "[E::%s] --sort-tmp names the directory of --sort's temporary file: it needs --sort\n", "main_align"); return 1; }
 	if (sort_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", SORT_RANKS_MSG); return 1; }
@@ -847,7 +865,7 @@ loop_done:
 	if (bsconv_on && bsx_shard_world <= 1) bsconv_report();   /* (several ranks: rank 0 reports the sum, bsx_align_main_ranks_with) */
 	if (qc_on) { /* the device's counts are read while it is open; several ranks: kept for the sum */
 		g_qc_paired = (opt->flag & BSX_F_PE) ? 1 : 0;
-		if (bsx_shard_world <= 1) { if (rc == 0 && qc_report() != BSX_OK) rc = 1; if (rc == 0 && qc_cov_on && qc_cov_report() != BSX_OK) rc = 1; }
+		if (bsx_shard_world <= 1) { if (rc == 0 && qc_report() != BSX_OK) rc = 1; if (rc == 0 && qc_cov_on && qc_cov_report() != BSX_OK) rc = 1; if (rc == 0 && qc_meth_on && qc_meth_report() != BSX_OK) rc = 1; }
 		else if (bsx_process_qc_totals(0, 0) != BSX_OK) rc = 1;
 	}
 	if (markdup_on && bsx_verbose >= 3) {
@@ -861,6 +879,7 @@ cleanup:
 	free(sort_hdr);
 	if (markdup_on) bsx_process_set_markdup(0);
 	if (qc_cov_on) bsx_process_set_qc_cov(0);
+	if (qc_meth_on) bsx_process_set_qc_meth(0);
 	if (qc_on && bsx_shard_world <= 1) bsx_process_set_qc(0);
 	if (bsconv_on && bsx_shard_world <= 1) bsx_process_set_bsconv(0);
 	if (open_device && ud && g_close_device) g_close_device(ud);   /* the device this call opened: index replica, lanes, streams */
@@ -935,6 +954,7 @@ BSX_API int bsx_align_main_ranks_with(int argc, char **argv, bsx_process_fn proc
 	if (rank < 0 || rank >= world) { fprintf(stderr, "[E::%s] RANK %d of WORLD_SIZE %d\n", "main_align", rank, world); return 1; }
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 3 && strncmp("--markdup", argv[k], strlen(argv[k])) == 0) { /* (any abbreviation getopt_long takes: no other long option begins with --m) */ fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; } }   /* (before any transport is opened) */
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 6 && strncmp("--qc-cov", argv[k], strlen(argv[k])) == 0) { /* (--qc-c, --qc-co: what getopt_long takes for it) */ fprintf(stderr, "[E::%s] %s\n", "main_align", QC_COV_RANKS_MSG); return 1; } }
+	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 6 && strncmp("--qc-meth", argv[k], strlen(argv[k])) == 0) { /* (--qc-m .. --qc-met: what getopt_long takes for it) */ fprintf(stderr, "[E::%s] %s\n", "main_align", QC_METH_RANKS_MSG); return 1; } }
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strncmp(argv[k], "--s", 3) == 0) { /* (--sort, --sort-tmp and every abbreviation: no other long option begins with --s) */ fprintf(stderr, "[E::%s] %s\n", "main_align", SORT_RANKS_MSG); return 1; } }
 	memset(&R, 0, sizeof(R));
 	if (id_env && *id_env) snprintf(id_path, sizeof(id_path), "%s", id_env);

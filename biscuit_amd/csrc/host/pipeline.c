@@ -124,7 +124,7 @@ BSX_API int bsx_process_bsconv_totals(uint64_t out[8], uint64_t *n, uint64_t *n_
 }
 
 /* ------------------------------------------------------------------ BISCUITqc while aligning (qc.c): setting and totals of the process (a stream has its own) */
-static bsx_qc_state_t g_qc = {0, PTHREAD_MUTEX_INITIALIZER, .cov = {0, PTHREAD_MUTEX_INITIALIZER}};
+static bsx_qc_state_t g_qc = {0, PTHREAD_MUTEX_INITIALIZER, .cov = {0, PTHREAD_MUTEX_INITIALIZER}, .meth = {0, PTHREAD_MUTEX_INITIALIZER}};
 static int qc_state_totals(bsx_qc_state_t *q, bsx_qc_totals_t *out)
 {
 	int rc = bsx_qc_collect(q);
@@ -151,6 +151,16 @@ static int qc_cov_set(bsx_qc_state_t *q, int on)
 BSX_API int bsx_process_set_qc_cov(int on) { return qc_cov_set(&g_qc, on); }
 BSX_API int bsx_process_set_qc_cov_mask(int which, int64_t n, const int64_t *beg_end) { return bsx_cov_state_mask(&g_qc.cov, which, n, beg_end); }
 BSX_API int bsx_process_qc_cov_tables(bsx_cov_tables_t *out) { return bsx_cov_state_tables(&g_qc.cov, out); }
+
+/* the base-averaged conversion table over the same records (meth.c): part of the QC state, set after it */
+static int qc_meth_set(bsx_qc_state_t *q, int on)
+{
+	if (on && !q->on) return BSX_E_ARG;
+	bsx_meth_state_set(&q->meth, on);
+	return BSX_OK;
+}
+BSX_API int bsx_process_set_qc_meth(int on) { return qc_meth_set(&g_qc, on); }
+BSX_API int bsx_process_qc_meth_tables(bsx_meth_tables_t *out) { return bsx_meth_state_tables(&g_qc.meth, out); }
 
 /* ------------------------------------------------------------------ duplicate marking while aligning (markdup.c): setting and totals of the process (a stream has its own) */
 static bsx_md_state_t g_md = BSX_MD_STATE_INIT;
@@ -986,7 +996,7 @@ static void plan_free_worker(void *data, long u, int tid)
 		if (Q->ctx[u].table[w]) for (k = 0; k < regs->n; ++k) bsx_cfree(Q->ctx[u].table[w][k].cigar);
 		bsx_cfree(Q->ctx[u].table[w]); bsx_cvec_free(Q->ctx[u].want[w]); bsx_cfree(Q->ctx[u].zn[w]);
 	}
-	bsx_cvec_free(Q->ctx[u].qc_recs); bsx_cvec_free(Q->ctx[u].qc_cig);
+	bsx_cvec_free(Q->ctx[u].qc_recs); bsx_cvec_free(Q->ctx[u].qc_cig); bsx_cvec_free(Q->ctx[u].qc_qm);
 }
 
 static pthread_mutex_t g_stat_mu = PTHREAD_MUTEX_INITIALIZER;   /* a chunk's phase times, added to by the slices of its back half */
@@ -1095,7 +1105,7 @@ static int emit_sam(chunk_t *C, int u0, int u1, int sl, int n_sl)   /* the units
 		stat_add(&C->st.t_cigar, now_s() - t0); t0 = now_s();
 	}
 	if (rc == BSX_OK && C->bs) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].bs = &C->bs->conf; ctx[k].bs_filter = C->bs->filter; }   /* (the planning pass writes no records) */
-	if (rc == BSX_OK && C->qc) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].qc = 1; ctx[k].qc_roff[0] = C->roff[(u0 + k) * per]; ctx[k].qc_roff[1] = C->roff[(u0 + k) * per + per - 1]; }
+	if (rc == BSX_OK && C->qc) for (k = 0; k < (size_t)n_units; ++k) { ctx[k].qc = 1; ctx[k].qc_meth = C->qc->meth.on; ctx[k].qc_roff[0] = C->roff[(u0 + k) * per]; ctx[k].qc_roff[1] = C->roff[(u0 + k) * per + per - 1]; }
 	if (rc == BSX_OK) { P.final_pass = 1; bsx_parallel_for(C->nt, out_worker, &P, n_units); }
 	if (rc == BSX_OK && C->qc) rc = bsx_qc_slice(C->qc, C->be, C->idx, C->buf, (size_t)C->roff[C->n], ctx, (size_t)n_units);
 	if (rc == BSX_OK && C->bs) {
@@ -1799,6 +1809,17 @@ BSX_API int bsx_stream_qc_cov_tables(bsx_stream_t *s, bsx_cov_tables_t *out)
 	return bsx_cov_state_tables(s->qc.on ? &s->qc.cov : &g_qc.cov, out);
 }
 
+BSX_API int bsx_stream_set_qc_meth(bsx_stream_t *s, int on)
+{
+	if (!s || s->n_pushed) return BSX_E_ARG;
+	return qc_meth_set(&s->qc, on);
+}
+BSX_API int bsx_stream_qc_meth_tables(bsx_stream_t *s, bsx_meth_tables_t *out)
+{
+	if (!s) return BSX_E_ARG;
+	return bsx_meth_state_tables(s->qc.on ? &s->qc.meth : &g_qc.meth, out);
+}
+
 BSX_API int bsx_stream_set_markdup(bsx_stream_t *s, int on)
 {
 	if (!s || s->n_pushed) return BSX_E_ARG;
@@ -1877,5 +1898,6 @@ BSX_API void bsx_stream_close(bsx_stream_t *s)
 	(void)stream_drain(s);
 	bsx_md_state_end(&s->md);
 	bsx_cov_state_set(&s->qc.cov, 0);
+	bsx_meth_state_set(&s->qc.meth, 0);
 	free(s);
 }

@@ -44,6 +44,11 @@ typedef struct {
 	int32_t tlen;
 	uint16_t flag;
 	uint8_t mapq, mapped;
+	/* the base-averaged conversion table (--qc-meth, meth.c): does the record count, where its quality mask starts in the unit's mask words,
+	 * the forward interval a read 2 leaves to its mate (empty otherwise) */
+	uint8_t meth;
+	uint32_t qm_off;
+	int64_t ov_beg, ov_end;
 } bsx_qc_rec_t;
 typedef BSX_VEC(bsx_qc_rec_t) bsx_qc_rec_v;
 typedef BSX_VEC(uint32_t) bsx_qc_cig_v;
@@ -68,6 +73,8 @@ typedef struct {
 	uint32_t qc_roff[2];
 	bsx_qc_rec_v qc_recs;
 	bsx_qc_cig_v qc_cig;
+	int qc_meth;              /* also note what the base-averaged conversion table needs (bsx_qc_rec_t.meth ..), quality masks in qc_qm */
+	bsx_qc_cig_v qc_qm;
 	/* duplicate marking while aligning (md 0: off): the planning pass notes each end's primary record -- index of its region, -1: the unplaced
 	 * stand-in, -2: none yet / no such end; md_dup: the template is a duplicate, the final pass writes 0x400 into every record */
 	int md, md_dup;

@@ -10,9 +10,11 @@
 void bsx_qc_state_set(bsx_qc_state_t *q, int on)
 {
 	bsx_cov_state_set(&q->cov, 0);   /* (frees what an earlier run's state holds) */
+	bsx_meth_state_set(&q->meth, 0);
 	memset(q, 0, sizeof(*q));
 	pthread_mutex_init(&q->mu, 0);
 	pthread_mutex_init(&q->cov.mu, 0);
+	pthread_mutex_init(&q->meth.mu, 0);
 	q->on = on ? 1 : 0;
 }
 
@@ -78,6 +80,40 @@ void bsx_qc_walk_host(const bsx_index_t *idx, const uint8_t *reads, size_t reads
 	}
 }
 
+/* the records of the slice that count towards the base-averaged conversion table (sam.c has applied the record filters) as jobs of their own:
+ * what the QC job has, the strand tag, the quality mask behind the CIGAR words in one pool, the mate overlap */
+static int meth_slice(bsx_qc_state_t *q, const bsx_backend_t *be, const bsx_index_t *idx, const uint8_t *reads, size_t reads_len, const samctx_t *ctx, size_t n_units)
+{
+	bsx_meth_job_t *jobs;
+	uint32_t *pool;
+	size_t u, k, n_recs = 0, n_words = 0, nj = 0, nw = 0;
+	int rc;
+	for (u = 0; u < n_units; ++u) { n_recs += ctx[u].qc_recs.n; n_words += ctx[u].qc_cig.n + ctx[u].qc_qm.n; }
+	jobs = (bsx_meth_job_t*)malloc(sizeof(*jobs) * (n_recs ? n_recs : 1));
+	pool = (uint32_t*)malloc(4 * n_words + 4);
+	for (u = 0; u < n_units; ++u) {
+		const size_t cig0 = nw, qm0 = nw + ctx[u].qc_cig.n;
+		for (k = 0; k < ctx[u].qc_recs.n; ++k) {
+			const bsx_qc_rec_t *r = &ctx[u].qc_recs.a[k];
+			bsx_meth_job_t *j = &jobs[nj];
+			if (!r->mapped || !r->meth) continue;
+			memset(j, 0, sizeof(*j));
+			j->fpos = r->job.fpos; j->roff = r->job.roff; j->rskip = r->job.rskip; j->rlen = r->job.rlen;
+			j->cig_off = (uint32_t)cig0 + r->job.cig_off; j->n_cigar = r->job.n_cigar;
+			j->flags = r->job.flags & (BSX_QC_REVERSE | BSX_QC_READ2 | 3u << 2);
+			j->qm_off = (uint32_t)qm0 + r->qm_off;
+			j->ov_beg = r->ov_beg; j->ov_end = r->ov_end;
+			++nj;
+		}
+		if (ctx[u].qc_cig.n) memcpy(pool + cig0, ctx[u].qc_cig.a, 4 * ctx[u].qc_cig.n);
+		if (ctx[u].qc_qm.n) memcpy(pool + qm0, ctx[u].qc_qm.a, 4 * ctx[u].qc_qm.n);
+		nw = qm0 + ctx[u].qc_qm.n;
+	}
+	rc = bsx_meth_slice(&q->meth, be, idx, reads, reads_len, (int64_t)nj, jobs, pool, nw);
+	free(jobs); free(pool);
+	return rc;
+}
+
 int bsx_qc_slice(bsx_qc_state_t *q, const bsx_backend_t *be, const bsx_index_t *idx, const uint8_t *reads, size_t reads_len,
                  const samctx_t *ctx, size_t n_units)
 {
@@ -88,6 +124,7 @@ int bsx_qc_slice(bsx_qc_state_t *q, const bsx_backend_t *be, const bsx_index_t *
 	int rc = BSX_OK, i;
 	for (u = 0; u < n_units; ++u) { n_recs += ctx[u].qc_recs.n; n_words += ctx[u].qc_cig.n; }
 	if (q->cov.on && (rc = bsx_cov_attach(&q->cov, be, idx)) != BSX_OK) return rc;
+	if (q->meth.on && (rc = bsx_meth_attach(&q->meth, be, idx)) != BSX_OK) return rc;
 	if (n_recs == 0) return BSX_OK;
 	t = (bsx_qc_totals_t*)calloc(1, sizeof(*t));
 	jobs = (bsx_qc_job_t*)malloc(sizeof(*jobs) * n_recs);
@@ -117,6 +154,7 @@ int bsx_qc_slice(bsx_qc_state_t *q, const bsx_backend_t *be, const bsx_index_t *
 	else if (nj && be->qc_batch) rc = be->qc_batch(be->ctx, (int64_t)nj, jobs, pool, nw, 0, 0);
 	else for (k = 0; k < nj; ++k) bsx_qc_walk_host(idx, reads, reads_len, &jobs[k], pool + jobs[k].cig_off, &t->dev);
 	if (rc == BSX_OK && q->cov.on && !(be->qc_batch && be->cov_batch)) rc = bsx_cov_slice(&q->cov, be, idx, (int64_t)nj, jobs, pool, nw);
+	if (rc == BSX_OK && q->meth.on) rc = meth_slice(q, be, idx, reads, reads_len, ctx, n_units);
 	if (rc == BSX_OK) {
 		pthread_mutex_lock(&q->mu);
 		counts_add(&q->tot.dev, &t->dev);

@@ -5,6 +5,7 @@
 #include <pthread.h>
 #include "pipeline.h"
 #include "cov.h"
+#include "meth.h"
 
 #define BSX_QC_MAX_BE 48
 typedef struct {
@@ -15,6 +16,7 @@ typedef struct {
 	struct { int (*fn)(void*, int64_t, const bsx_qc_job_t*, const uint32_t*, size_t, bsx_qc_counts_t*, int); void *ctx; } be[BSX_QC_MAX_BE];
 	int n_be;
 	bsx_cov_state_t cov;   /* the coverage tables over the same records (cov.c): off unless set after this state was set on */
+	bsx_meth_state_t meth; /* the base-averaged conversion table over the same records (meth.c): likewise */
 } bsx_qc_state_t;
 
 void bsx_qc_state_set(bsx_qc_state_t *q, int on);

@@ -393,7 +393,7 @@ static int bsconv_record(drv_t *D, int which, sbuf_t *str, size_t rec0, const re
 
 /* BISCUITqc while aligning: note the record just written for the slice's count (qc.c) -- the fields process_qc (src/qc.c:125-160) looks at and,
  * for a mapped record, the job of the column counts: the read where the chunk's read buffer has it, the CIGAR as printed (S or H alike) */
-static void qc_record(drv_t *D, int which, const bsx_read_t *s, const reg_t *p, int64_t tlen)
+static void qc_record(drv_t *D, int which, const bsx_read_t *s, const reg_t *p, int64_t tlen, int l_printed, const reg_t *m)
 {
 	const int flag = (p->flag & 0xffff) | (p->flag & 0x10000 ? 0x100 : 0), mapq = p->rid >= 0 ? (int)p->mapq : 0;
 	bsx_qc_rec_t r;
@@ -410,6 +410,22 @@ static void qc_record(drv_t *D, int which, const bsx_read_t *s, const reg_t *p, 
 		if (mapq >= 40 && !(flag & 0x100)) r.job.flags |= BSX_QC_CINREAD;
 		if (mapq >= 40 && !(flag & 0x100) && !(flag & 0x400) && !(flag & 0x200) && (flag & 0x1) && (flag & 0x2)) r.job.flags |= BSX_QC_BSCONV;
 		for (k = 0; k < p->n_cigar; ++k) bsx_cvec_push(D->ctx->qc_cig, p->cigar[k]);
+		/* the record filters of `biscuit pileup` at its defaults (src/pileup.c:713-726; a record without AS passes) */
+		if (D->ctx->qc_meth && !(flag & (0x100 | 0x200 | 0x400)) && mapq >= 40 && l_printed >= 10 && !((flag & 0x1) && !(flag & 0x2)) && !(p->score >= 0 && p->score < 40)) {
+			const int L = s->l_seq0, rev = flag & 0x10 ? 1 : 0;
+			uint32_t w = 0;
+			r.meth = 1;
+			r.qm_off = (uint32_t)D->ctx->qc_qm.n;
+			for (k = 0; k < L; ++k) { /* bit k: the base at position k of the whole read as the record has it, quality >= 20 (no qualities: 0xff in the tool) */
+				if (!s->qual || s->qual[rev ? L - 1 - k : k] - 33 >= 20) w |= 1u << (k & 31);
+				if ((k & 31) == 31 || k == L - 1) { bsx_cvec_push(D->ctx->qc_qm, w); w = 0; }
+			}
+			if ((flag & 0x80) && m) { /* src/pileup.c:732-747, 773-778: max(POS, PNEXT) .. min(end, the mate's end by MC), half-open here */
+				const int64_t off = D->idx->ref.anns[p->rid].offset, e0 = p->pos + get_rlen(p->n_cigar, p->cigar), e1 = m->pos + (m->n_cigar ? get_rlen(m->n_cigar, m->cigar) : 0);
+				r.ov_beg = off + (p->pos > m->pos ? p->pos : m->pos); r.ov_end = off + (e0 < e1 ? e0 : e1);
+				if (r.ov_end < r.ov_beg) r.ov_end = r.ov_beg;
+			}
+		}
 	}
 	bsx_cvec_push(D->ctx->qc_recs, r);
 }
@@ -422,7 +438,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 	const bsx_refmeta_t *ref = &D->idx->ref;
 	reg_t p = *p0, m;
 	int64_t tlen = 0;   /* as written */
-	int i;
+	int i, l_printed = 0;   /* bases of SEQ as written */
 	if (D->ctx->plan) { /* planning only needs the side effects on CIGAR availability */
 		if (D->ctx->trace && D->ctx->n_trace < D->ctx->m_trace) {
 			int *t = D->ctx->trace[D->ctx->n_trace++];
@@ -489,6 +505,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 			}
 		}
 		sb_need(str, (size_t)(qe - qb > 0 ? qe - qb : 0) * 2 + 4);
+		l_printed = qe - qb > 0 ? qe - qb : 0;
 		if (p.is_rev) {
 			for (i = qe - 1; i >= qb; --i) str->s[str->l++] = "TGCAN"[(int)s->seq0[i]];
 			str->s[str->l] = 0;
@@ -533,7 +550,7 @@ static void format_sam(drv_t *D, int which, sbuf_t *str, bsx_read_t *s, const re
 	if (p.bss_u) sb_putc(str, 'u');
 	else sb_putc(str, "fr"[p.bss]);
 	if (D->ctx->bs && bsconv_record(D, which, str, rec0, &p, p0, regs0)) return;
-	if (D->ctx->qc) qc_record(D, which, s, &p, tlen);
+	if (D->ctx->qc) qc_record(D, which, s, &p, tlen, l_printed, m0 ? &m : 0);
 	sb_putc(str, '\n');
 }
 

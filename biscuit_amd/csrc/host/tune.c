@@ -55,6 +55,7 @@ static knob_t g_knobs[] = {
 	{"long_dedup", "[1] 0: reads with more than 32 regions are de-duplicated on the host (A/B against k_dedup_long)", 0},
 	{"markdup_slots", "[32 per key of the first batch, at least 65536] slots of the first table of template keys (--markdup), a power of two; it doubles before a batch would load it beyond one half", 0},
 	{"cov_lds_bins", "[512] depths below this are counted in a workgroup's LDS histograms by the coverage tables' last pass (--qc-cov), deeper ones in HBM directly; a power of two up to 512", 0},
+	{"meth_flush_tiles", "[1024] tests: tiles after which a wave of the base-averaged conversion table's pass (--qc-meth) adds its sums to the 64-bit cells (32-bit registers: at most 1024)", 0},
 	{"cov_flush_tiles", "[524287] tests: tiles after which a workgroup of that pass adds its LDS histograms to the bins (32-bit cells: at most 2^32 / 4096 - 1)", 0},
 	{"sort_buf_bytes", "[1 GB / runs, at most 8 MB] bytes of the buffer every sorted run of --sort is read back through in the final merge (tests: 1, a record is then many fills)", 0},
 	{"markdup_hash_bits", "[64] tests: low bits kept of a template key's claim word (different keys then meet in one slot and take the next salt)", 0},

@@ -379,6 +379,45 @@ int bsx_cov_tables(bsx_device_t *dev, bsx_cov_tables_t *out);
 void bsx_cov_tables_free(bsx_cov_tables_t *t);
 int bsx_cov_reset(bsx_device_t *dev);   /* the depth state and both masks freed: all-zero depth, no masks (it waits for a batch or a tables call in flight) */
 
+/* BISCUITqc base-averaged conversion table (k_meth.hip): what `biscuit pileup`, `biscuit vcf2bed -e -t c` and the awk of scripts/QC.sh:423-450
+ * make of a sorted BAM at their defaults, from four counters per forward reference position that stay on the device: ret, conv, opp_ref,
+ * opp_alt, 32 bits each, held as two 64-bit words (ret | conv << 32, opp_ref | opp_alt << 32) so that a column is one 64-bit atomic add.
+ * A job is a record that counts (the caller has applied the record filters), described as a bsx_qc_job_t describes it -- fpos, the read in the
+ * resident read buffer (roff, rskip, rlen), the final CIGAR at cig_off of the pool, flags BSX_QC_REVERSE, BSX_QC_READ2 and the YD tag at
+ * BSX_QC_TAG -- plus: qm_off, the word offset in the same pool of the record's quality mask, (rlen + 31) / 32 words, bit (q & 31) of word
+ * q >> 5 set when the base at 0-based position q of the whole read in the record's orientation has quality >= 20 (all ones for a read without
+ * qualities); and [ov_beg, ov_end), the forward interval whose columns a BSX_QC_READ2 job leaves to its mate (empty otherwise).
+ * The strand is 0 for tag 0, 1 for tag 1, else inferred over the M columns with the mask bit set: 0 when ref C / read T columns are at least
+ * as many as ref G / read A columns, else 1.  A column counts when its mask bit is set, 3 < q1 and q1 + 3 <= rlen (q1 = q + 1; H advances q
+ * like S), its reference base is no N hole and, for BSX_QC_READ2, it lies outside the interval.  At a reference C: strand 0 read C -> ret,
+ * read T -> conv, strand 1 read C -> opp_ref, read T -> opp_alt; at a reference G: strand 1 read G -> ret, read A -> conv, strand 0 read G ->
+ * opp_ref, read A -> opp_alt.  The state (16 bytes per base, zeroed) is made by the first call that needs it and freed by bsx_meth_reset and
+ * bsx_device_close; BSX_E_NOMEM when it cannot be had. */
+typedef struct bsx_meth_job {
+	int64_t fpos;
+	uint32_t roff;
+	int32_t rskip;
+	uint32_t rlen;
+	uint32_t cig_off, n_cigar;
+	uint32_t flags;
+	uint32_t qm_off;
+	uint32_t pad;
+	int64_t ov_beg, ov_end;
+} bsx_meth_job_t;
+#define BSX_METH_N_CTX 5   /* CA, CC, CG, CT, and CN: the neighbour is an N hole or beyond the contig */
+/* per context: k = reported sites (a reference C or G outside N holes with ret + conv > 0 that is callable: opp_alt == 0 or 20 * opp_alt <
+ * ret + opp_ref), s = the sum over them of the beta in thousandths, the integer printf("%1.3f", (double)ret / (double)(ret + conv)) shows */
+typedef struct bsx_meth_tables { uint64_t k[BSX_METH_N_CTX], s[BSX_METH_N_CTX]; } bsx_meth_tables_t;
+/* every job must lie inside the genome and the pool (fpos >= 0, fpos + reference length <= l_pac, cig_off + n_cigar <= pool_len, qm_off +
+ * (rlen + 31) / 32 <= pool_len): BSX_E_ARG otherwise, and nothing is launched.  The reads are those of bsx_device_set_reads.  Exact integer
+ * sums: the order of jobs and the split into batches do not matter. */
+int bsx_meth_batch(bsx_device_t *dev, int64_t n, const bsx_meth_job_t *jobs, const uint32_t *pool, size_t pool_len);
+/* the four counters of the positions [fpos, fpos + n) into out[4 * i + (0 ret, 1 conv, 2 opp_ref, 3 opp_alt)]; waits for the batches in flight */
+int bsx_meth_read(bsx_device_t *dev, int64_t fpos, int64_t n, uint32_t *out);
+/* waits for the batches in flight and makes the sums; the state is only read */
+int bsx_meth_tables(bsx_device_t *dev, bsx_meth_tables_t *out);
+int bsx_meth_reset(bsx_device_t *dev);   /* the state freed: every counter zero */
+
 /* Duplicate templates (k_markdup.hip): a table of template keys that stays on the device until bsx_markdup_reset or bsx_device_close.
  * A key is the ordered pair of the template's ends, w[0] = read 1 (or the single read), w[1] = read 2; an end that is not placed (its primary
  * record has 0x4) is 0, the second end of a single read is BSX_MD_SINGLE: a single read never equals a pair, not even one whose read 2 is not
@@ -626,6 +665,20 @@ int  bsx_cov_write(const char *prefix, const bsx_cov_tables_t *t);
  * word is "track" or "browser" skipped) -> forward intervals, *beg_end malloc'd (2 * *n values).  BSX_E_IO: cannot be read; BSX_E_FORMAT: a malformed line, an
  * interval outside its contig, a contig that is not in the index (message on stderr) */
 int  bsx_cov_read_bed(const char *path, const bsx_index_t *idx, int64_t *n, int64_t **beg_end);
+
+/* BISCUITqc's base-averaged conversion table while aligning (--qc-meth): with set_qc on, every record written that passes the record filters
+ * of `biscuit pileup` at its defaults -- none of 0x4, 0x100, 0x200, 0x400 (after --markdup), MAPQ >= 40, at least 10 bases of SEQ, not paired
+ * without 0x2, AS >= 40; after --bsconv's filters -- goes to the counters of the device it was aligned on (bsx_meth_batch; a backend without
+ * the seam keeps them on the host, meth.c).  One counter state per device: one stream or one process call at a time.  set_qc_meth(1) needs
+ * set_qc(1) before it (BSX_E_ARG otherwise) and starts from zero.  The tables: after bsx_stream_flush / while the device is open. */
+int  bsx_stream_set_qc_meth(bsx_stream_t *s, int on);
+int  bsx_stream_qc_meth_tables(bsx_stream_t *s, bsx_meth_tables_t *out);
+int  bsx_process_set_qc_meth(int on);
+int  bsx_process_qc_meth_tables(bsx_meth_tables_t *out);
+/* PREFIX_totalBaseConversionRate.txt: the title, CA\tCC\tCG\tCT, and per context -1 when k < 20, else (double)s / (1000.0 * (double)k) as %.6g */
+int  bsx_meth_write(const char *prefix, const bsx_meth_tables_t *t);
+/* the beta in thousandths: the integer printf("%1.3f", (double)r / (double)n) shows, times 1000 (0 <= r <= n, n > 0), without printf */
+uint32_t bsx_meth_milli(uint32_t r, uint32_t n);
 
 /* Duplicate marking while aligning (--markdup).  A template is one unit of the input, a pair or a single read; its ordinal is its 0-based index
  * in the input of the stream (or of the process) over all chunks.  Each end's primary record is the one with neither 0x100 nor 0x800; the
