@@ -162,6 +162,8 @@ class Device(Batches):
         fns = {k: getattr(L, v) for k, v in names.items() if hasattr(L, v)}
         Batches.__init__(self, fns, self.h)
         self.name = L.bsx_device_name(self.h).decode()
+        L.bsx_device_n_cu.argtypes = [C.c_void_p]
+        self.n_cu = int(L.bsx_device_n_cu(self.h))      # the grids of the persistent kernels are multiples of it
 
     def upload_index(self, index):
         B.check(B.lib().bsx_device_upload_index(self.h, index.h), "bsx_device_upload_index")

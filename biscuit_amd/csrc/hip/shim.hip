@@ -241,6 +241,7 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 }
 
 extern "C" BSX_API const char *bsx_device_name(const bsx_device_t *d) { return d ? d->name : ""; }
+extern "C" BSX_API int bsx_device_n_cu(const bsx_device_t *d) { return d ? d->n_cu : 0; }
 
 // pac and the contig table: what the kernels need of the reference besides the FM indices
 static int upload_ref(bsx_device_t *d, const bsx_index_t *idx)

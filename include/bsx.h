@@ -244,6 +244,8 @@ int  bsx_device_set_opt(bsx_device_t *dev, const bsx_opt_t *opt);
 /* upload the chunk read buffer (nt4 codes of all clipped reads, concatenated) */
 int  bsx_device_set_reads(bsx_device_t *dev, const uint8_t *buf, size_t n);
 const char *bsx_device_name(const bsx_device_t *dev);
+/* compute units of the device: the grids of the persistent kernels are multiples of it (0 for a null dev) */
+int bsx_device_n_cu(const bsx_device_t *dev);
 
 /* K1+K2: all three seeding passes of mem_collect_intv + final ordering by info.
  * out_off has n+1 entries; *out / *out_cap is a caller-owned growable array (realloc'd). */

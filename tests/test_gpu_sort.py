@@ -1,7 +1,8 @@
 """-m gpu: coordinate order on the device.  (1) Device.sort_run (k_sort.hip) against np.argsort(kind="stable") on designed key lists at every
 size where the code takes another path (one workgroup in LDS up to SORT_TILE keys, tiled passes over HBM beyond); (2) Device.sort_schedule over
 several runs against the stable argsort of their concatenation; (3) the HIP command line with --sort against tests/sort_model.py's rewrite of
-its own plain run, the CPU checker's --sort output and the same run read back through one-byte buffers, and the QC tables with and without."""
+its own plain run, the CPU checker's --sort output and the same run read back through one-byte buffers, and the QC tables with and without;
+(4) sort_run and sort_schedule at sizes where k_sort_scan2, one workgroup over the scan blocks' totals, takes a second and a third step."""
 import os
 import numpy as np
 import pytest
@@ -117,6 +118,71 @@ def test_schedule_is_the_stable_argsort_of_the_concatenation_as_run_ids(dev, whi
             assert (merged == np.sort(cat, kind="stable")).all(), name
             assert dev.sort_info() == (len(cuts), n)      # the runs stay
             assert (dev.sort_schedule() == got).all()
+    dev.sort_reset()
+    assert dev.sort_info() == (0, 0)
+
+
+# ---------------------------------------------------------------------------------------------- past one step of k_sort_scan2
+# k_sort_scan2 is one workgroup that takes 256 scan blocks (2048 tiles, 4 194 304 keys) a step and carries the sum between steps: 2049 tiles are
+# the first size with a second step, 4100 tiles make three.  Every run of the command line's --sort ends in one bsx_sort_schedule over all
+# records of the run, so a real library is past these sizes within its first few chunks.
+BIG = lambda: [T() * T() + 1, 2 * T() * T() + 3 * T() + 7]
+BIG_CASES = [(0, name) for name in ("genomic", "random64", "two_values", "top_byte_only", "all_equal", "reversed")] + [(1, "genomic"), (1, "random64")]
+_big_lists = {}
+
+
+def big_keys(n, name):
+    if n not in _big_lists:      # (one size at a time: nine lists of 4 or 8 M keys)
+        _big_lists.clear()
+        _big_lists[n] = key_lists(n)
+    return _big_lists[n][name]
+
+
+def test_the_large_sizes_pass_one_two_scan_steps():
+    from biscuit_amd.api import SORT_TILE
+    blocks = [(-(-n // SORT_TILE) * 256 + 2047) // 2048 for n in BIG()]      # sort_n_scan_blocks
+    assert SORT_TILE == 2048 and blocks == [257, 513] and [-(-b // 256) for b in blocks] == [2, 3]
+
+
+@pytest.mark.parametrize("which,name", BIG_CASES)
+def test_sort_run_past_one_scan_step_is_the_stable_argsort(dev, which, name):
+    n = BIG()[which]
+    keys = big_keys(n, name)
+    dev.sort_reset()
+    want = np.argsort(keys, kind="stable")
+    got = dev.sort_run(keys)
+    bad = np.flatnonzero(got != want)
+    assert len(got) == n and len(bad) == 0, (name, n, len(bad), bad[:10].tolist(), got[bad[:10]].tolist(), want[bad[:10]].tolist())
+    assert dev.sort_info() == (1, n)
+    dev.sort_reset()
+
+
+@pytest.mark.parametrize("name", ["genomic", "random64", "two_values"])
+def test_schedule_of_chunk_sized_runs_whose_total_passes_one_scan_step(dev, name):
+    """four runs of about 1.1 M keys, a chunk's worth each: every run takes the tiled passes within one scan step, their concatenation -- sorted
+    with the run ids as the payload, not the index -- takes two"""
+    cuts = [1100003, 1048576, 1100001, 1150000]
+    n = sum(cuts)
+    assert max(cuts) <= T() * T() < n and min(cuts) > T()
+    keys = big_keys(n, name)
+    run_id = np.repeat(np.arange(len(cuts)), cuts)
+    dev.sort_reset()
+    at, runs = 0, []
+    for c in cuts:
+        k = keys[at:at + c]
+        perm = dev.sort_run(k)
+        runs.append(k[perm])
+        at += c
+    cat = np.concatenate(runs)
+    order = np.argsort(cat, kind="stable")
+    got = dev.sort_schedule()
+    want = run_id[order]
+    bad = np.flatnonzero(got != want)
+    assert len(got) == n and len(bad) == 0, (name, len(bad), bad[:10].tolist())
+    assert dev.sort_info() == (len(cuts), n)
+    merged = np.empty(n, np.uint64)      # following the schedule with one cursor per run gives the sorted concatenation
+    merged[np.argsort(got, kind="stable")] = cat
+    assert (merged == cat[order]).all(), name
     dev.sort_reset()
     assert dev.sort_info() == (0, 0)
 
