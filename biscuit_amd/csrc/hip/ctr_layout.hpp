@@ -25,6 +25,7 @@ enum CtrSlot {
 	CTR_T3_LONGEST = 128, CTR_T3_HIST = 130, CTR_T3_HIST_N = 22,   // the last tier: its longest strand search (packed), strand searches by duration
 	CTR_T3_N = 24,                                    // (the record, a spare slot, the histogram: read and zeroed together)
 	CTR_HANDON = 160, CTR_HANDON_N = 12,              // $BSX_PHASES=2: why a tier hands a strand search on, CTR_HANDON + status
+	CTR_X4W = 176, CTR_X4W_N = 8,                     // $BSX_PHASES: extensions made ahead that the seed loop never read, CTR_X4W + 4 * kernel + CtrX4w
 	CTR_SEED2 = 256, CTR_SEED3 = 384,                 // bases of the blocks of the second seeding pass inside the sequence / of the one on the side stream
 	CTR_SEED_BLOCK_N = 125,                           // a seeding pass reaches up to CTR_SEEDT_REQ of its block
 	// where the cursor structs below live
@@ -35,6 +36,10 @@ enum CtrSlot {
 // what k_ext4 / k_extl add to, relative to CTR_EXT
 enum CtrExt { EXT4_JOBS = 0, EXT4_ROWS = 1, EXT4_TRIPS = 2, EXT4_COLD = 3, EXT4_SLOTS = 4, EXT4_NARROW_ROWS = 5,
               EXTL_JOBS = 6, EXTL_ROWS = 7, EXTL_TRIPS = 8, EXTL_COLD = 9, EXTL_SENT_ON = 10 };
+
+// what rg_c2r adds to when the first seed it reaches in a chain's main list is skipped as contained while a valid extension made ahead lay in
+// the chain's slot: relative to CTR_X4W + 4 * k, k = 0 the job ran in k_ext4, 1 in k_extl
+enum CtrX4w { X4W_JOBS = 0, X4W_ROWS = 1, X4W_JOBS_R0 = 2, X4W_ROWS_R0 = 3 };   // _R0: of which contained in the strand search's first region
 
 // the cursors every launch of a chunk shares
 struct CtrShared {
@@ -90,6 +95,7 @@ constexpr CtrRange ctr_ranges[] = {
 	{CTR_SEEDT_HOT, CTR_SEEDT_HOT + CTR_SEEDT_N},
 	{CTR_T3_LONGEST, CTR_T3_LONGEST + CTR_T3_N},
 	{CTR_HANDON, CTR_HANDON + CTR_HANDON_N},
+	{CTR_X4W, CTR_X4W + CTR_X4W_N},
 	{CTR_SEED2, CTR_SEED2 + CTR_SEED_BLOCK_N},
 	{CTR_SEED3, CTR_SEED3 + CTR_SEED_BLOCK_N},
 };
@@ -115,4 +121,5 @@ static_assert(CTR_EXT == 56 && CTR_EXT + CTR_EXT_N - 1 == 66 && CTR_SEED_HIST ==
 static_assert(CTR_TIER2_TIME == 110 && CTR_TIER3_TIME == 114 && CTR_TIER3_TIME + CTR_TIER_TIME_N - 1 == 117, "");
 static_assert(CTR_OVERFLOW == 119 && CTR_TAB_LOOKUPS == 120, "");
 static_assert(CTR_SEEDT_HOT == 121 && CTR_SEEDT_FETCH == 122 && CTR_SEEDT_POST == 123 && CTR_SEEDT_REQ == 124, "");
+static_assert(CTR_X4W == 176 && CTR_X4W_N == 8 && X4W_JOBS == 0 && X4W_ROWS == 1 && X4W_JOBS_R0 == 2 && X4W_ROWS_R0 == 3, "");
 static_assert(CTR_T3_LONGEST == 128 && CTR_T3_HIST == 130 && CTR_HANDON == 160 && CTR_SEED2 == 256 && CTR_SEED3 == 384, "");

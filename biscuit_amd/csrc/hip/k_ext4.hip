@@ -213,7 +213,9 @@ enum { X4_IDLE = 0, X4_NEXT, X4_ROW, X4_AFTER, X4_REFILL, X4_DONE };
 
 // CHAIN: jobs are X4Job (a chain's best seed, both sides, band retries; the result goes to the chain's RgXExt); else bsx_ext_job_t ->
 // bsx_ext_res_t, one ksw_extend2 call each (the batch form, for the kernel's own tests; score = X4_DECLINED for a job that does not fit)
-template <int NCQ, bool CHAIN>
+// TALLY ($BSX_PHASES, CHAIN only): res_ is the export pool's row words (RgXPoolArg::rows) and a finished job leaves there the rows it ran; the
+// instantiations without it are the code they were
+template <int NCQ, bool CHAIN, bool TALLY = false>
 __global__ void __launch_bounds__(256, X4_OCC)
 k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void *jobs_, void *res_, unsigned char *xbase,
        const unsigned int *n_ptr, unsigned int n_fixed, unsigned int *cursor, unsigned long long *prof, int take_second)
@@ -255,6 +257,7 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 #pragma unroll
 	for (int c = 0; c < NCQ; ++c) { Hr[c] = Er[c] = 0; sqp[c] = 0; }
 	unsigned int pf_rows = 0, pf_trips = 0, pf_jobs = 0, pf_cold = 0, pf_slots = 0, pf_nrows = 0;
+	[[maybe_unused]] unsigned int jrows = 0;   // (TALLY: rows of the job under way)
 	for (;;) {
 		// ---- between extensions: results, the next side or band, the next job.  Run when two rows of lanes wait for it, when a row has
 		// waited for a few trips, or when no extension is under way (a wave pays for this block whichever of its rows is in it)
@@ -303,6 +306,7 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 								RgXExt xe; xe.rb = R_rb; xe.re = R_re; xe.qb = R_qb; xe.qe = R_qe; xe.score = R_score; xe.truesc = R_truesc;
 								xe.aw0 = aw0; xe.aw1 = aw1; xe.si = si; xe.status = 1;
 								*(RgXExt*)(xbase + ext_at) = xe;
+								if constexpr (TALLY) ((unsigned int*)res_)[RGX_ROWS_AT(ext_at)] = jrows;
 							}
 							st = X4_IDLE;
 						}
@@ -332,6 +336,7 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 						s_rbeg = J.s_rbeg; rmax0 = J.rmax0; rmax1 = J.rmax1; ext_at = J.ext_at; qoff0 = J.qoff;
 						l_query = J.l_query; s_qbeg = J.s_qbeg; s_len = J.s_len; par = J.parent; si = J.si;
 						side = 0; attempt = 0; aw0 = aw1 = P.w; R_score = R_truesc = -1; R_qb = R_qe = 0; R_rb = R_re = 0;
+						if constexpr (TALLY) jrows = 0;
 						++pf_jobs;
 						st = X4_NEXT;
 					} else {
@@ -402,7 +407,7 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 		// ---- one row of every extension under way.  Straight-line code: what a row of lanes without an extension computes is thrown
 		// away by selects (a branch per 16 lanes costs the wave more than the instructions it skips)
 		const bool run = st == X4_ROW;
-		if (run) { ++pf_rows; if (CHAIN && s_len < X4_NARROW) ++pf_nrows; }
+		if (run) { ++pf_rows; if (CHAIN && s_len < X4_NARROW) ++pf_nrows; if constexpr (TALLY) ++jrows; }
 		// (what the lanes of a row without an extension do to these is of no consequence: the next set-up writes them all)
 		const int t = (int)(y0 & 3u) ^ tcomp;
 		y0 = __builtin_amdgcn_alignbit(y1, y0, 2); y1 = __builtin_amdgcn_alignbit(y2, y1, 2); y2 >>= 2; --yleft;
@@ -540,10 +545,12 @@ void launch_x4(hipStream_t st, int n_cu, const RgLaunch &G, const RgXPoolArg &XA
 	const unsigned int jcap = (unsigned int)std::min<unsigned long long>(job_cap, 0xfffffff0ull);
 	const int pgrid = (int)((n_tasks + 64 * X4P_WPB - 1) / (64 * X4P_WPB));
 	(void)hipMemsetAsync(ctr32, 0, 16, st);
+	if (XA.rows) (void)hipMemsetAsync(XA.rows, 0, rgx_rows_bytes(X.cap), st);   // ($BSX_PHASES: a slot k_x4prep answers itself ran no rows)
 	hipLaunchKernelGGL(k_x4prep, dim3(std::max(1, pgrid)), dim3(64 * X4P_WPB), 0, st, ix, P, tasks, X, (X4Job*)jobs, jcap, ctr32);
 	const int use_l = (int)bsx_tune_long("xl", 1);   // 0: the narrow queue through k_ext4 too
-	if (use_l) launch_extl(st, n_cu, ix, sc, P, reads, jobs, jcap, ctr32, X.base, n_tasks * 4, prof);
+	if (use_l) launch_extl(st, n_cu, ix, sc, P, reads, jobs, jcap, ctr32, X.base, n_tasks * 4, prof, XA.rows);
 	const int wpc = 3;   // (three waves per SIMD at 167 VGPRs)
 	const int grid = (int)std::max<long long>(1, std::min<long long>((n_tasks * 4 + 15) / 16, (long long)n_cu * wpc));
-	hipLaunchKernelGGL((k_ext4<10, true>), dim3(grid), dim3(256), 0, st, ix, sc, P, reads, (const void*)jobs, (void*)nullptr, X.base, (const unsigned int*)ctr32, jcap, ctr32 + 1, prof, use_l ? 0 : 1);
+	if (XA.rows) hipLaunchKernelGGL((k_ext4<10, true, true>), dim3(grid), dim3(256), 0, st, ix, sc, P, reads, (const void*)jobs, (void*)XA.rows, X.base, (const unsigned int*)ctr32, jcap, ctr32 + 1, prof, use_l ? 0 : 1);
+	else hipLaunchKernelGGL((k_ext4<10, true>), dim3(grid), dim3(256), 0, st, ix, sc, P, reads, (const void*)jobs, (void*)nullptr, X.base, (const unsigned int*)ctr32, jcap, ctr32 + 1, prof, use_l ? 0 : 1);
 }

@@ -33,7 +33,8 @@ __device__ __forceinline__ int xl_max3(int a, int b, int c) { const int m = a > 
 
 // CHAIN: the narrow queue of launch_x4's pool; else plain ksw_extend2 jobs (bsx_ext_job_t -> bsx_ext_res_t at res_, n = jcap of them, for the
 // kernel's own tests): a job this kernel cannot hold leaves its result slot as it was and counts in ctr32[0]
-template <bool CHAIN>
+// TALLY ($BSX_PHASES, CHAIN only): res_ is the export pool's row words (RgXPoolArg::rows), as in k_ext4
+template <bool CHAIN, bool TALLY = false>
 __global__ void __launch_bounds__(64, XL_OCC)
 k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs_, void *res_, unsigned int jcap, unsigned int *ctr32, unsigned char *xbase, unsigned long long *prof)
 {
@@ -77,6 +78,7 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 #pragma unroll
 	for (int g = 0; g < XL_W / 16; ++g) QW[g] = 0;
 	unsigned int pf_rows = 0, pf_trips = 0, pf_jobs = 0, pf_cold = 0, pf_bail = 0;
+	[[maybe_unused]] unsigned int jrows = 0;   // (TALLY: rows of the job under way; a job sent on to k_ext4 is tallied there, from its first row again)
 #define XL_QWIN() do { const int b16_ = base >> 4; _Pragma("unroll") for (int g_ = 0; g_ < XL_W / 16; ++g_) { uint32_t v_ = 0; \
 		_Pragma("unroll") for (int k_ = 0; k_ < XL_QCOLS / 16; ++k_) v_ = b16_ + g_ == k_ ? QF[k_] : v_; QW[g_] = v_; } } while (0)
 	for (;;) {
@@ -121,6 +123,7 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 							RgXExt xe; xe.rb = R_rb; xe.re = R_re; xe.qb = R_qb; xe.qe = R_qe; xe.score = R_score; xe.truesc = R_truesc;
 							xe.aw0 = aw0; xe.aw1 = aw1; xe.si = si; xe.status = 1;
 							*(RgXExt*)(xbase + ext_at) = xe;
+							if constexpr (TALLY) ((unsigned int*)res_)[RGX_ROWS_AT(ext_at)] = jrows | RGX_ROWS_L;
 							st = XL_IDLE;
 						}
 					}
@@ -170,6 +173,7 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 							s_rbeg = J.s_rbeg; rmax0 = J.rmax0; rmax1 = J.rmax1; ext_at = J.ext_at; qoff0 = J.qoff;
 							l_query = J.l_query; s_qbeg = J.s_qbeg; s_len = J.s_len; par = J.parent; si = J.si;
 							side = 0; attempt = 0; aw0 = aw1 = P.w; R_score = R_truesc = -1; R_qb = R_qe = 0; R_rb = R_re = 0;
+							if constexpr (TALLY) jrows = 0;
 							++pf_jobs;
 							st = XL_NEXT;
 						}
@@ -250,7 +254,7 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 		++pf_trips;
 		// ---- one row of every lane's extension (ksw.c:410-470); lanes without one compute on stale registers and throw the result away
 		const bool run = st == XL_ROW;
-		if (run) ++pf_rows;
+		if (run) { ++pf_rows; if constexpr (TALLY) ++jrows; }
 		const int t = (int)(y0 & 3u) ^ tcomp;
 		y0 = __builtin_amdgcn_alignbit(y1, y0, 2); y1 = __builtin_amdgcn_alignbit(y2, y1, 2); y2 >>= 2; --yleft;
 		beg = beg > i - w ? beg : i - w;
@@ -335,11 +339,12 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 // the narrow queue of launch_x4's job pool (jobs[jcap / 2 ..], count ctr32[2], cursor ctr32[3]) a lane per job; what it cannot hold joins
 // the wide queue (jobs[0 ..], count ctr32[0]) for k_ext4
 void launch_extl(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, void *jobs, unsigned int jcap,
-                 unsigned int *ctr32, unsigned char *xbase, long long n_upper, unsigned long long *prof)
+                 unsigned int *ctr32, unsigned char *xbase, long long n_upper, unsigned long long *prof, unsigned int *rows)
 {
 	const int wpc = 4 * XL_OCC;
 	const int grid = (int)std::max<long long>(1, std::min<long long>((n_upper + 63) / 64, (long long)n_cu * wpc));
-	hipLaunchKernelGGL(k_extl<true>, dim3(grid), dim3(64), 0, st, ix, sc, P, reads, jobs, (void*)nullptr, jcap, ctr32, xbase, prof);
+	if (rows) hipLaunchKernelGGL((k_extl<true, true>), dim3(grid), dim3(64), 0, st, ix, sc, P, reads, jobs, (void*)rows, jcap, ctr32, xbase, prof);
+	else hipLaunchKernelGGL(k_extl<true>, dim3(grid), dim3(64), 0, st, ix, sc, P, reads, jobs, (void*)nullptr, jcap, ctr32, xbase, prof);
 }
 
 // plain jobs[0 .. n) through the same lanes (tests): res[i] is written for every job the kernel holds, ctr32[0] counts the others; ctr32[0..3] zero at launch

@@ -1356,9 +1356,12 @@ typedef RgC2rHT<RG_QCAP_LONG, 1536, 1024, 8192> RgC2rHL;   // reads up to a kilo
 static_assert(RgC2rHL::XREGS == RgHuge::CCAP, "the last chains -> regions launch of an exporting sequence holds a region for every chain the last tier can export");
 typedef RgC2rT<RG_QCAP, RG_WIN, 256, 256> RgC2rB;   // reads inside repeat families: up to 256 regions of a strand search, 256 seeds of a chain (22 KB: seven waves per CU); for what k_c2r<RgC2r> declines   // reads up to a kilobase: a chain's window is the read plus its two gaps, a true chain has a few hundred seeds
 
-template <bool PK = false, typename WT>   // PK: as in rg_task (tables for reads of up to 256 bases only)
+// TALLY ($BSX_PHASES with extensions made ahead, RgXPoolArg::rows set): an extension of launch_x4 that the loop does not read, its seed being contained in a
+// region made before, is counted by the kernel that ran the job (CTR_X4W + 4 * k): jobs, their rows, and of both those inside the strand
+// search's first region.  An instantiation of its own: the others are the code they were.
+template <bool PK = false, bool TALLY = false, typename WT>   // PK: as in rg_task (tables for reads of up to 256 bases only)
 __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, int l_query, int parent, uint32_t qoff,
-                      const RgXHdr *H, int lane, unsigned long long *counters, const int *gap, const long long *ctg)
+                      const RgXHdr *H, int lane, unsigned long long *counters, const int *gap, const long long *ctg, const RgXPool &X)
 {
 	const long long l_pac = ix.l_pac;
 	long long pf_t = P.prof ? (long long)__builtin_readcyclecounter() : 0;
@@ -1476,7 +1479,17 @@ __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const Reg
 						}
 						any = __ballot(alt) != 0;
 					}
-					if (!any) { ++pf_skip; WAVE_SYNC(); if (lane == 0) W.srt[k] = 0; WAVE_SYNC(); continue; }
+					if (!any) {
+						// the chain's extension was made ahead and is never read: this is the seed k_x4prep chose (the first one the loop reaches in the main list)
+						if constexpr (TALLY) if (has_ext == 1 && pass == 0 && uni(W.xe[ci - xc_lo].status) == 1 && uni(W.xe[ci - xc_lo].si) == si) {
+							const unsigned long long at = (unsigned long long)((const unsigned char*)(XEw + (size_t)ci * (sizeof(RgXExt) / 8)) - X.base);
+							const unsigned int rw = (unsigned int)uni((int)((const unsigned int*)(X.base + rgx_rows_offset(X.cap)))[RGX_ROWS_AT(at)]);
+							const unsigned long long rows = rw & ~RGX_ROWS_L;
+							const unsigned long long v = lane == X4W_JOBS ? 1ull : lane == X4W_ROWS ? rows : u != 0 ? 0ull : lane == X4W_JOBS_R0 ? 1ull : rows;
+							if (lane < 4 && v) atomicAdd(&counters[CTR_X4W + ((rw & RGX_ROWS_L) ? 4 : 0) + lane], v);
+						}
+						++pf_skip; WAVE_SYNC(); if (lane == 0) W.srt[k] = 0; WAVE_SYNC(); continue;
+					}
 				}
 				// extension (memchain.c:613-730): left then right, each with up to MAX_BAND_TRY band widths -- taken from the record when this
 				// is the seed k_ext4 extended ahead of the loop (the first one the loop reaches in a chain's main list)
@@ -1963,7 +1976,7 @@ k_seedsw_apply(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, co
 #ifndef C2R_WPB
 #define C2R_WPB 1    // waves per workgroup (a workgroup's slots come back when its last wave ends)
 #endif
-template <typename WT, int OCC, bool PK = false>
+template <typename WT, int OCC, bool PK = false, bool TALLY = false>
 __global__ void __launch_bounds__(64 * C2R_WPB, OCC)
 k_c2r(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const bsx_seed_task_t *tasks, RgXPool X,
       bsx_region_t *out, unsigned long long out_cap, unsigned long long *out_cursor, long long *reg_off, int *reg_n,
@@ -1997,7 +2010,7 @@ k_c2r(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const bsx_s
 		const int l_query = uni(tasks[t].len), parent = uni(tasks[t].parent);
 		const uint32_t qoff = (uint32_t)uni((int)tasks[t].qoff);
 		const RgXHdr *H = (const RgXHdr*)(X.base + uni64(X.xoff[t]));
-		int status = rg_c2r<PK>(W, ix, sc, P, reads, l_query, parent, qoff, H, lane, counters, gap_tab, ctg_tab);
+		int status = rg_c2r<PK, TALLY>(W, ix, sc, P, reads, l_query, parent, qoff, H, lane, counters, gap_tab, ctg_tab, X);
 		WAVE_SYNC();
 		if constexpr (WT::HBM) { // publish: hundreds of regions, all lanes copy
 			const int nr = status ? 0 : uni(W.n_regs);
@@ -2392,7 +2405,10 @@ void launch_c2r(hipStream_t st, int grid, const RgLaunch &G, const RgXPoolArg &X
 	// the forms with their tables in LDS: `grid` counts groups of four waves; in HBM: workgroups, with c2r_hbm_slab_bytes(form == RG_C2R_HL) of `slab` each
 #define RG_C2R_(TAB, OCC, GRID, SLAB, ...) hipLaunchKernelGGL((k_c2r<TAB, OCC, ##__VA_ARGS__>), dim3(GRID), dim3(64 * C2R_WPB), 0, st, RG_COMMON_, X, RG_OUT_, cursor, next_list, next_count, G.counters, quota, (unsigned char*)(SLAB))
 	// (G.ext_pk: the instantiations whose extension rows are packed 16-bit; the forms for long reads have none)
-	if (G.ext_pk && form == RG_C2R_H) RG_C2R_(RgC2rH, 2, grid, slab, true);
+	// XA.rows ($BSX_PHASES): the counting instantiations of the two launches every ordinary chunk makes over records with extensions made ahead
+	if (XA.rows && form == RG_C2R_B) { if (G.ext_pk) RG_C2R_(RgC2rB, 2, grid * (4 / C2R_WPB), nullptr, true, true); else RG_C2R_(RgC2rB, 2, grid * (4 / C2R_WPB), nullptr, false, true); }
+	else if (XA.rows && form == RG_C2R) { if (G.ext_pk) RG_C2R_(RgC2r, 4, grid * (4 / C2R_WPB), nullptr, true, true); else RG_C2R_(RgC2r, 4, grid * (4 / C2R_WPB), nullptr, false, true); }
+	else if (G.ext_pk && form == RG_C2R_H) RG_C2R_(RgC2rH, 2, grid, slab, true);
 	else if (G.ext_pk && form == RG_C2R_B) RG_C2R_(RgC2rB, 2, grid * (4 / C2R_WPB), nullptr, true);
 	else if (G.ext_pk && form == RG_C2R) RG_C2R_(RgC2r, 4, grid * (4 / C2R_WPB), nullptr, true);
 	else

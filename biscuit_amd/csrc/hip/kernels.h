@@ -110,7 +110,7 @@ struct RgXPoolArg; struct RgLaunch;
 void launch_x4(hipStream_t st, int n_cu, const RgLaunch &G, const RgXPoolArg &X, void *jobs, unsigned long long job_cap, unsigned int *ctr32, unsigned long long *prof);   // G.n_tasks bounds the number of exported strand searches
 // K4 a lane per job (k_extl.hip) for the narrow queue of launch_x4's pool; called by launch_x4
 void launch_extl(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const RegParams &P, const uint8_t *reads, void *jobs, unsigned int jcap,
-                 unsigned int *ctr32, unsigned char *xbase, long long n_upper, unsigned long long *prof);
+                 unsigned int *ctr32, unsigned char *xbase, long long n_upper, unsigned long long *prof, unsigned int *rows = nullptr);   // rows: RgXPoolArg::rows
 void launch_extl_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t *jobs, bsx_ext_res_t *res,
                        unsigned int n, unsigned int *ctr32);
 void launch_ext4_batch(hipStream_t st, int n_cu, const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t *jobs, bsx_ext_res_t *res,
@@ -122,7 +122,8 @@ size_t regions_slab_bytes(int tier);
 // where the LDS tiers leave the chains that survive the filter for launch_c2r (chains -> regions): a byte pool with a bump cursor,
 // the block of task t at xoff[t], and the list of tasks that have one
 struct RgXPoolArg { unsigned char *base; unsigned long long cap; unsigned long long *cursor; long long *xoff; int *xlist; unsigned int *xcount;
-                    int ext; };   // ext: the records leave room for the extensions launch_x4 makes ahead of launch_c2r
+                    int ext;      // ext: the records leave room for the extensions launch_x4 makes ahead of launch_c2r
+                    unsigned int *rows; };   // $BSX_PHASES only (else null): the rows each job of launch_x4 ran, in the pool's allocation at base + rgx_rows_offset(cap) (rgx.hpp)
 // what every launch over one task list is given: the same at every call site of a tier sequence
 struct RgLaunch {
 	const DevIndex *ix; const DevScoring *sc; const RegParams *P;

@@ -16,6 +16,14 @@ struct RgXSeed { long long rbeg; short qbeg, len; int sb; };   // sb: mem_seed_t
 // ahead of that loop: what it needs of them to fill in the region.  status: 0 none (k_c2r extends inline), 1 valid
 struct RgXExt { long long rb, re; int qb, qe, score, truesc; int aw0, aw1; int si, status; };
 struct RgXPool { unsigned char *base; unsigned long long cap; unsigned long long *cursor; long long *xoff; int *xlist; unsigned int *xcount; int ext; };
+// $BSX_PHASES only (RgXPoolArg::rows set): behind the pool, at rgx_rows_offset(cap), the rows the job of each RgXExt slot ran.  The record has no
+// spare field and keeps its layout, and the pool's device-side description keeps its own (the kernels that count are instantiations of their
+// own and find the words from base and cap).  Slots are 48 bytes and do not overlap, so the slot at byte offset o of the pool owns word o / 48
+// (RGX_ROWS_AT): its rows, and RGX_ROWS_L when k_extl finished the job (k_ext4 otherwise).  launch_x4 zeroes the words.
+#define RGX_ROWS_AT(byte_off) ((byte_off) / sizeof(RgXExt))
+#define RGX_ROWS_L 0x80000000u
+static BSX_HD unsigned long long rgx_rows_offset(unsigned long long cap) { return (cap + 7) & ~7ull; }
+static inline size_t rgx_rows_bytes(unsigned long long cap) { return (size_t)(cap / sizeof(RgXExt) + 2) * sizeof(unsigned int); }
 static inline RgXPool rgx_pool(const RgXPoolArg *XA)
 {
 	RgXPool X; X.base = nullptr; X.cap = 0; X.cursor = nullptr; X.xoff = nullptr; X.xlist = nullptr; X.xcount = nullptr; X.ext = 0;

@@ -17,6 +17,7 @@
 #include "index_build.h"
 #include "tune.h"
 #include "ext_pk_bound.h"
+#include "rgx.hpp"
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[bsx-hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return BSX_E_NODEVICE; } } while (0)
 
@@ -1019,7 +1020,7 @@ static int rg_plan(RgBatch &B)
 	TRY(L.posoff.reserve((size_t)n * 8 + 64));
 	// what the LDS tiers export for the chains -> regions launch: ~0.5 KB per strand search (a task that finds no room goes to the next tier)
 	B.xcap = (unsigned long long)n * 2560 * lf + (64u << 20);   // (a dozen chains per strand search at hg38 size: 24 + 16 bytes each, 48 more for its extensions)
-	TRY(L.xpool.reserve((size_t)B.xcap));
+	TRY(L.xpool.reserve(B.trace ? (size_t)rgx_rows_offset(B.xcap) + rgx_rows_bytes(B.xcap) : (size_t)B.xcap));   // ($BSX_PHASES: behind the pool, the rows each extension made ahead ran, rgx.hpp)
 	TRY(L.xmeta.reserve((size_t)n * 12 + 64));
 	// the extensions of the exported chains' best seeds are made ahead of chains -> regions, four to a wavefront (k_ext4.hip); $BSX_X4=0: all
 	// of them inline in k_c2r (the tests compare the two).  Not for chunks whose lists the seed-SW filter rewrites after the export.
@@ -1049,6 +1050,7 @@ static int rg_plan(RgBatch &B)
 	++g_ext_forms[G.ext_pk ? 0 : 1];
 	M.X.base = (unsigned char*)L.xpool.p; M.X.cap = B.xcap; M.X.cursor = &SH->xpool_cursor; M.X.xcount = &M.c->front.x_count;
 	M.X.ext = B.use_x4 && !B.export_all ? 1 : 0;
+	M.X.rows = B.trace && M.X.ext ? (unsigned int*)((unsigned char*)L.xpool.p + rgx_rows_offset(B.xcap)) : nullptr;
 	return BSX_OK;
 }
 
@@ -1498,6 +1500,13 @@ static int rg_report(RgBatch &B)
 	HIPCHK(hipMemsetAsync(ctr + CTR_EXT, 0, sizeof(xp), L.st));
 	if (xp[EXT4_JOBS] || xp[EXTL_JOBS]) fprintf(stderr, "[M::regions_batch] k_ext4: %llu jobs, %llu rows in %llu wave trips (%.2f rows per trip), %llu passes between extensions, %.2f slots per trip, %llu rows of narrow jobs\n", xp[0], xp[1], xp[2], xp[2] ? (double)xp[1] / xp[2] : 0.0, xp[3], xp[2] ? (double)xp[4] / xp[2] : 0.0, xp[5]);
 	if (xp[EXTL_JOBS]) fprintf(stderr, "[M::regions_batch] k_extl: %llu jobs (%llu sent on to k_ext4), %llu rows in %llu wave trips (%.1f rows per trip), %llu passes between extensions\n", xp[6], xp[10], xp[7], xp[8], xp[8] ? (double)xp[7] / xp[8] : 0.0, xp[9]);
+	unsigned long long xw[CTR_X4W_N];
+	D2H(L.st, xw, ctr + CTR_X4W, sizeof(xw));
+	HIPCHK(hipMemsetAsync(ctr + CTR_X4W, 0, sizeof(xw), L.st));
+	if (xp[EXT4_JOBS] || xp[EXTL_JOBS]) for (int k = 0; k < 2; ++k)   // the extensions made ahead that the seed loops never read (first seed of a chain skipped as contained)
+		fprintf(stderr, "[M::regions_batch] %s: unread jobs %llu with %llu rows (%.3f%% of the kernel's rows) | of which inside the strand search's first region: %llu jobs, %llu rows (%.4f%%)\n",
+		        k ? "k_extl" : "k_ext4", xw[4 * k + X4W_JOBS], xw[4 * k + X4W_ROWS], xp[k ? EXTL_ROWS : EXT4_ROWS] ? 100.0 * xw[4 * k + X4W_ROWS] / xp[k ? EXTL_ROWS : EXT4_ROWS] : 0.0,
+		        xw[4 * k + X4W_JOBS_R0], xw[4 * k + X4W_ROWS_R0], xp[k ? EXTL_ROWS : EXT4_ROWS] ? 100.0 * xw[4 * k + X4W_ROWS_R0] / xp[k ? EXTL_ROWS : EXT4_ROWS] : 0.0);
 	unsigned long long pf[CTR_STAGE_N];
 	D2H(L.st, pf, ctr + CTR_STAGE, sizeof(pf));
 	HIPCHK(hipMemsetAsync(ctr + CTR_STAGE, 0, sizeof(pf), L.st));
