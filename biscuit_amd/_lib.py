@@ -88,7 +88,7 @@ class GlbTag(C.Structure):
 
 class Backend(C.Structure):  # bsx_backend_t (csrc/host/bsx_core.h)
     _fields_ = [("ctx", C.c_void_p), ("name", C.c_char_p)] + [(n, C.c_void_p) for n in
-                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p), ("sort_batch", C.c_void_p), ("meth_batch", C.c_void_p)]
+                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p), ("sort_batch", C.c_void_p), ("meth_batch", C.c_void_p), ("meth_sites", C.c_void_p)]
 
 
 class GlbCtx(C.Structure):  # bsx_glb_ctx_t: [strand hypothesis][A, C, G, T, N context][retained, converted]
@@ -121,6 +121,19 @@ class MethJob(C.Structure):  # bsx_meth_job_t: what QcJob has (flags: QC_REVERSE
 
 class MethTables(C.Structure):  # bsx_meth_tables_t: per context CA, CC, CG, CT, CN the reported sites and the sum of their betas in thousandths
     _fields_ = [("k", C.c_uint64 * 5), ("s", C.c_uint64 * 5)]
+
+
+class MethSiteOpt(C.Structure):  # bsx_meth_site_opt_t: METH_TYPE_*, merge (type cg only), the least ret + conv of a site that is kept
+    _fields_ = [("type", C.c_int32), ("merge", C.c_int32), ("min_cov", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class MethSite(C.Structure):  # bsx_meth_site_t: the position the record belongs to, ret and ret + conv of its C and G sides, class | METH_SITE_C | METH_SITE_G
+    _fields_ = [("fpos", C.c_int64), ("ret_c", C.c_uint32), ("n_c", C.c_uint32), ("ret_g", C.c_uint32), ("n_g", C.c_uint32), ("flags", C.c_uint32), ("pad", C.c_uint32)]
+
+
+METH_TYPES = {"cg": 0, "ch": 1, "c": 2}                                       # BSX_METH_TYPE_*
+METH_CLASSES = ["CG", "CHG", "CHH", "CN"]                                     # BSX_METH_CLS_*: flags & 3
+METH_SITE_C, METH_SITE_G = 4, 8
 
 
 class QcCounts(C.Structure):  # bsx_qc_counts_t: [CpG, CpH][read][position][converted, retained], the eight totals, confusion[tag * 4 + inferred]

@@ -352,6 +352,30 @@ class Device(Batches):
         f.argtypes = [C.c_void_p]
         B.check(f(self.h), "bsx_meth_reset")
 
+    def meth_sites_window(self, f_lo, f_hi, typ="cg", min_cov=1, merge=False, cap=1 << 20):
+        """bsx_meth_sites, one call -> (records, f_next): the records (numpy structured array of _lib.MethSite's layout) of as many whole tiles
+        of [f_lo, f_hi) from f_lo on as fit cap records, and where the next call goes on (f_hi: nothing is left)"""
+        opt = B.MethSiteOpt(B.METH_TYPES[typ], int(bool(merge)), int(min_cov), 0)
+        out = np.zeros(max(int(cap), 0), dtype=np.dtype(B.MethSite))
+        n, f_next = C.c_int64(-1), C.c_int64(-1)
+        f = B.lib().bsx_meth_sites
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        B.check(f(self.h, C.byref(opt), int(f_lo), int(f_hi), _p(out), int(cap), C.byref(n), C.byref(f_next)), "bsx_meth_sites")
+        return out[:n.value].copy(), f_next.value
+
+    def meth_sites(self, f_lo, f_hi, typ="cg", min_cov=1, merge=False, cap=1 << 20):
+        """the methylation sites of the device's counters that belong to [f_lo, f_hi) (k_msite.hip) -> numpy structured array of _lib.MethSite's
+        layout in ascending position: what `biscuit pileup` -> `biscuit vcf2bed -t typ -k min_cov` lists, with merge what `biscuit mergecg`
+        makes of it (typ cg only); window by window through a buffer of cap records (at least _lib.COV_TILE)"""
+        parts = []
+        while True:
+            recs, f_next = self.meth_sites_window(f_lo, f_hi, typ, min_cov, merge, cap)
+            parts.append(recs)
+            if f_next >= f_hi:
+                return np.concatenate(parts)
+            assert f_next > f_lo
+            f_lo = f_next
+
     def markdup_batch(self, keys, first_ordinal):
         """bsx_markdup_batch: keys = uint64[n, 2] (_lib.MarkdupKey's layout; both words all ones: skipped), the template with ordinal
         first_ordinal + i at keys[i] -> uint8[n], 1 where an equal key with a lower ordinal is in the device's table or earlier in the batch"""

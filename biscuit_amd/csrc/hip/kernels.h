@@ -72,6 +72,13 @@ size_t meth_state_entries(long long l_pac);
 void launch_meth_add(hipStream_t st, const DevIndex &ix, const uint8_t *reads, long long reads_len, const bsx_meth_job_t *jobs, long long n,
                      const uint32_t *pool, long long pool_len, void *state, int n_cu);
 void launch_meth_tables(hipStream_t st, int n_cu, const DevIndex &ix, const void *state, long long n_tiles, int flush_tiles, unsigned long long *out);
+// k_msite.hip: the methylation sites of that state (bsx_meth_sites) over the nt tiles from tile t_lo on.  launch_msite_count: cnt[i] = the records
+// that belong to tile t_lo + i and to [f_lo, f_hi).  launch_msite_emit: base = nt + 1 exclusive sums of those counts; the records of tile
+// t_lo + i go to out[base[i] .. base[i + 1]), and nothing is written at or beyond out[base[i + 1]]
+void launch_msite_count(hipStream_t st, int n_cu, const DevIndex &ix, const void *state, const bsx_meth_site_opt_t &opt, long long f_lo, long long f_hi,
+                        long long t_lo, long long nt, uint32_t *cnt);
+void launch_msite_emit(hipStream_t st, int n_cu, const DevIndex &ix, const void *state, const bsx_meth_site_opt_t &opt, long long f_lo, long long f_hi,
+                       long long t_lo, long long nt, const uint32_t *base, bsx_meth_site_t *out);
 // k_markdup.hip: the device's table of template keys (bsx_markdup_batch).  A slot: claim word (0: empty), lowest ordinal, the key (all ones: none yet)
 struct MdSlot { unsigned long long claim, ord, k0, k1; };
 enum { MD_CTR_TAKEN = 0, MD_CTR_OPEN = 1, MD_CTR_LOST = 2 };   // ctr[] of the two launchers below

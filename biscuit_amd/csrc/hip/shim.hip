@@ -2450,7 +2450,61 @@ static int dev_meth_reset(bsx_device_t *d)
 	if (d->meth_st) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(d->meth_st); d->meth_st = nullptr; }
 	return BSX_OK;
 }
+// the methylation sites of the state (k_msite.hip): the tiles' counts come to the host, which sums them and cuts the window that fits cap; the
+// records of that window are written on the device at their final places and come down in one copy
+static int dev_meth_sites(bsx_device_t *d, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next)
+{
+	if (!d || !d->has_index) return BSX_E_NODEVICE;
+	if (!opt || !n || !f_next || f_lo < 0 || f_lo > f_hi || f_hi > d->ix.l_pac || cap < BSX_COV_TILE || !out) return BSX_E_ARG;
+	if (opt->type < BSX_METH_TYPE_CG || opt->type > BSX_METH_TYPE_C || opt->min_cov < 1 || (opt->merge && opt->type != BSX_METH_TYPE_CG)) return BSX_E_ARG;
+	*n = 0; *f_next = f_hi;
+	if (f_lo == f_hi) return BSX_OK;
+	if (cap > (1ll << 31) - 1) cap = (1ll << 31) - 1;   // 32-bit places
+	std::lock_guard<std::mutex> lock(d->meth_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	if (!d->meth_st) return BSX_OK;   // no batch yet: no site
+	HIPCHK(hipDeviceSynchronize());   // every lane's batches
+	const long long t_lo = f_lo / BSX_COV_TILE, nt = (f_hi + BSX_COV_TILE - 1) / BSX_COV_TILE - t_lo;
+	bsx_meth_site_opt_t o = *opt;
+	o.merge = o.merge ? 1 : 0; o.pad = 0;
+	uint32_t *cnt = nullptr;    // nt counts, then the window's nt + 1 exclusive sums
+	bsx_meth_site_t *recs = nullptr;
+	if (hipMalloc((void**)&cnt, ((size_t)nt + 1) * 4) != hipSuccess) { (void)hipGetLastError(); return BSX_E_NOMEM; }
+	std::vector<uint32_t> h((size_t)nt + 1);
+	launch_msite_count(0, d->n_cu, d->ix, d->meth_st, o, f_lo, f_hi, t_lo, nt, cnt);
+	hipError_t e = hipGetLastError();
+	if (e == hipSuccess) e = hipMemcpy(h.data(), cnt, (size_t)nt * 4, hipMemcpyDeviceToHost);
+	long long w = 0;            // tiles of the window
+	uint64_t total = 0;
+	int rc = BSX_OK;
+	if (e == hipSuccess) {
+		for (; w < nt; ++w) {
+			const uint32_t c = h[(size_t)w];
+			if (c > BSX_COV_TILE) { rc = BSX_E_INTERNAL; break; }
+			if (total + c > (uint64_t)cap) break;
+			h[(size_t)w] = (uint32_t)total; total += c;
+		}
+		if (rc == BSX_OK) h[(size_t)w] = (uint32_t)total;
+	}
+	if (e == hipSuccess && rc == BSX_OK && total) {
+		if (hipMalloc((void**)&recs, (size_t)total * sizeof(bsx_meth_site_t)) != hipSuccess) { (void)hipGetLastError(); rc = BSX_E_NOMEM; }
+		if (rc == BSX_OK) e = hipMemcpy(cnt, h.data(), ((size_t)w + 1) * 4, hipMemcpyHostToDevice);
+		if (rc == BSX_OK && e == hipSuccess) { launch_msite_emit(0, d->n_cu, d->ix, d->meth_st, o, f_lo, f_hi, t_lo, w, cnt, recs); e = hipGetLastError(); }
+		if (rc == BSX_OK && e == hipSuccess) e = hipMemcpy(out, recs, (size_t)total * sizeof(bsx_meth_site_t), hipMemcpyDeviceToHost);
+	}
+	if (recs) (void)hipFree(recs);
+	(void)hipFree(cnt);
+	HIPCHK(e);
+	if (rc != BSX_OK) return rc;
+	*n = (int64_t)total;
+	*f_next = w == nt ? f_hi : (int64_t)(t_lo + w) * BSX_COV_TILE;
+	return BSX_OK;
+}
 static_assert(sizeof(bsx_meth_tables_t) == 2 * BSX_METH_N_CTX * 8, "k_meth_walk's cells are bsx_meth_tables_t");
+extern "C" BSX_API int bsx_meth_sites(bsx_device_t *d, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next)
+{
+	return dev_meth_sites(d, opt, f_lo, f_hi, out, cap, n, f_next);
+}
 extern "C" BSX_API int bsx_meth_batch(bsx_device_t *d, int64_t n, const bsx_meth_job_t *jobs, const uint32_t *pool, size_t pool_len) { return lane_meth_batch(d, 0, n, jobs, pool, pool_len); }
 extern "C" BSX_API int bsx_meth_read(bsx_device_t *d, int64_t fpos, int64_t n, uint32_t *out) { return dev_meth_read(d, fpos, n, out); }
 extern "C" BSX_API int bsx_meth_tables(bsx_device_t *d, bsx_meth_tables_t *out) { return dev_meth_tables(d, out); }
@@ -2744,6 +2798,11 @@ static int be_meth(void *c, int op, int64_t n, const bsx_meth_job_t *j, const ui
 	return BSX_E_ARG;
 }
 
+static int be_meth_sites(void *c, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next)
+{
+	return dev_meth_sites(((LaneRef*)c)->d, opt, f_lo, f_hi, out, cap, n, f_next);
+}
+
 static int be_sort(void *c, int op, int64_t n, const uint64_t *keys, uint32_t *perm_out, int64_t *n_total, uint32_t **run_of)
 {
 	bsx_device_t *d = ((LaneRef*)c)->d;
@@ -2764,7 +2823,7 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	memset(out, 0, sizeof(*out));
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
-	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov; out->sort_batch = be_sort; out->meth_batch = be_meth;
+	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov; out->sort_batch = be_sort; out->meth_batch = be_meth; out->meth_sites = be_meth_sites;
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

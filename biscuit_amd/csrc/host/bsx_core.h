@@ -210,6 +210,9 @@ typedef struct bsx_backend {
 	 * BSX_METH_OP_BATCH (bsx_meth_batch over n jobs, the reads those of set_reads), BSX_METH_OP_TABLES (bsx_meth_tables into out),
 	 * BSX_METH_OP_RESET (bsx_meth_reset).  Without it the host keeps the counters (meth.c). */
 	int (*meth_batch)(void *ctx, int op, int64_t n, const bsx_meth_job_t *jobs, const uint32_t *pool, size_t pool_len, bsx_meth_tables_t *out);
+	/* optional (may be NULL; a backend that clears the struct has it NULL), set together with meth_batch: the methylation sites of those counters
+	 * (bsx_meth_sites).  A backend without meth_batch has the counters on the host, and meth.c lists the sites there. */
+	int (*meth_sites)(void *ctx, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next);
 } bsx_backend_t;
 enum { BSX_METH_OP_BATCH = 0, BSX_METH_OP_TABLES = 1, BSX_METH_OP_RESET = 2 };
 enum { BSX_SORT_OP_RUN = 0, BSX_SORT_OP_SCHEDULE = 1, BSX_SORT_OP_RESET = 2 };

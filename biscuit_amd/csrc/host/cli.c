@@ -77,6 +77,12 @@ static int usage(void)
 		"  qc-meth   : --qc-meth  with --qc PREFIX: BISCUITqc's PREFIX_totalBaseConversionRate.txt over the same records, as `biscuit pileup`, `biscuit vcf2bed\n"
 		"              -e -t c` and the script's awk make it at their defaults: per cytosine context the mean over the callable cytosines of retained /\n"
 		"              (retained + converted) to three places, -1 below 20 cytosines; one process only (refused with WORLD_SIZE > 1)\n"
+		"  meth-bed  : --meth-bed FILE  with --qc PREFIX --qc-meth: the per-cytosine methylation levels of the same counts, written when every record has\n"
+		"              been counted, as `biscuit pileup` -> `biscuit vcf2bed -t TYPE -k K` list them: contig, start, end, retained / (retained +\n"
+		"              converted) to three places, retained + converted; contigs in the order of the header's @SQ lines\n"
+		"              --meth-type cg|ch|c  the cytosines listed, by pileup's five-base context: CG, CHG and CHH, or all (default: cg)\n"
+		"              --meth-min-cov INT  only cytosines with at least INT retained + converted (default: 1)\n"
+		"              --meth-merge  what `biscuit mergecg` makes of that list: one line per CpG, both strands' counts together (type cg only)\n"
 		"  markdup   : --markdup  0x400 on every record of a template (a pair, or a single read) whose ends' unclipped 5' positions, strands and YD\n"
 		"              equal those of an earlier template of the input; one process only (refused with WORLD_SIZE > 1)\n"
 		"  sort      : --sort  the records in coordinate order: by the rank of RNAME among the header's @SQ lines ('*' last), POS, then forward before\n"
@@ -395,6 +401,24 @@ static int qc_cov_report(void)
 	bsx_cov_tables_free(&t);
 	return rc;
 }
+/* --meth-bed: the sites of the process's counters, contig by contig in the header's order */
+static int meth_bed_sites(void *ud, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next)
+{
+	(void)ud;
+	return bsx_process_qc_meth_sites(opt, f_lo, f_hi, out, cap, n, f_next);
+}
+static int meth_bed_report(const char *path, const bsx_index_t *idx, const char *hdr_line, const bsx_meth_site_opt_t *opt)
+{
+	char *h = bsx_sam_header(idx, hdr_line, 0);
+	int32_t *order = h ? bsx_meth_bed_order(idx, h) : 0;
+	FILE *f = order ? fopen(path, "w") : 0;
+	int rc = !order ? BSX_E_NOMEM : !f ? BSX_E_IO : bsx_meth_bed_write(f, idx, order, opt, meth_bed_sites, 0, 0, 0);
+	if (order && !f) fprintf(stderr, "[E::%s] cannot write %s\n", "main_align", path);
+	if (f && fclose(f) != 0 && rc == BSX_OK) rc = BSX_E_IO;
+	free(order); free(h);
+	if (rc != BSX_OK) fprintf(stderr, "[E::%s] writing the methylation BED file failed (%s)\n", "main_align", bsx_strerror(rc));
+	return rc;
+}
 static int qc_meth_report(void)
 {
 	bsx_meth_tables_t t;
@@ -441,10 +465,14 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		{"bsconv-max-cph-frac", required_argument, 0, 1006}, {"bsconv-max-cpy-frac", required_argument, 0, 1007},
 		{"bsconv-filter-u", no_argument, 0, 1008}, {"bsconv-show-filtered", no_argument, 0, 1009}, {"qc", required_argument, 0, 1010}, {"markdup", no_argument, 0, 1011},
 		{"qc-cov", no_argument, 0, 1012}, {"qc-topgc", required_argument, 0, 1013}, {"qc-botgc", required_argument, 0, 1014},
-		{"sort", no_argument, 0, 1015}, {"sort-tmp", required_argument, 0, 1016}, {"qc-meth", no_argument, 0, 1017}, {0, 0, 0, 0}
+		{"sort", no_argument, 0, 1015}, {"sort-tmp", required_argument, 0, 1016}, {"qc-meth", no_argument, 0, 1017},
+		{"meth-bed", required_argument, 0, 1018}, {"meth-type", required_argument, 0, 1019}, {"meth-min-cov", required_argument, 0, 1020}, {"meth-merge", no_argument, 0, 1021},
+		{0, 0, 0, 0}
 	};
 	bsx_bsconv_conf_t bsconv;
 	int bsconv_on = 0, qc_on = 0, markdup_on = 0, qc_cov_on = 0, qc_meth_on = 0;
+	const char *meth_bed = 0, *meth_type = 0, *meth_min_cov = 0;
+	bsx_meth_site_opt_t meth_opt = {BSX_METH_TYPE_CG, 0, 1, 0};   /* vcf2bed.c:300: -k 1 */
 	const char *gc_bed[2] = {0, 0}, *sort_tmp = 0;
 	int sort_on = 0;
 	char *sort_hdr = 0;
@@ -467,6 +495,10 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		else if (c == 1015) sort_on = 1;
 		else if (c == 1016) sort_tmp = optarg;
 		else if (c == 1017) qc_meth_on = 1;
+		else if (c == 1018) meth_bed = optarg;
+		else if (c == 1019) meth_type = optarg;
+		else if (c == 1020) meth_min_cov = optarg;
+		else if (c == 1021) meth_opt.merge = 1;
 		else if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
 			bsconv_on = 1;
 			if (c == 1000) bsconv.annotate = 1;
@@ -620,6 +652,21 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	if (qc_cov_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", QC_COV_RANKS_MSG); return 1; }
 	if (qc_meth_on && !qc_on) { fprintf(stderr, "[E::%s] --qc-meth writes its table beside those of --qc: it needs --qc PREFIX\n", "main_align"); return 1; }
 	if (qc_meth_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", QC_METH_RANKS_MSG); return 1; }
+	if (meth_bed && !qc_meth_on) { fprintf(stderr, "[E::%s] --meth-bed lists the cytosines --qc-meth counts: it needs --qc PREFIX --qc-meth\n", "main_align"); return 1; }
+	if ((meth_type || meth_min_cov || meth_opt.merge) && !meth_bed) { fprintf(stderr, "[E::%s] --meth-type, --meth-min-cov and --meth-merge belong to --meth-bed FILE\n", "main_align"); return 1; }
+	if (meth_type) {
+		if (strcmp(meth_type, "cg") == 0) meth_opt.type = BSX_METH_TYPE_CG;
+		else if (strcmp(meth_type, "ch") == 0) meth_opt.type = BSX_METH_TYPE_CH;
+		else if (strcmp(meth_type, "c") == 0) meth_opt.type = BSX_METH_TYPE_C;
+		else { fprintf(stderr, "[E::%s] --meth-type %s: cg, ch or c\n", "main_align", meth_type); return 1; }
+	}
+	if (meth_min_cov) {
+		char *e = 0;
+		const long long k = strtoll(meth_min_cov, &e, 10);
+		if (e == meth_min_cov || *e || k < 1 || k > 0x7fffffffll) { fprintf(stderr, "[E::%s] --meth-min-cov %s: an integer of at least 1\n", "main_align", meth_min_cov); return 1; }
+		meth_opt.min_cov = (uint32_t)k;
+	}
+	if (meth_opt.merge && meth_opt.type != BSX_METH_TYPE_CG) { fprintf(stderr, "[E::%s] --meth-merge joins the two cytosines of a CpG: it needs --meth-type cg\n", "main_align"); return 1; }
 	bsx_process_set_qc(qc_on);
 	bsx_process_set_qc_cov(qc_cov_on);
 	bsx_process_set_qc_meth(qc_meth_on);
@@ -865,7 +912,7 @@ loop_done:
 	if (bsconv_on && bsx_shard_world <= 1) bsconv_report();   /* (several ranks: rank 0 reports the sum, bsx_align_main_ranks_with) */
 	if (qc_on) { /* the device's counts are read while it is open; several ranks: kept for the sum */
 		g_qc_paired = (opt->flag & BSX_F_PE) ? 1 : 0;
-		if (bsx_shard_world <= 1) { if (rc == 0 && qc_report() != BSX_OK) rc = 1; if (rc == 0 && qc_cov_on && qc_cov_report() != BSX_OK) rc = 1; if (rc == 0 && qc_meth_on && qc_meth_report() != BSX_OK) rc = 1; }
+		if (bsx_shard_world <= 1) { if (rc == 0 && qc_report() != BSX_OK) rc = 1; if (rc == 0 && qc_cov_on && qc_cov_report() != BSX_OK) rc = 1; if (rc == 0 && qc_meth_on && qc_meth_report() != BSX_OK) rc = 1; if (rc == 0 && meth_bed && meth_bed_report(meth_bed, idx, hdr_line, &meth_opt) != BSX_OK) rc = 1; }
 		else if (bsx_process_qc_totals(0, 0) != BSX_OK) rc = 1;
 	}
 	if (markdup_on && bsx_verbose >= 3) {
@@ -952,7 +999,7 @@ BSX_API int bsx_align_main_ranks_with(int argc, char **argv, bsx_process_fn proc
 	int64_t n_chunks = 0, mine, *all;
 	if (world <= 1 || bsx_emit_hook) return bsx_align_main_with(argc, argv, process, ud, open_device);   /* (a launcher with its own hook: multi_gpu.py) */
 	if (rank < 0 || rank >= world) { fprintf(stderr, "[E::%s] RANK %d of WORLD_SIZE %d\n", "main_align", rank, world); return 1; }
-	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 3 && strncmp("--markdup", argv[k], strlen(argv[k])) == 0) { /* (any abbreviation getopt_long takes: no other long option begins with --m) */ fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; } }   /* (before any transport is opened) */
+	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 4 && strncmp("--markdup", argv[k], strlen(argv[k])) == 0) { /* (any abbreviation getopt_long takes: --m is also the start of --meth-bed) */ fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; } }   /* (before any transport is opened) */
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 6 && strncmp("--qc-cov", argv[k], strlen(argv[k])) == 0) { /* (--qc-c, --qc-co: what getopt_long takes for it) */ fprintf(stderr, "[E::%s] %s\n", "main_align", QC_COV_RANKS_MSG); return 1; } }
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 6 && strncmp("--qc-meth", argv[k], strlen(argv[k])) == 0) { /* (--qc-m .. --qc-met: what getopt_long takes for it) */ fprintf(stderr, "[E::%s] %s\n", "main_align", QC_METH_RANKS_MSG); return 1; } }
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strncmp(argv[k], "--s", 3) == 0) { /* (--sort, --sort-tmp and every abbreviation: no other long option begins with --s) */ fprintf(stderr, "[E::%s] %s\n", "main_align", SORT_RANKS_MSG); return 1; } }

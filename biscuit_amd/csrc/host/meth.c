@@ -1,7 +1,9 @@
 /* meth.c -- BISCUITqc's base-averaged conversion table while aligning: what scripts/QC.sh:423-450 derives with `biscuit pileup`, `biscuit vcf2bed
  * -e -t c` and awk from a sorted BAM, from four counters per forward reference position kept while the records are written.  Per slice the jobs
  * qc.c built go to the backend's counters (k_meth.hip); a backend without the seam (the CPU checker's) keeps the same counters here and makes
- * the sums here.  Also the beta in thousandths without printf, and the file. */
+ * the sums here.  Also the beta in thousandths without printf, and the file.  And --meth-bed: the methylation sites of the same counters -- the
+ * host statement of what k_msite.hip lists, the state's hand-over to the backend -- their lines without printf, the contig order of a SAM
+ * header, and the BED file window by window. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -124,7 +126,7 @@ int bsx_meth_attach(bsx_meth_state_t *c, const bsx_backend_t *be, const bsx_inde
 	int rc = BSX_OK;
 	pthread_mutex_lock(&c->mu);
 	if (!c->attached) {
-		if (be->meth_batch) { rc = be->meth_batch(be->ctx, BSX_METH_OP_RESET, 0, 0, 0, 0, 0); c->fn = be->meth_batch; c->ctx = be->ctx; }
+		if (be->meth_batch) { rc = be->meth_batch(be->ctx, BSX_METH_OP_RESET, 0, 0, 0, 0, 0); c->fn = be->meth_batch; c->sites = be->meth_sites; c->ctx = be->ctx; }
 		else if (!(c->cnt = (uint32_t*)calloc((size_t)idx->ref.l_pac + 1, 16))) rc = BSX_E_NOMEM;
 		c->idx = idx;
 		if (rc == BSX_OK) c->attached = 1;
@@ -181,4 +183,211 @@ BSX_API int bsx_meth_write(const char *prefix, const bsx_meth_tables_t *t)
 	}
 	fprintf(f, "\n");
 	return fclose(f) != 0 ? BSX_E_IO : BSX_OK;
+}
+
+/* ------------------------------------------------------------------ the methylation sites of the counters (--meth-bed): the rule on plain arrays */
+typedef struct { uint32_t ret, n; int cls, isg, kept; } msite_t;
+
+/* the site at f: pileup's CX (bisc_utils.c:33-72) over f - 2 .. f + 2 on the cytosine's own strand, vcf2bed's -t and -k */
+static msite_t host_site(const bsx_index_t *idx, const uint32_t *cnt, const bsx_meth_site_opt_t *opt, int64_t f)
+{
+	const int64_t L = idx->ref.l_pac;
+	msite_t s = {0, 0, BSX_METH_CLS_CN, 0, 0};
+	const uint32_t *c;
+	int b, d, full, n1, n2;
+	if (f < 0 || f >= L) return s;
+	b = bsx_pac_get(idx->pac, f);
+	c = cnt + 4 * f;
+	if ((b != 1 && b != 2) || c[0] + c[1] == 0 || in_hole(idx, f)) return s;
+	if (c[3] != 0 && !(20ull * c[3] < (uint64_t)c[0] + c[2])) return s;   /* pileup.c:472-484 */
+	full = f >= 2 && f + 2 < L;
+	for (d = -2; d <= 2 && full; ++d) if ((d != -2 && ctg_start(idx, f + d)) || (d != 0 && in_hole(idx, f + d))) full = 0;
+	if (full) {
+		n1 = b == 1 ? bsx_pac_get(idx->pac, f + 1) : 3 - bsx_pac_get(idx->pac, f - 1);
+		n2 = b == 1 ? bsx_pac_get(idx->pac, f + 2) : 3 - bsx_pac_get(idx->pac, f - 2);
+		s.cls = n1 == 2 ? BSX_METH_CLS_CG : n2 == 2 ? BSX_METH_CLS_CHG : BSX_METH_CLS_CHH;
+	}
+	s.ret = c[0]; s.n = c[0] + c[1]; s.isg = b == 2;
+	s.kept = (opt->type == BSX_METH_TYPE_C || (opt->type == BSX_METH_TYPE_CG ? s.cls == BSX_METH_CLS_CG : s.cls == BSX_METH_CLS_CHG || s.cls == BSX_METH_CLS_CHH))
+	         && s.n >= opt->min_cov;
+	return s;
+}
+
+static int site_opt_ok(const bsx_meth_site_opt_t *opt)
+{
+	return opt && opt->type >= BSX_METH_TYPE_CG && opt->type <= BSX_METH_TYPE_C && opt->min_cov >= 1 && !(opt->merge && opt->type != BSX_METH_TYPE_CG);
+}
+
+int bsx_meth_host_sites(const bsx_index_t *idx, const uint32_t *cnt, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out,
+                        int64_t cap, int64_t *n, int64_t *f_next)
+{
+	int64_t tb, f, got = 0;
+	if (!site_opt_ok(opt) || !n || !f_next || !out || f_lo < 0 || f_lo > f_hi || f_hi > idx->ref.l_pac || cap < BSX_COV_TILE) return BSX_E_ARG;
+	for (tb = f_lo / BSX_COV_TILE * BSX_COV_TILE; tb < f_hi; tb += BSX_COV_TILE) { /* whole tiles: one that does not fit is left to the next call */
+		const int64_t a = tb > f_lo ? tb : f_lo, e = tb + BSX_COV_TILE < f_hi ? tb + BSX_COV_TILE : f_hi, got0 = got;
+		for (f = a; f < e; ++f) {
+			const msite_t s = host_site(idx, cnt, opt, f);
+			bsx_meth_site_t r;
+			if (!s.kept) continue;
+			memset(&r, 0, sizeof(r));
+			r.fpos = f;
+			if (!opt->merge) {
+				if (s.isg) { r.ret_g = s.ret; r.n_g = s.n; } else { r.ret_c = s.ret; r.n_c = s.n; }
+				r.flags = (uint32_t)s.cls | (s.isg ? BSX_METH_SITE_G : BSX_METH_SITE_C);
+			} else if (!s.isg) { /* mergecg.c:206-215: the kept G behind a kept C goes into the C's line */
+				const msite_t g = host_site(idx, cnt, opt, f + 1);
+				r.ret_c = s.ret; r.n_c = s.n; r.flags = BSX_METH_CLS_CG | BSX_METH_SITE_C;
+				if (g.kept && g.isg) { r.ret_g = g.ret; r.n_g = g.n; r.flags |= BSX_METH_SITE_G; }
+			} else {
+				const msite_t p = host_site(idx, cnt, opt, f - 1);
+				if (p.kept && !p.isg) continue;
+				r.ret_g = s.ret; r.n_g = s.n; r.flags = (uint32_t)s.cls | BSX_METH_SITE_G;
+			}
+			if (got == cap) { *n = got0; *f_next = tb; return BSX_OK; }
+			out[got++] = r;
+		}
+	}
+	*n = got; *f_next = f_hi;
+	return BSX_OK;
+}
+
+int bsx_meth_state_sites(bsx_meth_state_t *c, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n,
+                         int64_t *f_next)
+{
+	int rc = BSX_OK;
+	if (!c->on || !site_opt_ok(opt) || !n || !f_next || !out || f_lo < 0 || f_lo > f_hi || cap < BSX_COV_TILE) return BSX_E_ARG;
+	pthread_mutex_lock(&c->mu);
+	if (!c->attached) { *n = 0; *f_next = f_hi; }   /* no chunk was aligned: no site */
+	else if (c->fn) rc = c->sites ? c->sites(c->ctx, opt, f_lo, f_hi, out, cap, n, f_next) : BSX_E_INTERNAL;
+	else rc = bsx_meth_host_sites(c->idx, c->cnt, opt, f_lo, f_hi, out, cap, n, f_next);
+	pthread_mutex_unlock(&c->mu);
+	return rc;
+}
+
+/* ------------------------------------------------------------------ the BED file (vcf2bed.c:150-185, mergecg.c:90-137) */
+static char *put_u64(char *p, uint64_t v)
+{
+	char t[24];
+	int k = 0;
+	do { t[k++] = (char)('0' + v % 10); v /= 10; } while (v);
+	while (k) *p++ = t[--k];
+	return p;
+}
+static char *put_milli(char *p, uint32_t m)   /* %1.3f of m thousandths */
+{
+	p = put_u64(p, m / 1000);
+	*p++ = '.'; *p++ = (char)('0' + m / 100 % 10); *p++ = (char)('0' + m / 10 % 10); *p++ = (char)('0' + m % 10);
+	return p;
+}
+/* mergecg.c:116-118 on one side: the beta as printed and read back (atof of d.ddd is the double nearest to milli / 1000), times the depth in
+ * double, rounded to an integer as a float */
+static float merged_side(uint32_t ret, uint32_t n)
+{
+	if (!n) return 0.0f;
+	return rintf((float)((double)bsx_meth_milli(ret, n) / 1000.0 * (double)(int)n));
+}
+
+BSX_API size_t bsx_meth_bed_line(char *buf, const char *name, int64_t ctg_off, const bsx_meth_site_opt_t *opt, const bsx_meth_site_t *r)
+{
+	const size_t l = strlen(name);
+	const int64_t f = r->fpos - ctg_off;
+	char *p = buf + l;
+	memcpy(buf, name, l);
+	*p++ = '\t';
+	if (!opt->merge) {
+		const uint32_t ret = r->flags & BSX_METH_SITE_G ? r->ret_g : r->ret_c, n = r->flags & BSX_METH_SITE_G ? r->n_g : r->n_c;
+		p = put_u64(p, (uint64_t)f); *p++ = '\t'; p = put_u64(p, (uint64_t)f + 1); *p++ = '\t';
+		p = put_milli(p, bsx_meth_milli(ret, n)); *p++ = '\t'; p = put_u64(p, n);
+	} else {
+		const int has_c = (r->flags & BSX_METH_SITE_C) != 0;
+		const uint32_t n_c = has_c ? r->n_c : 0, n_g = r->flags & BSX_METH_SITE_G ? r->n_g : 0, cov = n_c + n_g;
+		const int M = (int)(merged_side(r->ret_c, n_c) + merged_side(r->ret_g, n_g));
+		p = put_u64(p, (uint64_t)(has_c ? f : f - 1)); *p++ = '\t'; p = put_u64(p, (uint64_t)(has_c ? f + 2 : f + 1)); *p++ = '\t';
+		p = put_milli(p, bsx_meth_milli((uint32_t)M, cov)); *p++ = '\t'; p = put_u64(p, cov);
+		memcpy(p, "\tC:", 3); p += 3;
+		if (n_c) { p = put_milli(p, bsx_meth_milli(r->ret_c, n_c)); *p++ = ':'; p = put_u64(p, n_c); } else { memcpy(p, ".:0", 3); p += 3; }
+		memcpy(p, ",G:", 3); p += 3;
+		if (n_g) { p = put_milli(p, bsx_meth_milli(r->ret_g, n_g)); *p++ = ':'; p = put_u64(p, n_g); } else { memcpy(p, ".:0", 3); p += 3; }
+	}
+	*p++ = '\n';
+	return (size_t)(p - buf);
+}
+
+BSX_API int bsx_meth_bed_write(FILE *fp, const bsx_index_t *idx, const int32_t *order, const bsx_meth_site_opt_t *opt, bsx_meth_sites_fn sites, void *ud,
+                               int64_t cap, uint64_t *n_lines)
+{
+	bsx_meth_site_t *recs;
+	char *text;
+	size_t max_name = 0, line_cap;
+	uint64_t lines = 0;
+	int rc = BSX_OK, i;
+	if (!fp || !idx || !site_opt_ok(opt) || !sites || cap < 0 || (cap && cap < BSX_COV_TILE)) return BSX_E_ARG;
+	if (!cap) cap = 1 << 20;
+	for (i = 0; i < idx->ref.n_seqs; ++i) { const size_t l = strlen(idx->ref.anns[i].name); if (l > max_name) max_name = l; }
+	line_cap = max_name + 160;
+	recs = (bsx_meth_site_t*)malloc((size_t)cap * sizeof(*recs));
+	text = (char*)malloc(line_cap * 4096);   /* 4096 lines at a time */
+	if (!recs || !text) { free(recs); free(text); return BSX_E_NOMEM; }
+	for (i = 0; i < idx->ref.n_seqs && rc == BSX_OK; ++i) {
+		const bsx_ann_t *a = &idx->ref.anns[order ? order[i] : i];
+		int64_t f = a->offset, end = a->offset + a->len;
+		if (order && (order[i] < 0 || order[i] >= idx->ref.n_seqs)) { rc = BSX_E_ARG; break; }
+		while (f < end && rc == BSX_OK) {
+			int64_t n = 0, next = end, k;
+			size_t used = 0;
+			if ((rc = sites(ud, opt, f, end, recs, cap, &n, &next)) != BSX_OK) break;
+			if (n < 0 || n > cap || next <= f || next > end) { rc = BSX_E_INTERNAL; break; }
+			for (k = 0; k < n; ++k) {
+				if (recs[k].fpos < a->offset || recs[k].fpos >= end) { rc = BSX_E_INTERNAL; break; }
+				used += bsx_meth_bed_line(text + used, a->name, a->offset, opt, &recs[k]);
+				if (((k + 1) & 4095) == 0 || k + 1 == n) { if (fwrite(text, 1, used, fp) != used) { rc = BSX_E_IO; break; } used = 0; }
+			}
+			lines += (uint64_t)n;
+			f = next;
+		}
+	}
+	free(recs); free(text);
+	if (n_lines) *n_lines = lines;
+	return rc;
+}
+
+typedef struct { const char *name; int32_t idx; } order_name_t;
+static int order_name_cmp(const void *a, const void *b)
+{
+	const order_name_t *x = (const order_name_t*)a, *y = (const order_name_t*)b;
+	const int c = strcmp(x->name, y->name);
+	return c ? c : (x->idx > y->idx) - (x->idx < y->idx);
+}
+BSX_API int32_t *bsx_meth_bed_order(const bsx_index_t *idx, const char *hdr)
+{
+	const int ns = idx->ref.n_seqs;
+	int32_t *order = (int32_t*)malloc(sizeof(int32_t) * (size_t)(ns ? ns : 1));
+	order_name_t *by_name = (order_name_t*)malloc(sizeof(order_name_t) * (size_t)(ns ? ns : 1));
+	char *taken = (char*)calloc((size_t)(ns ? ns : 1), 1);
+	const char *p;
+	int i, n = 0;
+	if (!order || !by_name || !taken) { free(order); free(by_name); free(taken); return 0; }
+	for (i = 0; i < ns; ++i) { by_name[i].name = idx->ref.anns[i].name; by_name[i].idx = i; }
+	qsort(by_name, (size_t)ns, sizeof(*by_name), order_name_cmp);
+	for (p = hdr; p && *p; ) { /* the @SQ lines as written; the first of two equal names counts */
+		const char *eol = strchr(p, '\n'), *end = eol ? eol : p + strlen(p), *f = p + 3;
+		if (strncmp(p, "@SQ\t", 4) == 0) while (f < end) { /* the SN field */
+			const char *g = (const char*)memchr(f + 1, '\t', (size_t)(end - f - 1));
+			if (!g) g = end;
+			if (strncmp(f + 1, "SN:", 3) == 0 && f + 4 <= g) {
+				const size_t l = (size_t)(g - (f + 4));
+				int lo = 0, hi = ns;   /* the first contig of the index, in name order, whose name is not below this one */
+				while (lo < hi) { const int mid = (lo + hi) >> 1; if (strncmp(by_name[mid].name, f + 4, l) < 0) lo = mid + 1; else hi = mid; }
+				if (lo < ns && strncmp(by_name[lo].name, f + 4, l) == 0 && by_name[lo].name[l] == 0 && !taken[by_name[lo].idx]) {
+					taken[by_name[lo].idx] = 1; order[n++] = by_name[lo].idx;   /* (of the names that begin with it the equal one comes first; equal ones by index) */
+				}
+				break;
+			}
+			f = g;
+		}
+		p = eol ? eol + 1 : 0;
+	}
+	for (i = 0; i < ns; ++i) if (!taken[i]) order[n++] = i;   /* no @SQ line: behind the others, in the index's order */
+	free(by_name); free(taken);
+	return order;
 }

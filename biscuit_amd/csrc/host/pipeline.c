@@ -161,6 +161,10 @@ static int qc_meth_set(bsx_qc_state_t *q, int on)
 }
 BSX_API int bsx_process_set_qc_meth(int on) { return qc_meth_set(&g_qc, on); }
 BSX_API int bsx_process_qc_meth_tables(bsx_meth_tables_t *out) { return bsx_meth_state_tables(&g_qc.meth, out); }
+BSX_API int bsx_process_qc_meth_sites(const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next)
+{
+	return bsx_meth_state_sites(&g_qc.meth, opt, f_lo, f_hi, out, cap, n, f_next);
+}
 
 /* ------------------------------------------------------------------ duplicate marking while aligning (markdup.c): setting and totals of the process (a stream has its own) */
 static bsx_md_state_t g_md = BSX_MD_STATE_INIT;
@@ -1818,6 +1822,12 @@ BSX_API int bsx_stream_qc_meth_tables(bsx_stream_t *s, bsx_meth_tables_t *out)
 {
 	if (!s) return BSX_E_ARG;
 	return bsx_meth_state_tables(s->qc.on ? &s->qc.meth : &g_qc.meth, out);
+}
+BSX_API int bsx_stream_qc_meth_sites(bsx_stream_t *s, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n,
+                                     int64_t *f_next)
+{
+	if (!s) return BSX_E_ARG;
+	return bsx_meth_state_sites(s->qc.on ? &s->qc.meth : &g_qc.meth, opt, f_lo, f_hi, out, cap, n, f_next);
 }
 
 BSX_API int bsx_stream_set_markdup(bsx_stream_t *s, int on)

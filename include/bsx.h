@@ -12,6 +12,7 @@
 
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -420,6 +421,38 @@ int bsx_meth_read(bsx_device_t *dev, int64_t fpos, int64_t n, uint32_t *out);
 int bsx_meth_tables(bsx_device_t *dev, bsx_meth_tables_t *out);
 int bsx_meth_reset(bsx_device_t *dev);   /* the state freed: every counter zero */
 
+/* The methylation sites of the same state (k_msite.hip): what `biscuit pileup` -> `biscuit vcf2bed -t TYPE -k K` lists, or with `merge` what
+ * `biscuit mergecg` makes of that list, as fixed-size records in ascending forward position.  A site is a site of bsx_meth_tables.  Its class is
+ * pileup's CX (bisc_utils.c:33-72) over the five bases f - 2 .. f + 2 read on the cytosine's own strand: CN when one of them is in an N hole or
+ * not a base of the site's contig, else CG when the next base is G, else CHG when the one after it is G, else CHH.  type BSX_METH_TYPE_CG keeps
+ * class CG, _CH keeps CHG and CHH, _C keeps every class; then a site is kept when ret + conv >= min_cov (>= 1).  Without merge a record is one
+ * kept site: fpos its position, the C side filled at a reference C, the G side at a reference G.  With merge (type CG only: BSX_E_ARG otherwise)
+ * a kept G at f + 1 is joined to a kept C at f: that record has fpos = f and both sides; a C alone has fpos = f and the C side, a G alone
+ * fpos = its own position and the G side.  A record belongs to the position fpos. */
+#define BSX_METH_TYPE_CG 0
+#define BSX_METH_TYPE_CH 1
+#define BSX_METH_TYPE_C  2
+#define BSX_METH_CLS_CG  0
+#define BSX_METH_CLS_CHG 1
+#define BSX_METH_CLS_CHH 2
+#define BSX_METH_CLS_CN  3
+#define BSX_METH_SITE_C  4u   /* flags: the class in the two low bits (of the C where there is one, else of the G), the sides that are present */
+#define BSX_METH_SITE_G  8u
+typedef struct bsx_meth_site_opt { int32_t type, merge; uint32_t min_cov, pad; } bsx_meth_site_opt_t;
+typedef struct bsx_meth_site {
+	int64_t fpos;
+	uint32_t ret_c, n_c;   /* retained and ret + conv of the C side, zero when it is absent */
+	uint32_t ret_g, n_g;   /* of the G side */
+	uint32_t flags;
+	uint32_t pad;
+} bsx_meth_site_t;
+/* the records that belong to [f_lo, f_hi), 0 <= f_lo <= f_hi <= l_pac, taken tile by tile (BSX_COV_TILE positions, tiles start at multiples of
+ * it): out gets the records of as many whole tiles from f_lo on as fit cap records, *n their number, *f_next the start of the first tile left
+ * out, or f_hi when none is: the caller goes on from there.  cap < BSX_COV_TILE (a tile may hold that many) is BSX_E_ARG and writes nothing.
+ * It waits for the batches in flight; the state is only read; without a state there is no record. */
+int bsx_meth_sites(bsx_device_t *dev, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n,
+                   int64_t *f_next);
+
 /* Duplicate templates (k_markdup.hip): a table of template keys that stays on the device until bsx_markdup_reset or bsx_device_close.
  * A key is the ordered pair of the template's ends, w[0] = read 1 (or the single read), w[1] = read 2; an end that is not placed (its primary
  * record has 0x4) is 0, the second end of a single read is BSX_MD_SINGLE: a single read never equals a pair, not even one whose read 2 is not
@@ -681,6 +714,29 @@ int  bsx_process_qc_meth_tables(bsx_meth_tables_t *out);
 int  bsx_meth_write(const char *prefix, const bsx_meth_tables_t *t);
 /* the beta in thousandths: the integer printf("%1.3f", (double)r / (double)n) shows, times 1000 (0 <= r <= n, n > 0), without printf */
 uint32_t bsx_meth_milli(uint32_t r, uint32_t n);
+
+/* The per-cytosine methylation BED while aligning (--meth-bed): the sites of the same counters (bsx_meth_sites; meth.c for a backend without
+ * the seam), with set_qc_meth on, after bsx_stream_flush / while the device is open.  A state no record has reached yet has no site. */
+int  bsx_stream_qc_meth_sites(bsx_stream_t *s, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap,
+                              int64_t *n, int64_t *f_next);
+int  bsx_process_qc_meth_sites(const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n,
+                               int64_t *f_next);
+/* the file: contig by contig in `order` (n_seqs indices of the index's contigs; NULL: the index's order; bsx_meth_bed_order makes it from a SAM
+ * header: the contigs in the order of its @SQ lines, the first of two equal names counting, those without a line behind the others in the
+ * index's order; free() it), every contig window by window through `sites` (a bsx_meth_sites / bsx_*_qc_meth_sites over `ud`) with a buffer of
+ * cap records (0: 1 << 20), every record as a line:
+ *   without merge  name\tf\tf + 1\tB\tn\n            f the 0-based offset in the contig, n = ret + conv, B = bsx_meth_milli(ret, n) as d.ddd
+ *   with merge     name\tbeg\tend\tB\tcov\tC:b:n,G:b:n\n   beg = f and end = f + 2 where there is a C, beg = f - 1 and end = f + 1 for a G alone;
+ *                  cov = nC + nG, B = bsx_meth_milli(M, cov) with M = (int)(rintf(bC * nC) + rintf(bG * nG)), b = milli / 1000.0 and the product in
+ *                  IEEE double, rintf of it as a float (mergecg.c:116-118), an absent side 0 and printed `C:.:0` / `G:.:0`
+ * No printf("%f"): digits from integers.  *n_lines (may be NULL): the lines written. */
+typedef int (*bsx_meth_sites_fn)(void *ud, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n,
+                                 int64_t *f_next);
+int  bsx_meth_bed_write(FILE *f, const bsx_index_t *idx, const int32_t *order, const bsx_meth_site_opt_t *opt, bsx_meth_sites_fn sites, void *ud,
+                        int64_t cap, uint64_t *n_lines);
+int32_t *bsx_meth_bed_order(const bsx_index_t *idx, const char *sam_header);
+/* one record as its line into buf (at least 160 bytes beyond the contig's name); returns the line's length */
+size_t bsx_meth_bed_line(char *buf, const char *name, int64_t ctg_off, const bsx_meth_site_opt_t *opt, const bsx_meth_site_t *r);
 
 /* Duplicate marking while aligning (--markdup).  A template is one unit of the input, a pair or a single read; its ordinal is its 0-based index
  * in the input of the stream (or of the process) over all chunks.  Each end's primary record is the one with neither 0x100 nor 0x800; the
