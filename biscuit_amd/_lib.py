@@ -88,7 +88,7 @@ class GlbTag(C.Structure):
 
 class Backend(C.Structure):  # bsx_backend_t (csrc/host/bsx_core.h)
     _fields_ = [("ctx", C.c_void_p), ("name", C.c_char_p)] + [(n, C.c_void_p) for n in
-                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p), ("sort_batch", C.c_void_p), ("meth_batch", C.c_void_p), ("meth_sites", C.c_void_p)]
+                ("set_opt", "set_reads", "seed_batch", "sa_batch", "extend_batch", "sw_batch", "global_batch", "global_batch_tags", "regions_batch", "regions_finish", "regions_dedup")] + [("dedup_cap", C.c_int), ("regions_dedup2", C.c_void_p), ("msw_plan", C.c_void_p), ("global_batch_tags_ctx", C.c_void_p), ("qc_batch", C.c_void_p), ("markdup_batch", C.c_void_p), ("cov_batch", C.c_void_p), ("sort_batch", C.c_void_p), ("meth_batch", C.c_void_p), ("meth_sites", C.c_void_p), ("bam_encode", C.c_void_p), ("bgzf_deflate", C.c_void_p)]
 
 
 class GlbCtx(C.Structure):  # bsx_glb_ctx_t: [strand hypothesis][A, C, G, T, N context][retained, converted]
@@ -159,6 +159,10 @@ SORT_NO_RANK = 0xffffffff
 def sort_key(rank, pos, rev):
     """BSX_SORT_KEY"""
     return (int(rank) << 32) | (int(pos) << 1) | (1 if rev else 0)
+
+
+BGZF_BLOCK = 0xff00      # BSX_BGZF_BLOCK: payload bytes of every block of --bam but the header's last and the file's last
+BAM_E_LINE, BAM_E_TAG, BAM_E_INT, BAM_E_NAME, BAM_E_CIGAR, BAM_E_REF, BAM_E_QUAL = 1, 2, 3, 4, 5, 6, 7      # BSX_BAM_E_*: why a line is refused
 
 
 class MarkdupTotals(C.Structure):  # bsx_markdup_totals_t

@@ -144,6 +144,52 @@ def _libc_free(p):
     _libc.free(p)
 
 
+def bam_encode(handle, header, text):
+    """bsx_bam_encode: handle None = the host's own statement of the record rule (csrc/host/bam_rec.h, the source the device compiles)"""
+    L = B.lib()
+    refs = C.c_void_p()
+    L.bsx_bam_refs_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.bsx_bam_refs_close.argtypes = [C.c_void_p]
+    B.check(L.bsx_bam_refs_open(bytes(header), C.byref(refs)), "bsx_bam_refs_open")
+    out, cap, n, nrec, bad, why = C.c_void_p(), C.c_size_t(0), C.c_size_t(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
+    f = L.bsx_bam_encode
+    f.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int)]
+    try:
+        B.check(f(handle, refs, bytes(text), len(text), C.byref(out), C.byref(cap), C.byref(n), C.byref(nrec), C.byref(bad), C.byref(why)), "bsx_bam_encode")
+        return (C.string_at(out, n.value) if n.value else b""), bad.value, why.value
+    finally:
+        if out.value:
+            _libc_free(out)
+        L.bsx_bam_refs_close(refs)
+
+
+def bam_header(header):
+    """bsx_bam_header: the header part of the BAM payload for the header text (bytes)"""
+    L = B.lib()
+    out, n = C.c_void_p(), C.c_size_t(0)
+    L.bsx_bam_header.argtypes = [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    B.check(L.bsx_bam_header(bytes(header), C.byref(out), C.byref(n)), "bsx_bam_header")
+    try:
+        return C.string_at(out, n.value)
+    finally:
+        _libc_free(out)
+
+
+def bgzf_deflate(handle, payload):
+    """bsx_bgzf_deflate: handle None = the host's statement (zlib level 1 raw, stored when that is no smaller)"""
+    L = B.lib()
+    out, cap, n = C.c_void_p(), C.c_size_t(0), C.c_size_t(0)
+    f = L.bsx_bgzf_deflate
+    f.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    try:
+        B.check(f(handle, bytes(payload), len(payload), C.byref(out), C.byref(cap), C.byref(n)), "bsx_bgzf_deflate")
+        return C.string_at(out, n.value) if n.value else b""
+    finally:
+        if out.value:
+            _libc_free(out)
+
+
 def cov_tables_arrays(t):
     """a filled _lib.CovTables as int64 arrays (copies)"""
     return [np.ctypeslib.as_array(t.t[i].count, shape=(int(t.t[i].n_bins),)).astype(np.int64) for i in range(12 if t.have_gc else 4)]
@@ -422,6 +468,15 @@ class Device(Batches):
             return np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint32)), shape=(n.value,)).copy()
         finally:
             _libc_free(out)
+
+    def bam_encode(self, header, text):
+        """bsx_bam_encode on the device (k_bam.hip): SAM text (bytes, whole lines) under the @SQ lines of `header` (bytes) -> (the BAM records,
+        the 0-based index of the first refused line or -1, its _lib.BAM_E_* or 0); the records before a refused line are returned"""
+        return bam_encode(self.h, header, text)
+
+    def bgzf_deflate(self, payload):
+        """bsx_bgzf_deflate on the device (k_bgzf.hip): bytes -> the BGZF members of its 0xff00-byte blocks, behind each other (no EOF block)"""
+        return bgzf_deflate(self.h, payload)
 
     def sort_info(self):
         """bsx_sort_info -> (runs, keys) retained on the device"""

@@ -79,6 +79,33 @@ void launch_msite_count(hipStream_t st, int n_cu, const DevIndex &ix, const void
                         long long t_lo, long long nt, uint32_t *cnt);
 void launch_msite_emit(hipStream_t st, int n_cu, const DevIndex &ix, const void *state, const bsx_meth_site_opt_t &opt, long long f_lo, long long f_hi,
                        long long t_lo, long long nt, const uint32_t *base, bsx_meth_site_t *out);
+// k_bam.hip: SAM lines -> BAM records (bsx_bam_encode; the rule is csrc/host/bam_rec.h).  text: whole lines on a 16-byte boundary, len below 2^31.
+// launch_bam_count: cnt[t] = newlines of tile t (bam_n_tiles(len) tiles).  launch_bam_scan: out[i] = in[0] + .. + in[i - 1] for i <= n (n + 1 entries
+// out; in place allowed), one workgroup.  launch_bam_starts: base = those sums of cnt; start[0] = 0, start[r + 1] = one past the r-th newline.
+// launch_bam_size: size[i] = the record length of line i, 0 for a refused line, errs[i] = 0 or its BSX_BAM_E_*; bad[w] (bam_lines_grid(n_lines)
+// words) = the least (line << 4 | code) among lines 256 w .., all ones for none.  launch_bam_emit: record i at out + off[i] for i < n_lines
+// (errs: the same n_lines words).  The name table: n_names
+// names sorted bytewise, name k = names[noff[k] .. noff[k + 1]), nid[k] its refID
+long long bam_n_tiles(long long len);
+int bam_lines_grid(long long n_lines);
+void launch_bam_count(hipStream_t st, int n_cu, const char *text, long long len, uint32_t *cnt);
+void launch_bam_scan(hipStream_t st, const uint32_t *in, uint32_t *out, long long n);
+void launch_bam_starts(hipStream_t st, int n_cu, const char *text, long long len, const uint32_t *base, uint32_t *start);
+void launch_bam_size(hipStream_t st, const char *text, const uint32_t *start, long long n_lines, const char *names, const uint32_t *noff,
+                     const int32_t *nid, int n_names, uint32_t *size, int *errs, unsigned long long *bad);
+void launch_bam_emit(hipStream_t st, const char *text, const uint32_t *start, long long n_lines, const char *names, const uint32_t *noff,
+                     const int32_t *nid, int n_names, int *errs, const uint32_t *off, uint8_t *out);
+// k_bgzf.hip: payload -> BGZF members (bsx_bgzf_deflate), a workgroup per block of 0xff00 bytes: n_launch <= bgzf_grid(blocks left) blocks from
+// block b0 on per launch, with bgzf_tok_bytes(n_launch) / bgzf_cand_bytes(n_launch) of workspace; block b's member goes to slots + b * 65536,
+// its length to sizes[b].  payload on a 16-byte boundary.  crc_ops: bgzf_crc_ops' 256 words on the device.  launch_bgzf_compact: off = the n_blocks + 1 exclusive sums of sizes; member b moves to out + off[b]
+size_t bgzf_lds_bytes(void);
+int bgzf_grid(long long n_blocks);
+size_t bgzf_tok_bytes(int grid);
+size_t bgzf_cand_bytes(int grid);
+void bgzf_crc_ops(uint32_t *ops);
+void launch_bgzf_deflate(hipStream_t st, const uint8_t *payload, long long len, long long b0, int n_launch, const uint32_t *crc_ops, uint32_t *ws_tok,
+                        uint16_t *ws_cand, uint8_t *slots, uint32_t *sizes);
+void launch_bgzf_compact(hipStream_t st, int n_cu, const uint8_t *slots, const uint32_t *off, long long n_blocks, uint8_t *out);
 // k_markdup.hip: the device's table of template keys (bsx_markdup_batch).  A slot: claim word (0: empty), lowest ordinal, the key (all ones: none yet)
 struct MdSlot { unsigned long long claim, ord, k0, k1; };
 enum { MD_CTR_TAKEN = 0, MD_CTR_OPEN = 1, MD_CTR_LOST = 2 };   // ctr[] of the two launchers below

@@ -102,6 +102,13 @@ struct bsx_device {
 	hipStream_t sort_st = nullptr;
 	DevBuf sort_k[2], sort_p[2], sort_counts, sort_btot;
 	std::mutex sort_mu;
+	// --bam (k_bam.hip, k_bgzf.hip): the writer's stream (the writer thread encodes a finished chunk while the lanes align the next ones), the
+	// name table of the writer's header (uploaded once: bam_tab_serial says whose it is) and the working buffers of both stages
+	hipStream_t bam_st = nullptr;
+	uint64_t bam_tab_serial = 0;
+	DevBuf bam_names, bam_noff, bam_nid, bam_text, bam_cnt, bam_start, bam_size, bam_bad, bam_pay, bam_err;
+	DevBuf bz_in, bz_tok, bz_cand, bz_slots, bz_sizes, bz_out, bz_ops; bool bz_ops_ok = false;
+	std::mutex bam_mu;
 	Lane lane[BSX_LANES];   // scoring matrices and penalties are per lane (Lane::sc): chunks with different options may be in flight together
 	// Front halves of consecutive chunks are chained stage by stage (the seeding launch of chunk k+1 waits for that of chunk k, the
 	// region launches likewise): four chunks that share the device evenly all finish at the same moment, and the device then idles
@@ -204,6 +211,14 @@ static void sort_release(bsx_device *d)
 	d->sort_counts.release(); d->sort_btot.release();
 	if (d->sort_st) { (void)hipStreamDestroy(d->sort_st); d->sort_st = nullptr; }
 }
+static void bam_release(bsx_device *d)
+{
+	DevBuf *b[] = {&d->bam_names, &d->bam_noff, &d->bam_nid, &d->bam_text, &d->bam_cnt, &d->bam_start, &d->bam_size, &d->bam_bad, &d->bam_pay, &d->bam_err,
+	               &d->bz_in, &d->bz_tok, &d->bz_cand, &d->bz_slots, &d->bz_sizes, &d->bz_out, &d->bz_ops};
+	for (DevBuf *x : b) x->release();
+	d->bam_tab_serial = 0; d->bz_ops_ok = false;
+	if (d->bam_st) { (void)hipStreamDestroy(d->bam_st); d->bam_st = nullptr; }
+}
 
 extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 {
@@ -216,6 +231,7 @@ extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 	cov_release(d);
 	if (d->meth_st) { (void)hipFree(d->meth_st); d->meth_st = nullptr; }
 	sort_release(d);
+	bam_release(d);
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
 		L.reads.release(); L.qpack.release(); L.gath.release(); L.jobs.release(); L.res.release(); L.scratch.release(); L.scratch2.release(); L.out.release(); L.aux.release(); L.pool.release();
@@ -2738,6 +2754,131 @@ extern "C" BSX_API int bsx_sort_info(bsx_device_t *d, uint64_t *n_runs, uint64_t
 	return BSX_OK;
 }
 
+// ---- BAM output (k_bam.hip, k_bgzf.hip) ----
+extern "C" {
+#include "bam.h"
+}
+static int bam_host_grow(uint8_t **out, size_t *cap, size_t want)
+{
+	if (want <= *cap) return BSX_OK;
+	size_t m = *cap ? *cap : 4096;
+	while (m < want) m += m >> 1;
+	uint8_t *p = (uint8_t*)realloc(*out, m);
+	if (!p) return BSX_E_NOMEM;
+	*out = p; *cap = m;
+	return BSX_OK;
+}
+static int bam_stream(bsx_device_t *d) { if (!d->bam_st) HIPCHK(hipStreamCreateWithFlags(&d->bam_st, hipStreamNonBlocking)); return BSX_OK; }
+// text -> records: newlines counted per tile and summed on the device, line starts, a size pass (the first refused line comes back as one word per
+// workgroup), the sizes summed on the device, the emit pass; 4 + 8 x workgroups + 4 bytes come to the host between the launches, then the payload
+static int dev_bam_encode(bsx_device_t *d, const bsx_bam_refs_t *refs, const char *text, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len,
+                          int64_t *n_records, int64_t *bad_record, int *bad_why)
+{
+	if (!d) return BSX_E_NODEVICE;
+	if (!refs || !out || !out_cap || !out_len || !n_records || !bad_record || !bad_why || (len && !text)) return BSX_E_ARG;
+	*out_len = 0; *n_records = 0; *bad_record = -1; *bad_why = 0;
+	if (len == 0) return BSX_OK;
+	if (text[len - 1] != '\n' || len >= ((size_t)1 << 31)) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->bam_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc;
+	if ((rc = bam_stream(d)) != BSX_OK) return rc;
+	hipStream_t st = d->bam_st;
+	if (d->bam_tab_serial != refs->serial) { // the writer's name table, once
+		if ((rc = d->bam_names.reserve(refs->names_len + 16)) != BSX_OK || (rc = d->bam_noff.reserve(((size_t)refs->n + 1) * 4)) != BSX_OK ||
+		    (rc = d->bam_nid.reserve(((size_t)refs->n + 1) * 4)) != BSX_OK) return rc;
+		if (refs->names_len) HIPCHK(hipMemcpyAsync(d->bam_names.p, refs->names, refs->names_len, hipMemcpyHostToDevice, st));
+		HIPCHK(hipMemcpyAsync(d->bam_noff.p, refs->off, ((size_t)refs->n + 1) * 4, hipMemcpyHostToDevice, st));
+		if (refs->n) HIPCHK(hipMemcpyAsync(d->bam_nid.p, refs->id, (size_t)refs->n * 4, hipMemcpyHostToDevice, st));
+		HIPCHK(hipStreamSynchronize(st));
+		d->bam_tab_serial = refs->serial;
+	}
+	const long long nt = bam_n_tiles((long long)len);
+	if ((rc = d->bam_text.reserve(len + 16)) != BSX_OK || (rc = d->bam_cnt.reserve(((size_t)nt + 1) * 4)) != BSX_OK) return rc;
+	const char *d_text = (const char*)d->bam_text.p;
+	uint32_t *cnt = (uint32_t*)d->bam_cnt.p;
+	HIPCHK(hipMemcpyAsync(d->bam_text.p, text, len, hipMemcpyHostToDevice, st));
+	launch_bam_count(st, d->n_cu, d_text, (long long)len, cnt);
+	launch_bam_scan(st, cnt, cnt, nt);
+	HIPCHK(hipGetLastError());
+	uint32_t n_lines = 0;
+	HIPCHK(hipMemcpyAsync(&n_lines, cnt + nt, 4, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	const int grid = bam_lines_grid(n_lines);
+	if ((rc = d->bam_start.reserve(((size_t)n_lines + 1) * 4)) != BSX_OK || (rc = d->bam_size.reserve(((size_t)n_lines + 1) * 4)) != BSX_OK ||
+	    (rc = d->bam_bad.reserve((size_t)grid * 8)) != BSX_OK || (rc = d->bam_err.reserve(((size_t)n_lines + 1) * 4)) != BSX_OK) return rc;
+	uint32_t *start = (uint32_t*)d->bam_start.p, *size = (uint32_t*)d->bam_size.p;
+	int *errs = (int*)d->bam_err.p;
+	launch_bam_starts(st, d->n_cu, d_text, (long long)len, cnt, start);
+	launch_bam_size(st, d_text, start, n_lines, (const char*)d->bam_names.p, (const uint32_t*)d->bam_noff.p, (const int32_t*)d->bam_nid.p, refs->n, size, errs,
+	                (unsigned long long*)d->bam_bad.p);
+	HIPCHK(hipGetLastError());
+	std::vector<unsigned long long> bad((size_t)grid);
+	HIPCHK(hipMemcpyAsync(bad.data(), d->bam_bad.p, (size_t)grid * 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	unsigned long long first = ~0ull;
+	for (unsigned long long b : bad) first = std::min(first, b);
+	const long long n_ok = first == ~0ull ? (long long)n_lines : (long long)(first >> 4);
+	if (first != ~0ull) { *bad_record = n_ok; *bad_why = (int)(first & 15); }
+	uint32_t total = 0;
+	if (n_ok > 0) {
+		launch_bam_scan(st, size, size, n_ok);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(&total, size + n_ok, 4, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+		if ((rc = d->bam_pay.reserve((size_t)total + 16)) != BSX_OK || (rc = bam_host_grow(out, out_cap, total)) != BSX_OK) return rc;
+		launch_bam_emit(st, d_text, start, n_ok, (const char*)d->bam_names.p, (const uint32_t*)d->bam_noff.p, (const int32_t*)d->bam_nid.p, refs->n, errs, size,
+		                (uint8_t*)d->bam_pay.p);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(*out, d->bam_pay.p, total, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+	}
+	*out_len = total; *n_records = n_ok;
+	return BSX_OK;
+}
+// payload -> members: every block deflated into its 64 KiB slot, the sizes summed on the device, the members moved behind each other, one copy down
+static int dev_bgzf_deflate(bsx_device_t *d, const uint8_t *payload, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len)
+{
+	if (!d) return BSX_E_NODEVICE;
+	if (!out || !out_cap || !out_len || (len && !payload)) return BSX_E_ARG;
+	*out_len = 0;
+	if (len == 0) return BSX_OK;
+	if (len >= ((size_t)1 << 31)) return BSX_E_ARG;
+	std::lock_guard<std::mutex> lock(d->bam_mu);
+	HIPCHK(hipSetDevice(d->ordinal));
+	int rc;
+	if ((rc = bam_stream(d)) != BSX_OK) return rc;
+	hipStream_t st = d->bam_st;
+	const long long nb = ((long long)len + BSX_BGZF_BLOCK - 1) / BSX_BGZF_BLOCK;
+	const int grid = bgzf_grid(nb);
+	if ((rc = d->bz_in.reserve(len + 16)) != BSX_OK || (rc = d->bz_tok.reserve(bgzf_tok_bytes(grid))) != BSX_OK || (rc = d->bz_cand.reserve(bgzf_cand_bytes(grid))) != BSX_OK ||
+	    (rc = d->bz_slots.reserve((size_t)nb * 65536)) != BSX_OK || (rc = d->bz_sizes.reserve(((size_t)nb + 1) * 4)) != BSX_OK || (rc = d->bz_ops.reserve(256 * 4)) != BSX_OK) return rc;
+	if (!d->bz_ops_ok) {
+		uint32_t ops[256];
+		bgzf_crc_ops(ops);
+		HIPCHK(hipMemcpyAsync(d->bz_ops.p, ops, sizeof(ops), hipMemcpyHostToDevice, st));
+		HIPCHK(hipStreamSynchronize(st));
+		d->bz_ops_ok = true;
+	}
+	uint32_t *sizes = (uint32_t*)d->bz_sizes.p, total = 0;
+	HIPCHK(hipMemcpyAsync(d->bz_in.p, payload, len, hipMemcpyHostToDevice, st));
+	for (long long b0 = 0; b0 < nb; b0 += grid) // (launches on one stream: the second one's workgroups find the workspaces free)
+		launch_bgzf_deflate(st, (const uint8_t*)d->bz_in.p, (long long)len, b0, (int)std::min<long long>(grid, nb - b0), (const uint32_t*)d->bz_ops.p, (uint32_t*)d->bz_tok.p,
+		                    (uint16_t*)d->bz_cand.p, (uint8_t*)d->bz_slots.p, sizes);
+	launch_bam_scan(st, sizes, sizes, nb);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(&total, sizes + nb, 4, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	if (total < 27 * (uint64_t)nb || (uint64_t)total > 65536ull * (uint64_t)nb) return BSX_E_INTERNAL;
+	if ((rc = d->bz_out.reserve(total)) != BSX_OK || (rc = bam_host_grow(out, out_cap, total)) != BSX_OK) return rc;
+	launch_bgzf_compact(st, d->n_cu, (const uint8_t*)d->bz_slots.p, sizes, nb, (uint8_t*)d->bz_out.p);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipMemcpyAsync(*out, d->bz_out.p, total, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	*out_len = total;
+	return BSX_OK;
+}
+
 // the seams as one vtable for the host pipeline; ctx = (device, lane)
 #define LR(c) ((LaneRef*)(c))->d, ((LaneRef*)(c))->lane
 static int be_set_opt(void *c, const bsx_opt_t *o) { return lane_set_opt(LR(c), o); }
@@ -2812,6 +2953,16 @@ static int be_sort(void *c, int op, int64_t n, const uint64_t *keys, uint32_t *p
 	return BSX_E_ARG;
 }
 
+static int be_bam_encode(void *c, const bsx_bam_refs_t *refs, const char *text, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len, int64_t *n_records,
+                         int64_t *bad_record, int *bad_why)
+{
+	return dev_bam_encode(((LaneRef*)c)->d, refs, text, len, out, out_cap, out_len, n_records, bad_record, bad_why);
+}
+static int be_bgzf_deflate(void *c, const uint8_t *payload, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len)
+{
+	return dev_bgzf_deflate(((LaneRef*)c)->d, payload, len, out, out_cap, out_len);
+}
+
 static LaneRef g_lane_ref[8][BSX_LANES];   // ctx storage for the vtables (by device ordinal)
 
 extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *out)
@@ -2824,6 +2975,7 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
 	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov; out->sort_batch = be_sort; out->meth_batch = be_meth; out->meth_sites = be_meth_sites;
+	out->bam_encode = be_bam_encode; out->bgzf_deflate = be_bgzf_deflate;
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

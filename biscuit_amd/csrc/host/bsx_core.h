@@ -213,6 +213,11 @@ typedef struct bsx_backend {
 	/* optional (may be NULL; a backend that clears the struct has it NULL), set together with meth_batch: the methylation sites of those counters
 	 * (bsx_meth_sites).  A backend without meth_batch has the counters on the host, and meth.c lists the sites there. */
 	int (*meth_sites)(void *ctx, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next);
+	/* optional (may be NULL; a backend that clears the struct has them NULL): the two stages of --bam, see bsx_bam_encode and bsx_bgzf_deflate.
+	 * Without one the host runs its own statement of that stage (bam.c: bam_rec.h's records, zlib's deflate). */
+	int (*bam_encode)(void *ctx, const bsx_bam_refs_t *refs, const char *text, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len,
+	                  int64_t *n_records, int64_t *bad_record, int *bad_why);
+	int (*bgzf_deflate)(void *ctx, const uint8_t *payload, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len);
 } bsx_backend_t;
 enum { BSX_METH_OP_BATCH = 0, BSX_METH_OP_TABLES = 1, BSX_METH_OP_RESET = 2 };
 enum { BSX_SORT_OP_RUN = 0, BSX_SORT_OP_SCHEDULE = 1, BSX_SORT_OP_RESET = 2 };

@@ -12,6 +12,7 @@
 #include "fastq.h"
 #include "pipeline.h"
 #include "sortout.h"
+#include "bam.h"
 #include <signal.h>
 #include <sys/time.h>
 
@@ -89,6 +90,10 @@ static int usage(void)
 		"              reverse; equal keys in the order of the unsorted output; @HD ... SO:coordinate first in the header.  The order is computed on the\n"
 		"              device, the records wait in one temporary file; one process only (refused with WORLD_SIZE > 1)\n"
 		"              --sort-tmp DIR  where that file is made (default: /tmp); it has no name while it exists\n"
+		"  bam       : --bam  BAM instead of SAM text: one record per line that would have been written (after --bsconv, --markdup and --sort), encoded\n"
+		"              and deflated on the device into BGZF blocks of 0xff00 payload bytes, the header in a block of its own, the EOF block last; a\n"
+		"              record BAM cannot hold (a read name beyond 254 bytes, an RNAME without an @SQ line in a header given with -H) ends the run\n"
+		"              with status 1; one process only (refused with WORLD_SIZE > 1)\n"
 		"  device    : $BSX_DEVICE selects the HIP device ordinal (default 0)\n\n");
 	return 1;
 }
@@ -256,6 +261,11 @@ static void emit_chunk(bsx_read_t *seqs, int n, int64_t chunk_idx, int ok);
 static volatile int g_write_error = 0;   /* a write to stdout failed (the reference aborts there: err_fputs, utils.c:214) */
 /* --sort: finished chunks go to the sorter instead of the output; what it holds leaves at the end of the call, behind the header */
 static bsx_sorter_t *g_sorter = 0;
+/* --bam: the text that would have been written goes through the writer (bam.c) instead; a refused record or a failed stage ends the run */
+static bsx_bam_writer_t *g_bam = 0;
+static volatile int g_bam_error = 0;
+static int64_t g_bam_piece = 0;
+static int bam_add(const char *text, size_t len);
 static volatile int g_sort_error = 0;   /* a chunk could not be sorted or kept: nothing is written */
 /* Several ranks over plain files: a scanner thread lists the chunk boundaries without building records (fastq.c) and this rank
  * parses only its own chunks r, r+N, ..., seeking to each.  Compressed or piped input: every rank inflates everything (threads of
@@ -326,32 +336,37 @@ static void *writer_main(void *arg)
 	return 0;
 }
 
-/* write out (or hand to the hook) the SAM text of a finished chunk and release its reads */
+/* the SAM text of a chunk's reads as one block (malloc'd; *len its length); NULL, with a message, when there is no memory for it */
+static char *chunk_text(const bsx_read_t *seqs, int n, size_t *len)
+{
+	size_t tot = 0, at = 0;
+	char *all;
+	int i;
+	for (i = 0; i < n; ++i) if (seqs[i].sam) tot += strlen(seqs[i].sam);
+	if ((all = (char*)malloc(tot + 1)) == 0) { fprintf(stderr, "[E::%s] no memory for the %zu bytes of a chunk's records\n", "main_align", tot); return 0; }
+	for (i = 0; i < n; ++i) if (seqs[i].sam) { const size_t l = strlen(seqs[i].sam); memcpy(all + at, seqs[i].sam, l); at += l; }
+	all[tot] = 0;
+	*len = tot;
+	return all;
+}
+/* write out (or hand to the sorter, the BAM writer or the hook) the SAM text of a finished chunk and release its reads */
 static void emit_chunk(bsx_read_t *seqs, int n, int64_t chunk_idx, int ok)
 {
 	int i;
-	if (g_sorter) {
-		if (ok && !g_sort_error) {
-			size_t tot = 0, at = 0; char *all;
-			for (i = 0; i < n; ++i) if (seqs[i].sam) tot += strlen(seqs[i].sam);
-			all = (char*)malloc(tot + 1);
-			for (i = 0; i < n; ++i) if (seqs[i].sam) { size_t l = strlen(seqs[i].sam); memcpy(all + at, seqs[i].sam, l); at += l; }
-			if ((i = bsx_sorter_add(g_sorter, all, tot)) != BSX_OK) { fprintf(stderr, "[E::%s] --sort: chunk %ld could not be sorted (%s)\n", "main_align", (long)chunk_idx, bsx_strerror(i)); g_sort_error = 1; }
-			free(all);
-		}
-		for (i = 0; i < n; ++i) bsx_read_free(&seqs[i]);
-		free(seqs);
-		return;
-	}
-	if (ok && bsx_emit_hook) {
-		size_t tot = 0, at = 0; char *all;
-		for (i = 0; i < n; ++i) if (seqs[i].sam) tot += strlen(seqs[i].sam);
-		all = (char*)malloc(tot + 1);
-		for (i = 0; i < n; ++i) if (seqs[i].sam) { size_t l = strlen(seqs[i].sam); memcpy(all + at, seqs[i].sam, l); at += l; }
-		bsx_emit_hook(bsx_emit_ud, chunk_idx, all, tot);
+	const int as_block = g_sorter ? !g_sort_error : g_bam ? !g_bam_error && !g_write_error : bsx_emit_hook != 0;
+	if (ok && as_block) {
+		size_t tot = 0;
+		char *all = chunk_text(seqs, n, &tot);
+		if (g_sorter) {
+			if (!all) g_sort_error = 1;
+			else if ((i = bsx_sorter_add(g_sorter, all, tot)) != BSX_OK) { fprintf(stderr, "[E::%s] --sort: chunk %ld could not be sorted (%s)\n", "main_align", (long)chunk_idx, bsx_strerror(i)); g_sort_error = 1; }
+		} else if (g_bam) {
+			if (!all) g_bam_error = 1; else (void)bam_add(all, tot);
+		} else if (!all) g_write_error = 1;
+		else bsx_emit_hook(bsx_emit_ud, chunk_idx, all, tot);
 		free(all);
 	}
-	for (i = 0; i < n; ++i) { if (ok && !bsx_emit_hook && !g_write_error && seqs[i].sam && fputs(seqs[i].sam, stdout) == EOF) g_write_error = 1; bsx_read_free(&seqs[i]); }
+	for (i = 0; i < n; ++i) { if (ok && !g_sorter && !g_bam && !bsx_emit_hook && !g_write_error && seqs[i].sam && fputs(seqs[i].sam, stdout) == EOF) g_write_error = 1; bsx_read_free(&seqs[i]); }
 	free(seqs);
 }
 
@@ -378,8 +393,41 @@ typedef struct { int64_t piece; } sort_sink_t;
 static int sort_sink(void *ud, const char *text, size_t len)
 {
 	sort_sink_t *k = (sort_sink_t*)ud;
+	if (g_bam) return bam_add(text, len);
 	if (bsx_emit_hook) { bsx_emit_hook(bsx_emit_ud, k->piece++, text, len); return 0; }
 	return fwrite(text, 1, len, stdout) == len ? 0 : 1;
+}
+/* --bam encodes the record stream of the whole output into blocks counted from its first record */
+#define BAM_RANKS_MSG "--bam cuts the records of the whole output into blocks through one writer on one device: it cannot run with WORLD_SIZE > 1"
+static int bam_sink(void *ud, const void *data, size_t len, int is_header)
+{
+	(void)ud;
+	if (bsx_emit_hook) { bsx_emit_hook(bsx_emit_ud, is_header ? -1 : g_bam_piece++, (const char*)data, len); return 0; }
+	return fwrite(data, 1, len, stdout) == len ? 0 : 1;
+}
+static int bam_add(const char *text, size_t len)
+{
+	const int rc = bsx_bam_writer_add(g_bam, text, len);
+	if (rc == BSX_OK) return 0;
+	if (!g_bam_error && !g_write_error) {
+		if (rc == BSX_E_FORMAT) {
+			int64_t rec = -1; int why = 0;
+			bsx_bam_writer_refused(g_bam, &rec, &why);
+			fprintf(stderr, "[E::%s] --bam: record %lld cannot be written as BAM: %s\n", "main_align", (long long)rec, bsx_bam_strerror(why));
+		} else if (rc == BSX_E_IO) g_write_error = 1;
+		else fprintf(stderr, "[E::%s] --bam: encoding failed (%s)\n", "main_align", bsx_strerror(rc));
+	}
+	g_bam_error = 1;
+	return 1;
+}
+static void hip_close(void *ud);
+static int bam_open(void *ud, const char *header)
+{
+	/* the product entry encodes and deflates on its device; another backend's records go through the host's statement of both stages */
+	const int rc = g_close_device == hip_close ? bsx_bam_writer_open((bsx_device_t*)ud, header, bam_sink, 0, &g_bam) : bsx_bam_writer_open_backend(0, header, bam_sink, 0, &g_bam);
+	g_bam_piece = 0;
+	if (rc != BSX_OK) { fprintf(stderr, "[E::%s] --bam: %s\n", "main_align", bsx_strerror(rc)); g_bam = 0; return 1; }
+	return 0;
 }
 static double now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.tv_sec + tv.tv_usec * 1e-6; }
 
@@ -467,6 +515,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		{"qc-cov", no_argument, 0, 1012}, {"qc-topgc", required_argument, 0, 1013}, {"qc-botgc", required_argument, 0, 1014},
 		{"sort", no_argument, 0, 1015}, {"sort-tmp", required_argument, 0, 1016}, {"qc-meth", no_argument, 0, 1017},
 		{"meth-bed", required_argument, 0, 1018}, {"meth-type", required_argument, 0, 1019}, {"meth-min-cov", required_argument, 0, 1020}, {"meth-merge", no_argument, 0, 1021},
+		{"bam", no_argument, 0, 1022},
 		{0, 0, 0, 0}
 	};
 	bsx_bsconv_conf_t bsconv;
@@ -474,7 +523,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	const char *meth_bed = 0, *meth_type = 0, *meth_min_cov = 0;
 	bsx_meth_site_opt_t meth_opt = {BSX_METH_TYPE_CG, 0, 1, 0};   /* vcf2bed.c:300: -k 1 */
 	const char *gc_bed[2] = {0, 0}, *sort_tmp = 0;
-	int sort_on = 0;
+	int sort_on = 0, bam_on = 0;
 	char *sort_hdr = 0;
 	double t_start = 0;
 	void (*old_xfsz)(int) = SIG_DFL;
@@ -499,6 +548,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		else if (c == 1019) meth_type = optarg;
 		else if (c == 1020) meth_min_cov = optarg;
 		else if (c == 1021) meth_opt.merge = 1;
+		else if (c == 1022) bam_on = 1;
 		else if (c >= 1000) { /* bsconv while aligning (main_bsconv, src/bsconv.c:224-242, has these as -m -a -c -t -x -f -y -u -v) */
 			bsconv_on = 1;
 			if (c == 1000) bsconv.annotate = 1;
@@ -678,6 +728,9 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 		fprintf(stderr, "[E::%s] --sort: no temporary file can be made in %s (%s)\n", "main_align", sort_tmp ? sort_tmp : "/tmp", strerror(errno));
 		return 1;
 	}
+	if (bam_on && bsx_shard_world > 1) { fprintf(stderr, "[E::%s] %s\n", "main_align", BAM_RANKS_MSG); return 1; }
+	if (bam_on && (opt->flag & BSX_F_ALN_REG)) { fprintf(stderr, "[E::%s] --bam encodes SAM records: it cannot be combined with -F\n", "main_align"); return 1; }
+	g_bam_error = 0;
 	bsx_process_set_markdup(markdup_on);
 	if (optind >= argc) { usage(); fprintf(stderr, "Missing fai-index base\n"); return 1; }
 	if ((rc = bsx_index_load(argv[optind], &idx)) != BSX_OK) { fprintf(stderr, "[E::%s] fail to locate the index files (%s)\n", "main_align", bsx_strerror(rc)); return 1; }
@@ -709,7 +762,8 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 	} else
 	if (!(opt->flag & BSX_F_ALN_REG) && bsx_shard_rank == 0) {
 		char *h = bsx_sam_header(idx, hdr_line, bsx_pg_line);
-		if (bsx_emit_hook) bsx_emit_hook(bsx_emit_ud, -1, h, strlen(h)); else if (fputs(h, stdout) == EOF) g_write_error = 1;
+		if (bam_on) { if (bam_open(ud, h)) { free(h); rc = 1; goto cleanup; } }
+		else if (bsx_emit_hook) bsx_emit_hook(bsx_emit_ud, -1, h, strlen(h)); else if (fputs(h, stdout) == EOF) g_write_error = 1;
 		free(h);
 	}
 	{
@@ -765,7 +819,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 				n_processed += r.n;
 				}
 				if (rc != BSX_OK) { fprintf(stderr, "[E::%s] alignment failed: %s\n", "main_align", bsx_strerror(rc)); rc = 1; R.stop = 1; break; }
-				if (g_write_error) { rc = 1; R.stop = 1; break; }
+				if (g_write_error || g_bam_error) { rc = 1; R.stop = 1; break; }
 				while (n_pend > depth - 1) { /* the push completed the oldest chunk in flight */
 					chunk_rec_t d; d.seqs = pend[0].seqs; d.n = pend[0].n; d.idx = pend[0].idx; d.ok = 1; d.n_before = -1;
 					cq_put(&out_q, d);
@@ -846,7 +900,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 				if (rc != BSX_OK) { fprintf(stderr, "[E::%s] alignment failed: %s\n", "main_align", bsx_strerror(rc)); rc = 1; }
 				n_processed += n_all;
 				emit_chunk(seqs, m, chunk_idx * bsx_shard_world + bsx_shard_rank, rc == 0);
-				if (g_write_error) rc = 1;
+				if (g_write_error || g_bam_error) rc = 1;
 				if (rc) break;
 				continue;
 			}
@@ -867,7 +921,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 					emit_chunk(pend[0].seqs, pend[0].n, pend[0].idx, 1);
 					for (i = 1; i < n_pend; ++i) pend[i - 1] = pend[i];
 					--n_pend;
-					if (g_write_error) rc = 1;
+					if (g_write_error || g_bam_error) rc = 1;
 				}
 				if (rc) break;
 				continue;
@@ -875,7 +929,7 @@ BSX_API int bsx_align_main_with(int argc, char **argv, process_fn process, void 
 			if (rc != BSX_OK) { fprintf(stderr, "[E::%s] alignment failed: %s\n", "main_align", bsx_strerror(rc)); rc = 1; }
 			n_processed += n;
 			emit_chunk(seqs, n, chunk_idx, rc == 0);
-			if (g_write_error) rc = 1;
+			if (g_write_error || g_bam_error) rc = 1;
 			if (rc) break;
 		}
 		if (stream) {
@@ -894,9 +948,12 @@ loop_done:
 		if (rc == 0) {
 			sort_sink_t k = {0};
 			int src;
-			if (bsx_emit_hook) bsx_emit_hook(bsx_emit_ud, -1, sort_hdr, strlen(sort_hdr)); else if (fputs(sort_hdr, stdout) == EOF) g_write_error = 1;
-			if (!g_write_error && (src = bsx_sorter_finish(g_sorter, sort_sink, &k)) != BSX_OK) {
-				if (src == BSX_E_IO && ferror(stdout)) g_write_error = 1;
+			if (bam_on) { if (bam_open(ud, sort_hdr)) g_bam_error = 1; }
+			else if (bsx_emit_hook) bsx_emit_hook(bsx_emit_ud, -1, sort_hdr, strlen(sort_hdr)); else if (fputs(sort_hdr, stdout) == EOF) g_write_error = 1;
+			if (g_bam_error) rc = 1;
+			else if (!g_write_error && (src = bsx_sorter_finish(g_sorter, sort_sink, &k)) != BSX_OK) {
+				if (g_bam_error || g_write_error) ;   /* (bam_add has said why) */
+				else if (src == BSX_E_IO && ferror(stdout)) g_write_error = 1;
 				else fprintf(stderr, "[E::%s] --sort: merging the sorted chunks failed (%s): the SAM is incomplete\n", "main_align", bsx_strerror(src));
 				rc = 1;
 			}
@@ -905,6 +962,18 @@ loop_done:
 			uint64_t nr = 0, nrec = 0;
 			bsx_sorter_counts(g_sorter, &nr, &nrec);
 			fprintf(stderr, "[M::%s] sort: %llu runs, %llu records (aligned in %.2f s, merged in %.2f s)\n", "main_align", (unsigned long long)nr, (unsigned long long)nrec, t_aligned - t_start, now_s() - t_aligned);
+		}
+	}
+	if (g_bam) { /* the tail of the record stream and the EOF block -- after an error nothing more */
+		if (g_bam_error) rc = 1;
+		if (rc == 0 && !g_write_error) {
+			uint64_t nrec = 0, npay = 0, nw = 0;
+			bsx_bam_writer_t *w = g_bam;
+			int brc;
+			bsx_bam_writer_counts(w, &nrec, &npay, &nw);
+			g_bam = 0;
+			if ((brc = bsx_bam_writer_close(w, 1)) != BSX_OK) { if (brc == BSX_E_IO) g_write_error = 1; else fprintf(stderr, "[E::%s] --bam: %s\n", "main_align", bsx_strerror(brc)); rc = 1; }
+			else if (bsx_verbose >= 3) fprintf(stderr, "[M::%s] bam: %llu records, %llu payload bytes behind the header\n", "main_align", (unsigned long long)nrec, (unsigned long long)npay);
 		}
 	}
 	if (fflush(stdout) != 0 || ferror(stdout)) g_write_error = 1;
@@ -922,6 +991,7 @@ loop_done:
 		        (unsigned long long)t.n_keyed, (unsigned long long)t.n_dup);
 	}
 cleanup:
+	if (g_bam) { (void)bsx_bam_writer_close(g_bam, 0); g_bam = 0; }   /* (before the device it encodes on is closed) */
 	if (g_sorter) { bsx_sorter_close(g_sorter); g_sorter = 0; signal(SIGXFSZ, old_xfsz); }   /* (before the device it sorts on is closed) */
 	free(sort_hdr);
 	if (markdup_on) bsx_process_set_markdup(0);
@@ -1002,6 +1072,7 @@ BSX_API int bsx_align_main_ranks_with(int argc, char **argv, bsx_process_fn proc
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 4 && strncmp("--markdup", argv[k], strlen(argv[k])) == 0) { /* (any abbreviation getopt_long takes: --m is also the start of --meth-bed) */ fprintf(stderr, "[E::%s] %s\n", "main_align", MARKDUP_RANKS_MSG); return 1; } }   /* (before any transport is opened) */
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 6 && strncmp("--qc-cov", argv[k], strlen(argv[k])) == 0) { /* (--qc-c, --qc-co: what getopt_long takes for it) */ fprintf(stderr, "[E::%s] %s\n", "main_align", QC_COV_RANKS_MSG); return 1; } }
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strlen(argv[k]) >= 6 && strncmp("--qc-meth", argv[k], strlen(argv[k])) == 0) { /* (--qc-m .. --qc-met: what getopt_long takes for it) */ fprintf(stderr, "[E::%s] %s\n", "main_align", QC_METH_RANKS_MSG); return 1; } }
+	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strcmp(argv[k], "--ba") == 0 || strcmp(argv[k], "--bam") == 0) { /* (what getopt_long takes for it: --b is also the start of --bsconv) */ fprintf(stderr, "[E::%s] %s\n", "main_align", BAM_RANKS_MSG); return 1; } }
 	{ int k; for (k = 1; k < argc; ++k) if (strcmp(argv[k], "--") == 0) break; else if (strncmp(argv[k], "--s", 3) == 0) { /* (--sort, --sort-tmp and every abbreviation: no other long option begins with --s) */ fprintf(stderr, "[E::%s] %s\n", "main_align", SORT_RANKS_MSG); return 1; } }
 	memset(&R, 0, sizeof(R));
 	if (id_env && *id_env) snprintf(id_path, sizeof(id_path), "%s", id_env);

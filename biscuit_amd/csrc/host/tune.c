@@ -58,6 +58,7 @@ static knob_t g_knobs[] = {
 	{"meth_flush_tiles", "[1024] tests: tiles after which a wave of the base-averaged conversion table's pass (--qc-meth) adds its sums to the 64-bit cells (32-bit registers: at most 1024)", 0},
 	{"cov_flush_tiles", "[524287] tests: tiles after which a workgroup of that pass adds its LDS histograms to the bins (32-bit cells: at most 2^32 / 4096 - 1)", 0},
 	{"sort_buf_bytes", "[1 GB / runs, at most 8 MB] bytes of the buffer every sorted run of --sort is read back through in the final merge (tests: 1, a record is then many fills)", 0},
+	{"bam_piece_bytes", "[32 MB] bytes of SAM text (whole lines; a longer line alone) the writer of --bam encodes and deflates at a time: the file does not depend on it (tests: small pieces, so that records and block_size fields straddle pieces and blocks)", 0},
 	{"markdup_hash_bits", "[64] tests: low bits kept of a template key's claim word (different keys then meet in one slot and take the next salt)", 0},
 };
 #define N_KNOBS ((int)(sizeof(g_knobs) / sizeof(g_knobs[0])))

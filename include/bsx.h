@@ -524,6 +524,50 @@ void bsx_sorter_counts(const bsx_sorter_t *s, uint64_t *n_runs, uint64_t *n_reco
 void bsx_sorter_close(bsx_sorter_t *s);
 char *bsx_sort_header(const char *header);
 
+/* BAM output (--bam; k_bam.hip, k_bgzf.hip, csrc/host/bam.c).  DESIGN.md section 7 has the rule, tests/bam_model.py is its reference statement.
+ * Two batch seams, each a pure function of its input:
+ *   bsx_bam_encode    SAM text (whole lines, each ending in '\n') -> the uncompressed BAM records, one per line, in order.  refs: the name table
+ *                     of the header the records belong to (bsx_bam_refs_open: one reference per @SQ line of the text, from SN and LN; RNAME is
+ *                     the index of the first line with that name).  A line BAM or this encoder cannot hold stops the call: *bad_record = its
+ *                     0-based index in the text, *bad_why = BSX_BAM_E_*, the records before it are returned, the return value is BSX_OK
+ *                     (*bad_record = -1 when every line was taken).  *n_records: the records returned.
+ *   bsx_bgzf_deflate  payload -> BGZF blocks behind each other, one per BSX_BGZF_BLOCK payload bytes (the last one shorter): the gzip member
+ *                     header with the BC field, a deflate stream (LZ77 + dynamic Huffman codes on the device; one stored block where that is
+ *                     no smaller: n + 31 bytes), CRC32, ISIZE.  The same payload gives the same bytes on every call.  len 0 gives nothing.  The
+ *                     compressed bytes are the coder's own: the device's and the host's (zlib level 1) differ, both inflate to the payload.
+ * Both write into a caller-owned growable buffer (*out / *out_cap, realloc'd by the call) from its start and set *out_len.  dev == NULL: the
+ * host's own statement of the stage (what a backend without the seam runs).
+ * The writer: bsx_bam_writer_open takes the header text as written, _add whole lines, _close(finish != 0) the last partial block and the 28-byte
+ * EOF block.  The header part ends its block; the record stream is cut every BSX_BGZF_BLOCK bytes counted from the first record across calls
+ * (the writer carries the tail), so the file is a function of the header and the record sequence alone.  It works in pieces of at most
+ * "bam_piece_bytes" (bsx_tune_set) of text, whole lines.  The sink gets the header's block (is_header = 1) with the first data it is called
+ * with -- a run whose first piece is refused has written nothing -- and then runs of whole blocks; a non-zero return from it is BSX_E_IO from
+ * the call and from every later one.  A refused line: BSX_E_FORMAT, nothing of its piece or after it reaches the sink, bsx_bam_writer_refused
+ * says which record of the whole stream (0-based) and why. */
+#define BSX_BGZF_BLOCK   0xff00
+#define BSX_BAM_E_LINE   1   /* not a SAM record: fewer than 11 columns, an empty column, a number that is none or out of its field's range */
+#define BSX_BAM_E_TAG    2   /* a field after column 11 that is not XX:T:value with T in A i Z f (H and B included) */
+#define BSX_BAM_E_INT    3   /* an i value outside -2^31 .. 2^32 - 1 */
+#define BSX_BAM_E_NAME   4   /* a read name longer than 254 bytes */
+#define BSX_BAM_E_CIGAR  5   /* more than 65535 CIGAR operations */
+#define BSX_BAM_E_REF    6   /* an RNAME or RNEXT without an @SQ line */
+#define BSX_BAM_E_QUAL   7   /* SEQ and QUAL of different lengths */
+typedef struct bsx_bam_refs bsx_bam_refs_t;
+typedef struct bsx_bam_writer bsx_bam_writer_t;
+typedef int (*bsx_bam_sink_fn)(void *ud, const void *data, size_t len, int is_header);
+int  bsx_bam_refs_open(const char *header_text, bsx_bam_refs_t **out);
+void bsx_bam_refs_close(bsx_bam_refs_t *refs);
+int  bsx_bam_header(const char *header_text, uint8_t **out, size_t *out_len);   /* the header part of the payload, malloc'd */
+const char *bsx_bam_strerror(int why);
+int  bsx_bam_encode(bsx_device_t *dev, const bsx_bam_refs_t *refs, const char *text, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len,
+                    int64_t *n_records, int64_t *bad_record, int *bad_why);
+int  bsx_bgzf_deflate(bsx_device_t *dev, const uint8_t *payload, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len);
+int  bsx_bam_writer_open(bsx_device_t *dev, const char *header_text, bsx_bam_sink_fn sink, void *ud, bsx_bam_writer_t **out);
+int  bsx_bam_writer_add(bsx_bam_writer_t *w, const char *text, size_t len);
+int  bsx_bam_writer_close(bsx_bam_writer_t *w, int finish);   /* frees the writer; finish = 0 after an error: nothing more is written */
+void bsx_bam_writer_refused(const bsx_bam_writer_t *w, int64_t *record, int *why);
+void bsx_bam_writer_counts(const bsx_bam_writer_t *w, uint64_t *n_records, uint64_t *payload_bytes, uint64_t *bytes_written);
+
 /* Settings of the library that never change its output (launch shapes, table sizes, which of two equivalent paths runs: what the tests and
  * the A/B tools switch).  One registry (csrc/host/tune.c has the table of names): bsx_tune_set(name, value) between calls of the library
  * (value NULL: back to the default; BSX_E_ARG for an unknown name), or "$BSX_TUNE=name=value,name=value" for a whole process.  bsx_phases():
