@@ -2,121 +2,14 @@
 // Owns: device selection, the HBM-resident index (both converted FM indices + SA samples + pac),
 // per-chunk read buffer, job/result staging, kernel timing (HIP events on the launch stream) and
 // the work counters behind the algorithmic-bytes model.  No CPU fallback: every entry point
-// returns BSX_E_NODEVICE when HIP is unusable.
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
+// returns BSX_E_NODEVICE when HIP is unusable.  The output passes that run while aligning are a unit of their own, shim_tables.hip; what the
+// two share (Lane, bsx_device, the error macros, xfer) is in shim_dev.hpp.
 #include <time.h>
-#include <algorithm>
-#include <vector>
-#include <mutex>
 #include <atomic>
-#include "devbuf.hpp"
-#include "kernels.h"
+#include "shim_dev.hpp"
 #include "index_build.h"
-#include "tune.h"
 #include "ext_pk_bound.h"
 #include "rgx.hpp"
-
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "[bsx-hip] %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_), __FILE__, __LINE__); return BSX_E_NODEVICE; } } while (0)
-
-// One lane = one HIP stream with its own staging: a chunk is bound to a lane for its whole life, so the front half
-// (seeding .. regions) of one chunk and the back half (merge .. SAM) of the previous one can be in flight together.
-#define BSX_LANES 6
-// the slots of bsx_device_kernel_time: the chunk-wide seeding pass, the suffix-array lookups, the DP batches (extensions, local alignments,
-// global alignments), tier 1, the later tiers, seeding outside the chunk-wide launch (the batch form, the merged second pass)
-enum KTime { KT_SEED = 0, KT_K3 = 1, KT_EXTEND = 2, KT_SW = 3, KT_GLOBAL = 4, KT_TIER1 = 5, KT_TIERS_LATER = 6, KT_SEED_OTHER = 7, KT_N = 8 };
-struct Lane {
-	hipStream_t st = nullptr;      // front-half kernels (low priority)
-	hipEvent_t ev_seed_done = nullptr, ev_regions_done = nullptr;   // what the next chunk's launches of the same stage wait for
-	hipStream_t st_hi = nullptr;   // back-half kernels (K5, K6): high priority, so that they get compute units while another chunk's front half runs
-	hipEvent_t ev_timed_begin = nullptr, ev_timed_end = nullptr;   // around the launch finish_timed times; in a regions batch: around the chunk-wide seeding pass
-	hipEvent_t ev_seed2_begin = nullptr, ev_seed2_end = nullptr;   // regions batch: around the second seeding pass inside the main sequence (recorded back to back when there is none)
-	hipEvent_t ev_occ_end = nullptr, ev_tier1_end = nullptr, ev_tiers_end = nullptr;   // ... behind the suffix-array lookups, behind tier 1, behind everything of the main sequence
-	hipEvent_t tier_ev[12] = {};   // $BSX_PHASES: between the region launches
-	hipStream_t st_cp = nullptr;   // unmasked: the front half's small copies (xfer)
-	hipEvent_t ev_cp = nullptr;
-	hipStream_t st3 = nullptr;     // the last HBM tier of what is known to need it when the occurrences are counted: beside the chunk's other tiers
-	hipEvent_t ev_t3a = nullptr, ev_t3b = nullptr;
-	hipStream_t st2 = nullptr;     // side stream of the front half: seeding redone with larger lists while the region kernels run
-	DevScoring sc;         // set by set_opt on this lane; read by every launch of this lane
-	DevBuf reads; size_t n_reads = 0;
-	DevBuf gath;             // lists gathered for the download of strand searches the caller takes back
-	DevBuf qpack;            // the chunk's reads as base-3 digits for the seeding kernel (k_seedt.hip)
-	int64_t rb_tasks = 0;    // strand searches of the last regions batch (their regions, offsets and counts are still in regs / regmeta)
-	int flt_key[3] = {-1, -1, -1};   // what fltab was made for
-	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, gctx, qcjobs, qcpool, mdkeys, mdres, mdslot, dd, sswjobs, c2rslab;
-	DevBuf small;          // the counter block: SMALL_BYTES laid out by ctr_layout.hpp
-	HostBuf hstage;        // pinned staging for bulk results
-	HostBuf pin;           // two pinned halves through which large host<->device copies are streamed
-	hipEvent_t pev[2] = {nullptr, nullptr};
-	// strand searches being seeded again on the side stream while the caller goes on (lane_regions_finish collects them)
-	struct {
-		bool active = false;
-		std::vector<int64_t> tasks;            // their indices in the chunk
-		std::vector<bsx_seed_task_t> sub;      // kept alive for the asynchronous upload
-		unsigned int n2u = 0;
-		HostBuf hres;                          // pinned: region offsets (8 B each) then counts (4 B each)
-		hipEvent_t ev = nullptr, ev_tiers = nullptr;
-		unsigned long long used_main = 0;      // regions the caller already holds
-		unsigned long long regs_cap = 0;       // size of the device's region pool for this chunk
-	} rs;
-	double k_ms[KT_N] = {0, 0, 0, 0, 0, 0, 0, 0};   // by KTime
-	int64_t k_launch[KT_N] = {0, 0, 0, 0, 0, 0, 0, 0};
-	uint64_t work[5] = {0, 0, 0, 0, 0};   // the region kernels' work since the last reset: strand searches, SA intervals, occurrences, regions, read bases
-	// what the last de-duplication of this lane left in `dd` (k_msw.hip reads the reads' lists from there): layout and validity
-	struct { bool valid = false; int64_t n_reads = 0; int per_read = 0; size_t o_idx = 0, o_off = 0, o_pool = 0; bool with_long = false; } ddl;
-	DevBuf msw_jobs, msw_res, msw_meta, msw_roff; int64_t msw_token = -1;
-	std::mutex hi_mu;      // the back half's batches (K5, K6) of this lane, one at a time: the slices of a chunk's back half call them from two threads
-	long last_overflow = -1;   // strand searches the first seeding pass of this lane's last chunk left to the second (-1: no chunk yet)
-	double seed2_ms = 0; int64_t seed2_launches = 0; uint64_t seed2_tasks = 0;   // the second seeding pass inside the chunk's sequence (its own launch, its own counters: CTR_SEED2)
-};
-// The seeding launches of a chunk count their FM blocks and table entries in blocks of their own, so that each pass's bytes can be put over
-// that pass's time (bsx_device_seed_passes): CTR_FM_SLOW, CTR_FM_FAST, CTR_TAB_LOOKUPS of the lane's counter block (ctr_layout.hpp) for the chunk-wide
-// first pass (and the batch form), the same three from CTR_SEED2 for the second pass inside the sequence, from CTR_SEED3 for the few seeded again
-// on the side stream.
-
-struct bsx_device {
-	int ordinal = 0;
-	char name[256];
-	int n_cu = 0;
-	DevIndex ix; bool has_index = false;
-	DevBuf bwt[2], sa[2], pac, ctg, holes, seedtab[2];
-	DevBuf qc;   // bsx_qc_counts_t: the BISCUITqc column counts of every lane's batches (k_qc.hip), zeroed when made and by bsx_qc_read(reset)
-	std::mutex qc_mu;
-	// the depth state of the coverage tables (k_cov.hip): the difference array (made and zeroed on first use) and the two optional masks, kept
-	// until bsx_cov_reset / close
-	void *cov_diff = nullptr; uint32_t *cov_mask[2] = {nullptr, nullptr};
-	std::mutex cov_mu;
-	// the counters of the base-averaged conversion table (k_meth.hip): two 64-bit words per position, made and zeroed on first use, kept until
-	// bsx_meth_reset / close
-	void *meth_st = nullptr;
-	std::mutex meth_mu;
-	// the table of template keys (k_markdup.hip): made by the first bsx_markdup_batch, doubled as it fills, kept until bsx_markdup_reset / close
-	MdSlot *md = nullptr; uint64_t md_slots = 0, md_used = 0;
-	std::mutex md_mu;
-	// the sorted runs of record keys (k_sort.hip): one block per bsx_sort_run, kept until bsx_sort_reset / close; the sort's own stream (the writer
-	// thread sorts a finished chunk while the lanes align the next ones) and its working buffers
-	std::vector<std::pair<uint64_t*, int64_t>> sort_runs;
-	hipStream_t sort_st = nullptr;
-	DevBuf sort_k[2], sort_p[2], sort_counts, sort_btot;
-	std::mutex sort_mu;
-	// --bam (k_bam.hip, k_bgzf.hip): the writer's stream (the writer thread encodes a finished chunk while the lanes align the next ones), the
-	// name table of the writer's header (uploaded once: bam_tab_serial says whose it is) and the working buffers of both stages
-	hipStream_t bam_st = nullptr;
-	uint64_t bam_tab_serial = 0;
-	DevBuf bam_names, bam_noff, bam_nid, bam_text, bam_cnt, bam_start, bam_size, bam_bad, bam_pay, bam_err;
-	DevBuf bz_in, bz_tok, bz_cand, bz_slots, bz_sizes, bz_out, bz_ops; bool bz_ops_ok = false;
-	std::mutex bam_mu;
-	Lane lane[BSX_LANES];   // scoring matrices and penalties are per lane (Lane::sc): chunks with different options may be in flight together
-	// Front halves of consecutive chunks are chained stage by stage (the seeding launch of chunk k+1 waits for that of chunk k, the
-	// region launches likewise): four chunks that share the device evenly all finish at the same moment, and the device then idles
-	// through the first of their back halves; chained, they are one stage apart and a chunk's seeding overlaps its predecessor's regions
-	std::mutex chain_mu;
-	hipEvent_t chain_seed = nullptr, chain_regions = nullptr;
-};
-struct LaneRef { bsx_device *d; int lane; };   // what the backend vtable carries as ctx
 
 #include <sys/time.h>
 static double bsx_now_s(void) { struct timeval tv; gettimeofday(&tv, 0); return tv.tv_sec + tv.tv_usec * 1e-6; }
@@ -197,45 +90,17 @@ extern "C" BSX_API int bsx_device_open(int ordinal, bsx_device_t **out)
 	return BSX_OK;
 }
 
-static void cov_release(bsx_device *d)
-{
-	if (d->cov_diff) { (void)hipFree(d->cov_diff); d->cov_diff = nullptr; }
-	for (int w = 0; w < 2; ++w) if (d->cov_mask[w]) { (void)hipFree(d->cov_mask[w]); d->cov_mask[w] = nullptr; }
-}
-
-static void sort_release(bsx_device *d)
-{
-	for (auto &r : d->sort_runs) (void)hipFree(r.first);
-	d->sort_runs.clear();
-	for (int i = 0; i < 2; ++i) { d->sort_k[i].release(); d->sort_p[i].release(); }
-	d->sort_counts.release(); d->sort_btot.release();
-	if (d->sort_st) { (void)hipStreamDestroy(d->sort_st); d->sort_st = nullptr; }
-}
-static void bam_release(bsx_device *d)
-{
-	DevBuf *b[] = {&d->bam_names, &d->bam_noff, &d->bam_nid, &d->bam_text, &d->bam_cnt, &d->bam_start, &d->bam_size, &d->bam_bad, &d->bam_pay, &d->bam_err,
-	               &d->bz_in, &d->bz_tok, &d->bz_cand, &d->bz_slots, &d->bz_sizes, &d->bz_out, &d->bz_ops};
-	for (DevBuf *x : b) x->release();
-	d->bam_tab_serial = 0; d->bz_ops_ok = false;
-	if (d->bam_st) { (void)hipStreamDestroy(d->bam_st); d->bam_st = nullptr; }
-}
-
 extern "C" BSX_API void bsx_device_close(bsx_device_t *d)
 {
 	if (!d) return;
 	(void)hipSetDevice(d->ordinal);
 	devbuf_drain(d->ordinal);   // the blocks this device's buffers left behind when they grew
 	for (int i = 0; i < 2; ++i) { d->bwt[i].release(); d->sa[i].release(); d->seedtab[i].release(); }
-	d->pac.release(); d->ctg.release(); d->holes.release(); d->qc.release();
-	if (d->md) { (void)hipFree(d->md); d->md = nullptr; d->md_slots = d->md_used = 0; }
-	cov_release(d);
-	if (d->meth_st) { (void)hipFree(d->meth_st); d->meth_st = nullptr; }
-	sort_release(d);
-	bam_release(d);
+	d->pac.release(); d->ctg.release(); d->holes.release();
+	d->qc.release(); d->cov.release(); d->meth.release(); d->md.release(); d->sort.release(); d->bam.release();
 	for (int l = 0; l < BSX_LANES; ++l) {
 		Lane &L = d->lane[l];
-		L.reads.release(); L.qpack.release(); L.gath.release(); L.jobs.release(); L.res.release(); L.scratch.release(); L.scratch2.release(); L.out.release(); L.aux.release(); L.pool.release();
-		L.small.release(); L.hstage.release(); L.regs.release(); L.regmeta.release(); L.slabs.release(); L.slabflags.release(); L.slabs3.release(); L.redo.release(); L.pin.release(); L.pos.release(); L.posoff.release(); L.xpool.release(); L.xmeta.release(); L.x4jobs.release(); L.fltab.release(); L.flt_key[0] = -1; L.tags.release(); L.mdpool.release(); L.gctx.release(); L.qcjobs.release(); L.qcpool.release(); L.mdkeys.release(); L.mdres.release(); L.mdslot.release(); L.dd.release(); L.c2rslab.release(); L.sswjobs.release(); L.msw_jobs.release(); L.msw_res.release(); L.msw_meta.release(); L.msw_roff.release();
+		L.release_buffers();
 		if (L.pev[0]) (void)hipEventDestroy(L.pev[0]);
 		if (L.pev[1]) (void)hipEventDestroy(L.pev[1]);
 		if (L.ev_seed_done) (void)hipEventDestroy(L.ev_seed_done);
@@ -476,7 +341,7 @@ static void copy_by_kernel(hipStream_t st, void *dst, const void *src, size_t n)
 	const unsigned int blocks = (unsigned int)std::min<size_t>(std::max<size_t>(1, (n / 16 + 255) / 256), 2048);
 	hipLaunchKernelGGL(k_copy_bytes, dim3(blocks), dim3(256), 0, st, (const unsigned char*)src, (unsigned char*)dst, n);
 }
-static int xfer(Lane &L, hipStream_t st, void *dst, const void *src, size_t n, bool h2d)
+int xfer(Lane &L, hipStream_t st, void *dst, const void *src, size_t n, bool h2d)
 {
 	if (n == 0) return BSX_OK;
 	const bool zc = st == L.st_hi;   // the back half's small batches move with a kernel on their own stream, not through the copy engines (round 4)
@@ -518,8 +383,6 @@ static int xfer(Lane &L, hipStream_t st, void *dst, const void *src, size_t n, b
 	if (!h2d) memcpy((char*)dst + prev_off, pin + (size_t)((i - 1) & 1) * XFER_CHUNK, prev_m);
 	return BSX_OK;
 }
-#define H2D(st, dst, src, n) do { int rc_ = xfer(L, st, dst, src, n, true); if (rc_ != BSX_OK) return rc_; } while (0)
-#define D2H(st, dst, src, n) do { int rc_ = xfer(L, st, dst, src, n, false); if (rc_ != BSX_OK) return rc_; } while (0)
 
 static int lane_set_reads(bsx_device_t *d, int lane, const uint8_t *buf, size_t n)
 {
@@ -877,8 +740,6 @@ static int lane_seed_batch(bsx_device_t *d, int lane, const bsx_opt_t *opt, int6
 // ------------------------------------------------------------------------------------------
 // K1+K2 -> K3 + chaining + chain filter + chain-to-region on the device; the interval lists never leave HBM
 // ------------------------------------------------------------------------------------------
-#define TRY(x) do { int rc_ = (x); if (rc_ != BSX_OK) return rc_; } while (0)
-
 // arrays carved out of a device buffer one behind the other: take<T>(count) aligns for T
 struct Bump {
 	char *p, *end;
@@ -2184,703 +2045,8 @@ extern "C" BSX_API int bsx_global_batch_tags_ctx(bsx_device_t *d, int64_t n, con
                                                  bsx_glb_tag_t *tags, char **md, int64_t *md_cap, bsx_glb_ctx_t *ctx)
 { if (!tags || !md || !md_cap || !ctx) return BSX_E_ARG; return lane_global_batch(d, 0, n, jobs, res, cigar_pool, cigar_pool_len, tags, md, md_cap, ctx); }
 
-// ------------------------------------------------------------------------------------------
-// BISCUITqc column counts (k_qc.hip)
-// ------------------------------------------------------------------------------------------
-static int qc_table(bsx_device_t *d)   // the device's table, made on first use
-{
-	std::lock_guard<std::mutex> lock(d->qc_mu);
-	if (d->qc.p) return BSX_OK;
-	int rc;
-	if ((rc = d->qc.reserve(sizeof(bsx_qc_counts_t))) != BSX_OK) return rc;
-	HIPCHK(hipMemset(d->qc.p, 0, sizeof(bsx_qc_counts_t)));
-	return BSX_OK;
-}
-static int cov_state_locked(bsx_device_t *d);
-// with_cov: the same upload also feeds k_cov_add (the jobs with BSX_QC_COV into the depth state of the coverage tables, below)
-static int lane_qc_batch(bsx_device_t *d, int lane, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len, bool with_cov = false)
-{
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	if (n == 0) return BSX_OK;
-	if (n < 0 || !jobs || (!cigar_pool && cigar_pool_len)) return BSX_E_ARG;
-	Lane &L = d->lane[lane];
-	for (int64_t i = 0; i < n; ++i) { // what the kernel indexes with must lie inside what it is given (read bases are checked one by one there)
-		const bsx_qc_job_t &j = jobs[i];
-		if ((size_t)j.cig_off + j.n_cigar > cigar_pool_len || j.rlen > (1u << 30) || j.fpos < 0 || j.fpos >= d->ix.l_pac) {
-			fprintf(stderr, "[bsx-hip] qc job %lld: invalid\n", (long long)i); return BSX_E_ARG;
-		}
-		uint64_t span = 0, rspan = 0;
-		for (uint32_t k = 0; k < j.n_cigar; ++k) { const uint32_t c = cigar_pool[j.cig_off + k], op = c & 0xf; if (op > 4) return BSX_E_ARG; span += c >> 4; if (op == 0 || op == 2) rspan += c >> 4; }
-		if (span > (1u << 30)) return BSX_E_ARG;
-		if (with_cov && (uint64_t)j.fpos + rspan > (uint64_t)d->ix.l_pac) { fprintf(stderr, "[bsx-hip] cov job %lld: beyond the reference\n", (long long)i); return BSX_E_ARG; }
-	}
-	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	int rc;
-	if ((rc = qc_table(d)) != BSX_OK) return rc;
-	if ((rc = L.qcjobs.reserve((size_t)n * sizeof(bsx_qc_job_t))) != BSX_OK) return rc;
-	if ((rc = L.qcpool.reserve(cigar_pool_len * 4 + 64)) != BSX_OK) return rc;
-	H2D(L.st_hi, L.qcjobs.p, jobs, (size_t)n * sizeof(bsx_qc_job_t));
-	H2D(L.st_hi, L.qcpool.p, cigar_pool, cigar_pool_len * 4);
-	launch_qc(L.st_hi, d->ix, (const uint8_t*)L.reads.p, (long long)L.n_reads, (const bsx_qc_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p,
-	          (unsigned long long*)d->qc.p, d->n_cu);
-	HIPCHK(hipGetLastError());
-	if (with_cov) { // (the depth state stays where it is until the launch is done: bsx_cov_reset takes the same lock)
-		std::lock_guard<std::mutex> lock(d->cov_mu);
-		if ((rc = cov_state_locked(d)) != BSX_OK) { (void)hipStreamSynchronize(L.st_hi); return rc; }
-		launch_cov_add(L.st_hi, d->n_cu, d->cov_diff, d->ix.l_pac, (const bsx_qc_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p, (long long)cigar_pool_len);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipStreamSynchronize(L.st_hi));
-		return BSX_OK;
-	}
-	HIPCHK(hipStreamSynchronize(L.st_hi));   // the lane's read buffer belongs to the next chunk once the caller is done with this one
-	return BSX_OK;
-}
-static int dev_qc_read(bsx_device_t *d, bsx_qc_counts_t *out, int reset)
-{
-	if (!d || !out) return BSX_E_ARG;
-	HIPCHK(hipSetDevice(d->ordinal));
-	int rc;
-	if ((rc = qc_table(d)) != BSX_OK) return rc;
-	std::lock_guard<std::mutex> lock(d->qc_mu);
-	HIPCHK(hipDeviceSynchronize());   // every lane's batches
-	HIPCHK(hipMemcpy(out, d->qc.p, sizeof(bsx_qc_counts_t), hipMemcpyDeviceToHost));
-	if (reset) HIPCHK(hipMemset(d->qc.p, 0, sizeof(bsx_qc_counts_t)));
-	return BSX_OK;
-}
-extern "C" BSX_API int bsx_qc_batch(bsx_device_t *d, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
-{ return lane_qc_batch(d, 0, n, jobs, cigar_pool, cigar_pool_len); }
-extern "C" BSX_API int bsx_qc_read(bsx_device_t *d, bsx_qc_counts_t *out, int reset) { return dev_qc_read(d, out, reset); }
-
-// ------------------------------------------------------------------------------------------
-// BISCUITqc coverage tables (k_cov.hip)
-// ------------------------------------------------------------------------------------------
-static int cov_alloc(const char *what, size_t bytes, void **out)   // zeroed device memory that is not a lane's
-{
-	*out = nullptr;
-	if (hipMalloc(out, bytes) != hipSuccess) {
-		size_t fr = 0, tot = 0; (void)hipGetLastError(); (void)hipMemGetInfo(&fr, &tot);
-		fprintf(stderr, "[bsx-hip] coverage tables: no room for %s, %zu bytes (%zu of %zu bytes free)\n", what, bytes, fr, tot);
-		*out = nullptr; return BSX_E_NOMEM;
-	}
-	// the lanes' streams do not wait for the null stream: the zeroes are there before anything is launched on one of them
-	if (hipMemsetAsync(*out, 0, bytes, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(*out); *out = nullptr; return BSX_E_NODEVICE; }
-	return BSX_OK;
-}
-static int cov_state_locked(bsx_device_t *d)   // the difference array, made on first use; the caller holds cov_mu
-{
-	if (d->cov_diff) return BSX_OK;
-	return cov_alloc("the depth state", cov_diff_entries(d->ix.l_pac) * 8, &d->cov_diff);
-}
-static int lane_cov_batch(bsx_device_t *d, int lane, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
-{
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	if (n == 0) return BSX_OK;
-	if (n < 0 || !jobs || (!cigar_pool && cigar_pool_len)) return BSX_E_ARG;
-	Lane &L = d->lane[lane];
-	for (int64_t i = 0; i < n; ++i) { // every event of every job inside the array, every CIGAR word inside the pool
-		const bsx_qc_job_t &j = jobs[i];
-		if ((size_t)j.cig_off + j.n_cigar > cigar_pool_len || j.fpos < 0 || j.fpos > d->ix.l_pac) { fprintf(stderr, "[bsx-hip] cov job %lld: invalid\n", (long long)i); return BSX_E_ARG; }
-		uint64_t span = 0;
-		for (uint32_t k = 0; k < j.n_cigar; ++k) { const uint32_t c = cigar_pool[j.cig_off + k]; const uint32_t op = c & 0xf; if (op > 4) return BSX_E_ARG; if (op == 0 || op == 2) span += c >> 4; }
-		if ((uint64_t)j.fpos + span > (uint64_t)d->ix.l_pac) { fprintf(stderr, "[bsx-hip] cov job %lld: beyond the reference\n", (long long)i); return BSX_E_ARG; }
-	}
-	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
-	std::lock_guard<std::mutex> lock(d->cov_mu);   // until the launch is done: bsx_cov_reset frees the state under the same lock
-	HIPCHK(hipSetDevice(d->ordinal));
-	int rc;
-	if ((rc = cov_state_locked(d)) != BSX_OK) return rc;
-	if ((rc = L.qcjobs.reserve((size_t)n * sizeof(bsx_qc_job_t))) != BSX_OK) return rc;
-	if ((rc = L.qcpool.reserve(cigar_pool_len * 4 + 64)) != BSX_OK) return rc;
-	H2D(L.st_hi, L.qcjobs.p, jobs, (size_t)n * sizeof(bsx_qc_job_t));
-	H2D(L.st_hi, L.qcpool.p, cigar_pool, cigar_pool_len * 4);
-	launch_cov_add(L.st_hi, d->n_cu, d->cov_diff, d->ix.l_pac, (const bsx_qc_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p, (long long)cigar_pool_len);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipStreamSynchronize(L.st_hi));   // the staging buffers are the next batch's
-	return BSX_OK;
-}
-static int dev_cov_set_mask(bsx_device_t *d, int which, int64_t n, const int64_t *beg_end)
-{
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	if (which < 0 || which > 1 || n < 0 || (n && !beg_end)) return BSX_E_ARG;
-	for (int64_t i = 0; i < n; ++i) if (beg_end[2 * i] < 0 || beg_end[2 * i] > beg_end[2 * i + 1] || beg_end[2 * i + 1] > d->ix.l_pac) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->cov_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	HIPCHK(hipDeviceSynchronize());
-	const size_t bytes = cov_mask_words(d->ix.l_pac) * 4;
-	int rc;
-	if (d->cov_mask[which]) HIPCHK(hipMemset(d->cov_mask[which], 0, bytes));
-	else if ((rc = cov_alloc("a mask", bytes, (void**)&d->cov_mask[which])) != BSX_OK) return rc;
-	if (n == 0) return BSX_OK;
-	long long *iv = nullptr;
-	if (hipMalloc((void**)&iv, (size_t)n * 16) != hipSuccess) { (void)hipGetLastError(); return BSX_E_NOMEM; }
-	hipError_t e = hipMemcpy(iv, beg_end, (size_t)n * 16, hipMemcpyHostToDevice);
-	if (e == hipSuccess) { launch_cov_paint(0, d->n_cu, d->cov_mask[which], d->ix.l_pac, iv, (long long)n); e = hipGetLastError(); }
-	if (e == hipSuccess) e = hipDeviceSynchronize();
-	(void)hipFree(iv);
-	HIPCHK(e);
-	return BSX_OK;
-}
-static int dev_cov_tables(bsx_device_t *d, bsx_cov_tables_t *out)
-{
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	if (!out) return BSX_E_ARG;
-	memset(out, 0, sizeof(*out));
-	HIPCHK(hipSetDevice(d->ordinal));
-	int rc;
-	long lds_bins = bsx_tune_long("cov_lds_bins", COV_LDS_BINS_MAX), flush_tiles = bsx_tune_long("cov_flush_tiles", 524287);
-	if (lds_bins < 1 || lds_bins > COV_LDS_BINS_MAX || (lds_bins & (lds_bins - 1)) || flush_tiles < 1 || flush_tiles > 524287) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->cov_mu);
-	if ((rc = cov_state_locked(d)) != BSX_OK) return rc;
-	if ((d->cov_mask[0] != nullptr) != (d->cov_mask[1] != nullptr)) { fprintf(stderr, "[bsx-hip] coverage tables: one GC mask without the other\n"); return BSX_E_ARG; }
-	HIPCHK(hipDeviceSynchronize());   // every lane's batches
-	const long long n_tiles = (long long)cov_n_tiles(d->ix.l_pac);
-	void *tsum = nullptr, *bins = nullptr;
-	if ((rc = cov_alloc("the tile sums", (size_t)n_tiles * 8 + 16, &tsum)) != BSX_OK) return rc;
-	int *gmax = (int*)((char*)tsum + (size_t)n_tiles * 8);
-	int vmax = 0;
-	hipError_t e = hipSuccess;
-	launch_cov_sums(0, d->n_cu, d->cov_diff, n_tiles, tsum);
-	launch_cov_max(0, d->n_cu, d->ix, d->cov_diff, tsum, n_tiles, gmax);
-	e = hipGetLastError();
-	if (e == hipSuccess) e = hipMemcpy(&vmax, gmax, 4, hipMemcpyDeviceToHost);
-	const uint64_t nb = (uint64_t)(vmax < 0 ? 0 : vmax) + 1;
-	std::vector<uint64_t> host((size_t)BSX_COV_N_TABLES * nb);
-	if (e == hipSuccess && (rc = cov_alloc("the bins", host.size() * 8, &bins)) == BSX_OK) {
-		launch_cov_count(0, d->n_cu, d->ix, d->cov_diff, tsum, n_tiles, d->cov_mask[0], d->cov_mask[1], (int)lds_bins, (int)flush_tiles, (unsigned long long*)bins, (long long)nb);
-		e = hipGetLastError();
-		if (e == hipSuccess) e = hipMemcpy(host.data(), bins, host.size() * 8, hipMemcpyDeviceToHost);
-	}
-	(void)hipFree(tsum);
-	if (bins) (void)hipFree(bins);
-	if (rc != BSX_OK) return rc;
-	HIPCHK(e);
-	out->have_gc = d->cov_mask[0] ? 1 : 0;
-	for (int i = 0; i < (out->have_gc ? BSX_COV_N_TABLES : 4); ++i) {
-		out->t[i].count = (uint64_t*)malloc(nb * 8);
-		if (!out->t[i].count) { bsx_cov_tables_free(out); return BSX_E_NOMEM; }
-		memcpy(out->t[i].count, host.data() + (size_t)i * nb, nb * 8);
-		out->t[i].n_bins = nb;
-	}
-	return BSX_OK;
-}
-static int dev_cov_reset(bsx_device_t *d)
-{
-	if (!d) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->cov_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (d->cov_diff || d->cov_mask[0] || d->cov_mask[1]) HIPCHK(hipDeviceSynchronize());
-	cov_release(d);
-	return BSX_OK;
-}
-extern "C" BSX_API int bsx_cov_batch(bsx_device_t *d, int64_t n, const bsx_qc_job_t *jobs, const uint32_t *cigar_pool, size_t cigar_pool_len)
-{ return lane_cov_batch(d, 0, n, jobs, cigar_pool, cigar_pool_len); }
-extern "C" BSX_API int bsx_cov_set_mask(bsx_device_t *d, int which, int64_t n, const int64_t *beg_end) { return dev_cov_set_mask(d, which, n, beg_end); }
-extern "C" BSX_API int bsx_cov_tables(bsx_device_t *d, bsx_cov_tables_t *out) { return dev_cov_tables(d, out); }
-extern "C" BSX_API int bsx_cov_reset(bsx_device_t *d) { return dev_cov_reset(d); }
-
-// ------------------------------------------------------------------------------------------
-// BISCUITqc base-averaged conversion table (k_meth.hip)
-// ------------------------------------------------------------------------------------------
-static int meth_state_locked(bsx_device_t *d)   // the counters, made on first use; the caller holds meth_mu
-{
-	if (d->meth_st) return BSX_OK;
-	const size_t bytes = meth_state_entries(d->ix.l_pac) * 16;
-	if (hipMalloc(&d->meth_st, bytes) != hipSuccess) {
-		size_t fr = 0, tot = 0; (void)hipGetLastError(); (void)hipMemGetInfo(&fr, &tot);
-		fprintf(stderr, "[bsx-hip] base-averaged conversion table: no room for the counters, %zu bytes (%zu of %zu bytes free)\n", bytes, fr, tot);
-		d->meth_st = nullptr; return BSX_E_NOMEM;
-	}
-	// the lanes' streams do not wait for the null stream: the zeroes are there before anything is launched on one of them
-	if (hipMemsetAsync(d->meth_st, 0, bytes, 0) != hipSuccess || hipStreamSynchronize(0) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(d->meth_st); d->meth_st = nullptr; return BSX_E_NODEVICE; }
-	return BSX_OK;
-}
-static int lane_meth_batch(bsx_device_t *d, int lane, int64_t n, const bsx_meth_job_t *jobs, const uint32_t *pool, size_t pool_len)
-{
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	if (n == 0) return BSX_OK;
-	if (n < 0 || !jobs || !pool) return BSX_E_ARG;
-	Lane &L = d->lane[lane];
-	for (int64_t i = 0; i < n; ++i) { // every column of every job inside the genome, every CIGAR and mask word inside the pool
-		const bsx_meth_job_t &j = jobs[i];
-		if ((size_t)j.cig_off + j.n_cigar > pool_len || j.rlen < 1 || j.rlen > (1u << 30) || (size_t)j.qm_off + (j.rlen + 31) / 32 > pool_len || j.fpos < 0 || j.fpos >= d->ix.l_pac) {
-			fprintf(stderr, "[bsx-hip] meth job %lld: invalid\n", (long long)i); return BSX_E_ARG;
-		}
-		uint64_t span = 0, rspan = 0;
-		for (uint32_t k = 0; k < j.n_cigar; ++k) { const uint32_t c = pool[j.cig_off + k], op = c & 0xf; if (op > 4) return BSX_E_ARG; span += c >> 4; if (op == 0 || op == 2) rspan += c >> 4; }
-		if (span > (1u << 30)) return BSX_E_ARG;
-		if ((uint64_t)j.fpos + rspan > (uint64_t)d->ix.l_pac) { fprintf(stderr, "[bsx-hip] meth job %lld: beyond the reference\n", (long long)i); return BSX_E_ARG; }
-	}
-	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
-	std::lock_guard<std::mutex> lock(d->meth_mu);   // until the launch is done: bsx_meth_reset frees the state under the same lock
-	HIPCHK(hipSetDevice(d->ordinal));
-	int rc;
-	if ((rc = meth_state_locked(d)) != BSX_OK) return rc;
-	if ((rc = L.qcjobs.reserve((size_t)n * sizeof(bsx_meth_job_t))) != BSX_OK) return rc;
-	if ((rc = L.qcpool.reserve(pool_len * 4 + 64)) != BSX_OK) return rc;
-	H2D(L.st_hi, L.qcjobs.p, jobs, (size_t)n * sizeof(bsx_meth_job_t));
-	H2D(L.st_hi, L.qcpool.p, pool, pool_len * 4);
-	launch_meth_add(L.st_hi, d->ix, (const uint8_t*)L.reads.p, (long long)L.n_reads, (const bsx_meth_job_t*)L.qcjobs.p, (long long)n, (const uint32_t*)L.qcpool.p,
-	                (long long)pool_len, d->meth_st, d->n_cu);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipStreamSynchronize(L.st_hi));   // the staging buffers are the next batch's, the lane's read buffer the next chunk's
-	return BSX_OK;
-}
-static int dev_meth_read(bsx_device_t *d, int64_t fpos, int64_t n, uint32_t *out)
-{
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	if (fpos < 0 || n < 0 || fpos > d->ix.l_pac || n > d->ix.l_pac - fpos || (n && !out)) return BSX_E_ARG;
-	if (n == 0) return BSX_OK;
-	std::lock_guard<std::mutex> lock(d->meth_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!d->meth_st) { memset(out, 0, (size_t)n * 16); return BSX_OK; }
-	HIPCHK(hipDeviceSynchronize());   // every lane's batches
-	HIPCHK(hipMemcpy(out, (const char*)d->meth_st + (size_t)fpos * 16, (size_t)n * 16, hipMemcpyDeviceToHost));   // (little endian: ret, conv, opp_ref, opp_alt)
-	return BSX_OK;
-}
-static int dev_meth_tables(bsx_device_t *d, bsx_meth_tables_t *out)
-{
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	if (!out) return BSX_E_ARG;
-	memset(out, 0, sizeof(*out));
-	const long flush_tiles = bsx_tune_long("meth_flush_tiles", METH_FLUSH_TILES_MAX);
-	if (flush_tiles < 1 || flush_tiles > METH_FLUSH_TILES_MAX) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->meth_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!d->meth_st) return BSX_OK;   // no batch yet: no site
-	HIPCHK(hipDeviceSynchronize());   // every lane's batches
-	unsigned long long *cells = nullptr;
-	if (hipMalloc((void**)&cells, sizeof(*out)) != hipSuccess) { (void)hipGetLastError(); return BSX_E_NOMEM; }
-	hipError_t e = hipMemset(cells, 0, sizeof(*out));
-	if (e == hipSuccess) { launch_meth_tables(0, d->n_cu, d->ix, d->meth_st, (long long)meth_n_tiles(d->ix.l_pac), (int)flush_tiles, cells); e = hipGetLastError(); }
-	if (e == hipSuccess) e = hipMemcpy(out, cells, sizeof(*out), hipMemcpyDeviceToHost);
-	(void)hipFree(cells);
-	HIPCHK(e);
-	return BSX_OK;
-}
-static int dev_meth_reset(bsx_device_t *d)
-{
-	if (!d) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->meth_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (d->meth_st) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(d->meth_st); d->meth_st = nullptr; }
-	return BSX_OK;
-}
-// the methylation sites of the state (k_msite.hip): the tiles' counts come to the host, which sums them and cuts the window that fits cap; the
-// records of that window are written on the device at their final places and come down in one copy
-static int dev_meth_sites(bsx_device_t *d, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next)
-{
-	if (!d || !d->has_index) return BSX_E_NODEVICE;
-	if (!opt || !n || !f_next || f_lo < 0 || f_lo > f_hi || f_hi > d->ix.l_pac || cap < BSX_COV_TILE || !out) return BSX_E_ARG;
-	if (opt->type < BSX_METH_TYPE_CG || opt->type > BSX_METH_TYPE_C || opt->min_cov < 1 || (opt->merge && opt->type != BSX_METH_TYPE_CG)) return BSX_E_ARG;
-	*n = 0; *f_next = f_hi;
-	if (f_lo == f_hi) return BSX_OK;
-	if (cap > (1ll << 31) - 1) cap = (1ll << 31) - 1;   // 32-bit places
-	std::lock_guard<std::mutex> lock(d->meth_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (!d->meth_st) return BSX_OK;   // no batch yet: no site
-	HIPCHK(hipDeviceSynchronize());   // every lane's batches
-	const long long t_lo = f_lo / BSX_COV_TILE, nt = (f_hi + BSX_COV_TILE - 1) / BSX_COV_TILE - t_lo;
-	bsx_meth_site_opt_t o = *opt;
-	o.merge = o.merge ? 1 : 0; o.pad = 0;
-	uint32_t *cnt = nullptr;    // nt counts, then the window's nt + 1 exclusive sums
-	bsx_meth_site_t *recs = nullptr;
-	if (hipMalloc((void**)&cnt, ((size_t)nt + 1) * 4) != hipSuccess) { (void)hipGetLastError(); return BSX_E_NOMEM; }
-	std::vector<uint32_t> h((size_t)nt + 1);
-	launch_msite_count(0, d->n_cu, d->ix, d->meth_st, o, f_lo, f_hi, t_lo, nt, cnt);
-	hipError_t e = hipGetLastError();
-	if (e == hipSuccess) e = hipMemcpy(h.data(), cnt, (size_t)nt * 4, hipMemcpyDeviceToHost);
-	long long w = 0;            // tiles of the window
-	uint64_t total = 0;
-	int rc = BSX_OK;
-	if (e == hipSuccess) {
-		for (; w < nt; ++w) {
-			const uint32_t c = h[(size_t)w];
-			if (c > BSX_COV_TILE) { rc = BSX_E_INTERNAL; break; }
-			if (total + c > (uint64_t)cap) break;
-			h[(size_t)w] = (uint32_t)total; total += c;
-		}
-		if (rc == BSX_OK) h[(size_t)w] = (uint32_t)total;
-	}
-	if (e == hipSuccess && rc == BSX_OK && total) {
-		if (hipMalloc((void**)&recs, (size_t)total * sizeof(bsx_meth_site_t)) != hipSuccess) { (void)hipGetLastError(); rc = BSX_E_NOMEM; }
-		if (rc == BSX_OK) e = hipMemcpy(cnt, h.data(), ((size_t)w + 1) * 4, hipMemcpyHostToDevice);
-		if (rc == BSX_OK && e == hipSuccess) { launch_msite_emit(0, d->n_cu, d->ix, d->meth_st, o, f_lo, f_hi, t_lo, w, cnt, recs); e = hipGetLastError(); }
-		if (rc == BSX_OK && e == hipSuccess) e = hipMemcpy(out, recs, (size_t)total * sizeof(bsx_meth_site_t), hipMemcpyDeviceToHost);
-	}
-	if (recs) (void)hipFree(recs);
-	(void)hipFree(cnt);
-	HIPCHK(e);
-	if (rc != BSX_OK) return rc;
-	*n = (int64_t)total;
-	*f_next = w == nt ? f_hi : (int64_t)(t_lo + w) * BSX_COV_TILE;
-	return BSX_OK;
-}
-static_assert(sizeof(bsx_meth_tables_t) == 2 * BSX_METH_N_CTX * 8, "k_meth_walk's cells are bsx_meth_tables_t");
-extern "C" BSX_API int bsx_meth_sites(bsx_device_t *d, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next)
-{
-	return dev_meth_sites(d, opt, f_lo, f_hi, out, cap, n, f_next);
-}
-extern "C" BSX_API int bsx_meth_batch(bsx_device_t *d, int64_t n, const bsx_meth_job_t *jobs, const uint32_t *pool, size_t pool_len) { return lane_meth_batch(d, 0, n, jobs, pool, pool_len); }
-extern "C" BSX_API int bsx_meth_read(bsx_device_t *d, int64_t fpos, int64_t n, uint32_t *out) { return dev_meth_read(d, fpos, n, out); }
-extern "C" BSX_API int bsx_meth_tables(bsx_device_t *d, bsx_meth_tables_t *out) { return dev_meth_tables(d, out); }
-extern "C" BSX_API int bsx_meth_reset(bsx_device_t *d) { return dev_meth_reset(d); }
-
-// ------------------------------------------------------------------------------------------
-// duplicate templates (k_markdup.hip)
-// ------------------------------------------------------------------------------------------
-static int md_alloc(bsx_device_t *d, hipStream_t st, uint64_t n_slots, MdSlot **out)   // an empty table of n_slots
-{
-	if (hipMalloc((void**)out, n_slots * sizeof(MdSlot)) != hipSuccess) {
-		size_t fr = 0, tot = 0; (void)hipGetLastError(); (void)hipMemGetInfo(&fr, &tot);
-		fprintf(stderr, "[bsx-hip] markdup: no room for a table of %llu slots, %llu bytes (%zu of %zu bytes free; the table in use has %llu slots)\n",
-		        (unsigned long long)n_slots, (unsigned long long)(n_slots * sizeof(MdSlot)), fr, tot, (unsigned long long)d->md_slots);
-		*out = nullptr; return BSX_E_NOMEM;
-	}
-	launch_md_init(st, *out, n_slots);
-	HIPCHK(hipGetLastError());
-	return BSX_OK;
-}
-// room for `more` new keys at a load of one half or less: the first table, or one of twice (four times, ...) the slots with every slot moved over
-static int md_room(bsx_device_t *d, Lane &L, uint64_t more, unsigned long long *ctr)
-{
-	uint64_t want = d->md_slots;
-	if (!d->md) {
-		const long t = bsx_tune_long("markdup_slots", 0);
-		want = t > 0 ? (uint64_t)t : std::max<uint64_t>(65536, 32 * more);
-		while (want & (want - 1)) want += want & (~want + 1);   // up to a power of two
-		if (want < 2) want = 2;
-	}
-	while ((d->md_used + more) * 2 > want) want *= 2;
-	if (d->md && want == d->md_slots) return BSX_OK;
-	MdSlot *T = nullptr;
-	int rc;
-	if ((rc = md_alloc(d, L.st_hi, want, &T)) != BSX_OK) return rc;
-	if (d->md) {
-		unsigned long long lost = 0;
-		launch_md_rehash(L.st_hi, d->md, d->md_slots, T, want, ctr);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(&lost, ctr + MD_CTR_LOST, 8, hipMemcpyDeviceToHost, L.st_hi));
-		HIPCHK(hipStreamSynchronize(L.st_hi));
-		if (lost) { (void)hipFree(T); return BSX_E_INTERNAL; }
-		(void)hipFree(d->md);
-		if (bsx_phases()) fprintf(stderr, "[M::markdup] table grown from %llu to %llu slots (%llu taken)\n", (unsigned long long)d->md_slots, (unsigned long long)want, (unsigned long long)d->md_used);
-	}
-	d->md = T; d->md_slots = want;
-	return BSX_OK;
-}
-static int dev_markdup_reset(bsx_device_t *d)
-{
-	if (!d) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->md_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (d->md) { HIPCHK(hipDeviceSynchronize()); (void)hipFree(d->md); }
-	d->md = nullptr; d->md_slots = d->md_used = 0;
-	return BSX_OK;
-}
-#define MD_MAX_SALTS 8
-static int lane_markdup_batch(bsx_device_t *d, int lane, int64_t n, const bsx_markdup_key_t *keys, uint64_t first_ordinal, uint8_t *dup_out)
-{
-	if (!d) return BSX_E_NODEVICE;
-	if (n < 0) return dev_markdup_reset(d);
-	if (n == 0) return BSX_OK;
-	if (!keys || !dup_out || first_ordinal + (uint64_t)n < first_ordinal || first_ordinal + (uint64_t)n == ~0ull) return BSX_E_ARG;
-	Lane &L = d->lane[lane];
-	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
-	std::lock_guard<std::mutex> lock(d->md_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	const int bits = (int)bsx_tune_long("markdup_hash_bits", 64);
-	const size_t res_bytes = ((size_t)n + 7) & ~(size_t)7, tail = 4 * 8;   // res[n], then ctr[4]: slots taken, keys left open, slots lost in a rehash
-	int rc;
-	if ((rc = L.mdkeys.reserve((size_t)n * sizeof(bsx_markdup_key_t))) != BSX_OK) return rc;
-	if ((rc = L.mdres.reserve(res_bytes + tail)) != BSX_OK) return rc;
-	if ((rc = L.mdslot.reserve((size_t)n * 8)) != BSX_OK) return rc;
-	uint8_t *res = (uint8_t*)L.mdres.p;
-	unsigned long long *ctr = (unsigned long long*)(res + res_bytes);
-	std::vector<uint8_t> host(res_bytes + tail);
-	HIPCHK(hipMemsetAsync(res, MD_RES_OPEN, res_bytes, L.st_hi));
-	HIPCHK(hipMemsetAsync(ctr, 0, tail, L.st_hi));
-	H2D(L.st_hi, L.mdkeys.p, keys, (size_t)n * sizeof(bsx_markdup_key_t));
-	uint64_t open = (uint64_t)n;
-	for (unsigned salt = 0; open; ++salt) {
-		if (salt == MD_MAX_SALTS) { fprintf(stderr, "[bsx-hip] markdup: %llu keys met other keys with their claim word at %d salts\n", (unsigned long long)open, MD_MAX_SALTS); return BSX_E_INTERNAL; }
-		if ((rc = md_room(d, L, open, ctr)) != BSX_OK) return rc;
-		HIPCHK(hipMemsetAsync(ctr, 0, tail, L.st_hi));
-		launch_md_round(L.st_hi, d->md, d->md_slots, (const bsx_markdup_key_t*)L.mdkeys.p, (long long)n, first_ordinal, salt, bits, res, (unsigned long long*)L.mdslot.p, ctr);
-		HIPCHK(hipGetLastError());
-		D2H(L.st_hi, host.data(), res, res_bytes + tail);
-		const unsigned long long *c = (const unsigned long long*)(host.data() + res_bytes);
-		d->md_used += c[0];
-		open = c[1];
-	}
-	for (int64_t i = 0; i < n; ++i) {
-		if (host[(size_t)i] == MD_RES_FULL || host[(size_t)i] == MD_RES_OPEN) return BSX_E_INTERNAL;
-		dup_out[i] = host[(size_t)i] == MD_RES_DUP;
-	}
-	return BSX_OK;
-}
-extern "C" BSX_API int bsx_markdup_batch(bsx_device_t *d, int64_t n, const bsx_markdup_key_t *keys, uint64_t first_ordinal, uint8_t *dup_out)
-{ if (n < 0) return BSX_E_ARG; return lane_markdup_batch(d, 0, n, keys, first_ordinal, dup_out); }
-extern "C" BSX_API int bsx_markdup_reset(bsx_device_t *d) { return dev_markdup_reset(d); }
-extern "C" BSX_API int bsx_markdup_table_info(bsx_device_t *d, uint64_t *n_slots, uint64_t *n_used)
-{
-	if (!d) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->md_mu);
-	if (n_slots) *n_slots = d->md_slots;
-	if (n_used) *n_used = d->md_used;
-	return BSX_OK;
-}
-
-// ---- coordinate order (k_sort.hip) ----
-// The passes over (sort_k[0], sort_p[0]) -- n keys; iota: the payload is the key's index and sort_p[0] holds nothing yet.  *cur = the buffer pair the
-// sorted keys and their payloads are in; *have_pay = 0 only when iota and every key was equal (nothing ran: the payload is the identity).
-static int sort_passes(bsx_device *d, int64_t n, bool iota, int *cur, int *have_pay, int *n_passes)
-{
-	hipStream_t st = d->sort_st;
-	uint64_t *k[2] = {(uint64_t*)d->sort_k[0].p, (uint64_t*)d->sort_k[1].p};
-	uint32_t *p[2] = {(uint32_t*)d->sort_p[0].p, (uint32_t*)d->sort_p[1].p};
-	*cur = 0; *have_pay = !iota; *n_passes = 0;
-	if (n <= BSX_SORT_TILE) {
-		launch_sort_small(st, (const unsigned long long*)k[0], iota ? nullptr : p[0], (unsigned long long*)k[1], p[1], n);
-		HIPCHK(hipGetLastError());
-		*cur = 1; *have_pay = 1;
-		return BSX_OK;
-	}
-	int rc;
-	if ((rc = d->sort_counts.reserve(sort_n_tiles(n) * 256 * 4)) != BSX_OK) return rc;
-	if ((rc = d->sort_btot.reserve(sort_n_scan_blocks(n) * 4 + 16)) != BSX_OK) return rc;
-	unsigned long long *bits_d = (unsigned long long*)((char*)d->sort_btot.p + ((sort_n_scan_blocks(n) * 4 + 7) & ~(size_t)7)), bits = 0;
-	HIPCHK(hipMemsetAsync(bits_d, 0, 8, st));
-	launch_sort_bits(st, (const unsigned long long*)k[0], n, bits_d);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(&bits, bits_d, 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	for (int shift = 0; shift < 64; shift += 8) {
-		if (((bits >> shift) & 255) == 0) continue;   // every key has the same digit here: the pass would move nothing
-		launch_sort_pass(st, (const unsigned long long*)k[*cur], *have_pay ? p[*cur] : nullptr, (unsigned long long*)k[*cur ^ 1], p[*cur ^ 1], n, shift,
-		                 (unsigned int*)d->sort_counts.p, (unsigned int*)d->sort_btot.p);
-		HIPCHK(hipGetLastError());
-		*cur ^= 1; *have_pay = 1; ++*n_passes;
-	}
-	return BSX_OK;
-}
-static int sort_buffers(bsx_device *d, int64_t n)
-{
-	int rc;
-	if (!d->sort_st) HIPCHK(hipStreamCreateWithFlags(&d->sort_st, hipStreamNonBlocking));
-	for (int i = 0; i < 2; ++i) {
-		if ((rc = d->sort_k[i].reserve((size_t)n * 8)) != BSX_OK) return rc;
-		if ((rc = d->sort_p[i].reserve((size_t)n * 4)) != BSX_OK) return rc;
-	}
-	return BSX_OK;
-}
-static int dev_sort_run(bsx_device_t *d, int64_t n, const uint64_t *keys, uint32_t *perm_out)
-{
-	if (!d) return BSX_E_NODEVICE;
-	if (n < 0 || n >= ((int64_t)1 << 31) || (n > 0 && (!keys || !perm_out))) return BSX_E_ARG;
-	if (n == 0) return BSX_OK;
-	std::lock_guard<std::mutex> lock(d->sort_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	int rc, cur, have_pay, n_passes;
-	if ((rc = sort_buffers(d, n)) != BSX_OK) return rc;
-	uint64_t *run = nullptr;
-	if (hipMalloc((void**)&run, (size_t)n * 8) != hipSuccess) { (void)hipGetLastError(); fprintf(stderr, "[bsx-hip] sort: no device memory for a run of %lld keys\n", (long long)n); return BSX_E_NOMEM; }
-	rc = BSX_E_NODEVICE;
-	do {
-		if (hipMemcpyAsync(d->sort_k[0].p, keys, (size_t)n * 8, hipMemcpyHostToDevice, d->sort_st) != hipSuccess) break;
-		if ((rc = sort_passes(d, n, true, &cur, &have_pay, &n_passes)) != BSX_OK) break;
-		rc = BSX_E_NODEVICE;
-		if (hipMemcpyAsync(run, d->sort_k[cur].p, (size_t)n * 8, hipMemcpyDeviceToDevice, d->sort_st) != hipSuccess) break;
-		if (have_pay && hipMemcpyAsync(perm_out, d->sort_p[cur].p, (size_t)n * 4, hipMemcpyDeviceToHost, d->sort_st) != hipSuccess) break;
-		if (hipStreamSynchronize(d->sort_st) != hipSuccess) break;
-		rc = BSX_OK;
-	} while (0);
-	if (rc != BSX_OK) { fprintf(stderr, "[bsx-hip] sort: %s\n", hipGetErrorString(hipGetLastError())); (void)hipFree(run); return rc; }
-	if (!have_pay) for (int64_t i = 0; i < n; ++i) perm_out[i] = (uint32_t)i;
-	if (bsx_phases()) fprintf(stderr, "[M::sort] run %zu: %lld keys, %d passes\n", d->sort_runs.size(), (long long)n, n_passes);
-	d->sort_runs.push_back(std::make_pair(run, n));
-	return BSX_OK;
-}
-static int dev_sort_schedule(bsx_device_t *d, int64_t *n_total, uint32_t **run_of)
-{
-	if (!d) return BSX_E_NODEVICE;
-	if (!n_total || !run_of) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->sort_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	int64_t n = 0;
-	*n_total = 0; *run_of = nullptr;
-	for (auto &r : d->sort_runs) n += r.second;
-	if (n == 0) return BSX_OK;
-	if (n >= ((int64_t)1 << 31)) { fprintf(stderr, "[bsx-hip] sort: %lld records; the schedule holds fewer than 2^31\n", (long long)n); return BSX_E_ARG; }
-	int rc, cur, have_pay, n_passes;
-	if ((rc = sort_buffers(d, n)) != BSX_OK) return rc;
-	int64_t off = 0;
-	for (size_t r = 0; r < d->sort_runs.size(); ++r) { // the concatenation in run order, each key's payload its run
-		const int64_t m = d->sort_runs[r].second;
-		HIPCHK(hipMemcpyAsync((uint64_t*)d->sort_k[0].p + off, d->sort_runs[r].first, (size_t)m * 8, hipMemcpyDeviceToDevice, d->sort_st));
-		HIPCHK(hipMemsetD32Async((hipDeviceptr_t)((uint32_t*)d->sort_p[0].p + off), (int)r, (size_t)m, d->sort_st));
-		off += m;
-	}
-	if ((rc = sort_passes(d, n, false, &cur, &have_pay, &n_passes)) != BSX_OK) return rc;
-	uint32_t *out = (uint32_t*)malloc((size_t)n * 4);
-	if (!out) return BSX_E_NOMEM;
-	if (hipMemcpyAsync(out, d->sort_p[cur].p, (size_t)n * 4, hipMemcpyDeviceToHost, d->sort_st) != hipSuccess || hipStreamSynchronize(d->sort_st) != hipSuccess) {
-		fprintf(stderr, "[bsx-hip] sort: %s\n", hipGetErrorString(hipGetLastError())); free(out); return BSX_E_NODEVICE;
-	}
-	if (bsx_phases()) fprintf(stderr, "[M::sort] schedule: %zu runs, %lld keys, %d passes\n", d->sort_runs.size(), (long long)n, n_passes);
-	*n_total = n; *run_of = out;
-	return BSX_OK;
-}
-static int dev_sort_reset(bsx_device_t *d)
-{
-	if (!d) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->sort_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	if (d->sort_st) HIPCHK(hipStreamSynchronize(d->sort_st));
-	sort_release(d);
-	return BSX_OK;
-}
-extern "C" BSX_API int bsx_sort_run(bsx_device_t *d, int64_t n, const uint64_t *keys, uint32_t *perm_out) { return dev_sort_run(d, n, keys, perm_out); }
-extern "C" BSX_API int bsx_sort_schedule(bsx_device_t *d, int64_t *n_total, uint32_t **run_of) { return dev_sort_schedule(d, n_total, run_of); }
-extern "C" BSX_API int bsx_sort_reset(bsx_device_t *d) { return d ? dev_sort_reset(d) : BSX_E_NODEVICE; }
-extern "C" BSX_API int bsx_sort_info(bsx_device_t *d, uint64_t *n_runs, uint64_t *n_keys)
-{
-	if (!d) return BSX_E_NODEVICE;
-	std::lock_guard<std::mutex> lock(d->sort_mu);
-	uint64_t n = 0;
-	for (auto &r : d->sort_runs) n += (uint64_t)r.second;
-	if (n_runs) *n_runs = d->sort_runs.size();
-	if (n_keys) *n_keys = n;
-	return BSX_OK;
-}
-
-// ---- BAM output (k_bam.hip, k_bgzf.hip) ----
-extern "C" {
-#include "bam.h"
-}
-static int bam_host_grow(uint8_t **out, size_t *cap, size_t want)
-{
-	if (want <= *cap) return BSX_OK;
-	size_t m = *cap ? *cap : 4096;
-	while (m < want) m += m >> 1;
-	uint8_t *p = (uint8_t*)realloc(*out, m);
-	if (!p) return BSX_E_NOMEM;
-	*out = p; *cap = m;
-	return BSX_OK;
-}
-static int bam_stream(bsx_device_t *d) { if (!d->bam_st) HIPCHK(hipStreamCreateWithFlags(&d->bam_st, hipStreamNonBlocking)); return BSX_OK; }
-// text -> records: newlines counted per tile and summed on the device, line starts, a size pass (the first refused line comes back as one word per
-// workgroup), the sizes summed on the device, the emit pass; 4 + 8 x workgroups + 4 bytes come to the host between the launches, then the payload
-static int dev_bam_encode(bsx_device_t *d, const bsx_bam_refs_t *refs, const char *text, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len,
-                          int64_t *n_records, int64_t *bad_record, int *bad_why)
-{
-	if (!d) return BSX_E_NODEVICE;
-	if (!refs || !out || !out_cap || !out_len || !n_records || !bad_record || !bad_why || (len && !text)) return BSX_E_ARG;
-	*out_len = 0; *n_records = 0; *bad_record = -1; *bad_why = 0;
-	if (len == 0) return BSX_OK;
-	if (text[len - 1] != '\n' || len >= ((size_t)1 << 31)) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->bam_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	int rc;
-	if ((rc = bam_stream(d)) != BSX_OK) return rc;
-	hipStream_t st = d->bam_st;
-	if (d->bam_tab_serial != refs->serial) { // the writer's name table, once
-		if ((rc = d->bam_names.reserve(refs->names_len + 16)) != BSX_OK || (rc = d->bam_noff.reserve(((size_t)refs->n + 1) * 4)) != BSX_OK ||
-		    (rc = d->bam_nid.reserve(((size_t)refs->n + 1) * 4)) != BSX_OK) return rc;
-		if (refs->names_len) HIPCHK(hipMemcpyAsync(d->bam_names.p, refs->names, refs->names_len, hipMemcpyHostToDevice, st));
-		HIPCHK(hipMemcpyAsync(d->bam_noff.p, refs->off, ((size_t)refs->n + 1) * 4, hipMemcpyHostToDevice, st));
-		if (refs->n) HIPCHK(hipMemcpyAsync(d->bam_nid.p, refs->id, (size_t)refs->n * 4, hipMemcpyHostToDevice, st));
-		HIPCHK(hipStreamSynchronize(st));
-		d->bam_tab_serial = refs->serial;
-	}
-	const long long nt = bam_n_tiles((long long)len);
-	if ((rc = d->bam_text.reserve(len + 16)) != BSX_OK || (rc = d->bam_cnt.reserve(((size_t)nt + 1) * 4)) != BSX_OK) return rc;
-	const char *d_text = (const char*)d->bam_text.p;
-	uint32_t *cnt = (uint32_t*)d->bam_cnt.p;
-	HIPCHK(hipMemcpyAsync(d->bam_text.p, text, len, hipMemcpyHostToDevice, st));
-	launch_bam_count(st, d->n_cu, d_text, (long long)len, cnt);
-	launch_bam_scan(st, cnt, cnt, nt);
-	HIPCHK(hipGetLastError());
-	uint32_t n_lines = 0;
-	HIPCHK(hipMemcpyAsync(&n_lines, cnt + nt, 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	const int grid = bam_lines_grid(n_lines);
-	if ((rc = d->bam_start.reserve(((size_t)n_lines + 1) * 4)) != BSX_OK || (rc = d->bam_size.reserve(((size_t)n_lines + 1) * 4)) != BSX_OK ||
-	    (rc = d->bam_bad.reserve((size_t)grid * 8)) != BSX_OK || (rc = d->bam_err.reserve(((size_t)n_lines + 1) * 4)) != BSX_OK) return rc;
-	uint32_t *start = (uint32_t*)d->bam_start.p, *size = (uint32_t*)d->bam_size.p;
-	int *errs = (int*)d->bam_err.p;
-	launch_bam_starts(st, d->n_cu, d_text, (long long)len, cnt, start);
-	launch_bam_size(st, d_text, start, n_lines, (const char*)d->bam_names.p, (const uint32_t*)d->bam_noff.p, (const int32_t*)d->bam_nid.p, refs->n, size, errs,
-	                (unsigned long long*)d->bam_bad.p);
-	HIPCHK(hipGetLastError());
-	std::vector<unsigned long long> bad((size_t)grid);
-	HIPCHK(hipMemcpyAsync(bad.data(), d->bam_bad.p, (size_t)grid * 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	unsigned long long first = ~0ull;
-	for (unsigned long long b : bad) first = std::min(first, b);
-	const long long n_ok = first == ~0ull ? (long long)n_lines : (long long)(first >> 4);
-	if (first != ~0ull) { *bad_record = n_ok; *bad_why = (int)(first & 15); }
-	uint32_t total = 0;
-	if (n_ok > 0) {
-		launch_bam_scan(st, size, size, n_ok);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(&total, size + n_ok, 4, hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));
-		if ((rc = d->bam_pay.reserve((size_t)total + 16)) != BSX_OK || (rc = bam_host_grow(out, out_cap, total)) != BSX_OK) return rc;
-		launch_bam_emit(st, d_text, start, n_ok, (const char*)d->bam_names.p, (const uint32_t*)d->bam_noff.p, (const int32_t*)d->bam_nid.p, refs->n, errs, size,
-		                (uint8_t*)d->bam_pay.p);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipMemcpyAsync(*out, d->bam_pay.p, total, hipMemcpyDeviceToHost, st));
-		HIPCHK(hipStreamSynchronize(st));
-	}
-	*out_len = total; *n_records = n_ok;
-	return BSX_OK;
-}
-// payload -> members: every block deflated into its 64 KiB slot, the sizes summed on the device, the members moved behind each other, one copy down
-static int dev_bgzf_deflate(bsx_device_t *d, const uint8_t *payload, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len)
-{
-	if (!d) return BSX_E_NODEVICE;
-	if (!out || !out_cap || !out_len || (len && !payload)) return BSX_E_ARG;
-	*out_len = 0;
-	if (len == 0) return BSX_OK;
-	if (len >= ((size_t)1 << 31)) return BSX_E_ARG;
-	std::lock_guard<std::mutex> lock(d->bam_mu);
-	HIPCHK(hipSetDevice(d->ordinal));
-	int rc;
-	if ((rc = bam_stream(d)) != BSX_OK) return rc;
-	hipStream_t st = d->bam_st;
-	const long long nb = ((long long)len + BSX_BGZF_BLOCK - 1) / BSX_BGZF_BLOCK;
-	const int grid = bgzf_grid(nb);
-	if ((rc = d->bz_in.reserve(len + 16)) != BSX_OK || (rc = d->bz_tok.reserve(bgzf_tok_bytes(grid))) != BSX_OK || (rc = d->bz_cand.reserve(bgzf_cand_bytes(grid))) != BSX_OK ||
-	    (rc = d->bz_slots.reserve((size_t)nb * 65536)) != BSX_OK || (rc = d->bz_sizes.reserve(((size_t)nb + 1) * 4)) != BSX_OK || (rc = d->bz_ops.reserve(256 * 4)) != BSX_OK) return rc;
-	if (!d->bz_ops_ok) {
-		uint32_t ops[256];
-		bgzf_crc_ops(ops);
-		HIPCHK(hipMemcpyAsync(d->bz_ops.p, ops, sizeof(ops), hipMemcpyHostToDevice, st));
-		HIPCHK(hipStreamSynchronize(st));
-		d->bz_ops_ok = true;
-	}
-	uint32_t *sizes = (uint32_t*)d->bz_sizes.p, total = 0;
-	HIPCHK(hipMemcpyAsync(d->bz_in.p, payload, len, hipMemcpyHostToDevice, st));
-	for (long long b0 = 0; b0 < nb; b0 += grid) // (launches on one stream: the second one's workgroups find the workspaces free)
-		launch_bgzf_deflate(st, (const uint8_t*)d->bz_in.p, (long long)len, b0, (int)std::min<long long>(grid, nb - b0), (const uint32_t*)d->bz_ops.p, (uint32_t*)d->bz_tok.p,
-		                    (uint16_t*)d->bz_cand.p, (uint8_t*)d->bz_slots.p, sizes);
-	launch_bam_scan(st, sizes, sizes, nb);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(&total, sizes + nb, 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	if (total < 27 * (uint64_t)nb || (uint64_t)total > 65536ull * (uint64_t)nb) return BSX_E_INTERNAL;
-	if ((rc = d->bz_out.reserve(total)) != BSX_OK || (rc = bam_host_grow(out, out_cap, total)) != BSX_OK) return rc;
-	launch_bgzf_compact(st, d->n_cu, (const uint8_t*)d->bz_slots.p, sizes, nb, (uint8_t*)d->bz_out.p);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipMemcpyAsync(*out, d->bz_out.p, total, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	*out_len = total;
-	return BSX_OK;
-}
 
 // the seams as one vtable for the host pipeline; ctx = (device, lane)
-#define LR(c) ((LaneRef*)(c))->d, ((LaneRef*)(c))->lane
 static int be_set_opt(void *c, const bsx_opt_t *o) { return lane_set_opt(LR(c), o); }
 static int be_set_reads(void *c, const uint8_t *b, size_t n) { return lane_set_reads(LR(c), b, n); }
 static int be_seed(void *c, const bsx_opt_t *o, int64_t n, const bsx_seed_task_t *t, bsx_intv_t **out, int64_t *cap, int64_t *off) { return lane_seed_batch(LR(c), o, n, t, out, cap, off); }
@@ -2910,58 +2076,6 @@ static int be_glb_tags(void *c, int64_t n, const bsx_glb_job_t *j, bsx_glb_res_t
 static int be_glb_tags_ctx(void *c, int64_t n, const bsx_glb_job_t *j, bsx_glb_res_t *r, uint32_t *pool, size_t len, bsx_glb_tag_t *t, char **md, int64_t *cap, bsx_glb_ctx_t *x)
 { return lane_global_batch(LR(c), n, j, r, pool, len, t, md, cap, x); }
 
-static int be_qc(void *c, int64_t n, const bsx_qc_job_t *j, const uint32_t *pool, size_t len, bsx_qc_counts_t *read_out, int reset)
-{
-	int rc = lane_qc_batch(LR(c), n, j, pool, len);
-	if (rc == BSX_OK && read_out) rc = dev_qc_read(((LaneRef*)c)->d, read_out, reset);
-	return rc;
-}
-
-static int be_markdup(void *c, int64_t n, const bsx_markdup_key_t *k, uint64_t first, uint8_t *out) { return lane_markdup_batch(LR(c), n, k, first, out); }
-
-static int be_cov(void *c, int op, int64_t n, const bsx_qc_job_t *j, const uint32_t *pool, size_t len, const int64_t *beg_end, bsx_cov_tables_t *out)
-{
-	bsx_device_t *d = ((LaneRef*)c)->d;
-	if (op == BSX_COV_OP_BATCH) return lane_cov_batch(LR(c), n, j, pool, len);
-	if (op == BSX_COV_OP_QC_BATCH) return lane_qc_batch(LR(c), n, j, pool, len, true);
-	if (op == BSX_COV_OP_MASK || op == BSX_COV_OP_MASK + 1) return dev_cov_set_mask(d, op - BSX_COV_OP_MASK, n, beg_end);
-	if (op == BSX_COV_OP_TABLES) return dev_cov_tables(d, out);
-	if (op == BSX_COV_OP_RESET) return dev_cov_reset(d);
-	return BSX_E_ARG;
-}
-
-static int be_meth(void *c, int op, int64_t n, const bsx_meth_job_t *j, const uint32_t *pool, size_t len, bsx_meth_tables_t *out)
-{
-	bsx_device_t *d = ((LaneRef*)c)->d;
-	if (op == BSX_METH_OP_BATCH) return lane_meth_batch(LR(c), n, j, pool, len);
-	if (op == BSX_METH_OP_TABLES) return dev_meth_tables(d, out);
-	if (op == BSX_METH_OP_RESET) return dev_meth_reset(d);
-	return BSX_E_ARG;
-}
-
-static int be_meth_sites(void *c, const bsx_meth_site_opt_t *opt, int64_t f_lo, int64_t f_hi, bsx_meth_site_t *out, int64_t cap, int64_t *n, int64_t *f_next)
-{
-	return dev_meth_sites(((LaneRef*)c)->d, opt, f_lo, f_hi, out, cap, n, f_next);
-}
-
-static int be_sort(void *c, int op, int64_t n, const uint64_t *keys, uint32_t *perm_out, int64_t *n_total, uint32_t **run_of)
-{
-	bsx_device_t *d = ((LaneRef*)c)->d;
-	if (op == BSX_SORT_OP_RUN) return dev_sort_run(d, n, keys, perm_out);
-	if (op == BSX_SORT_OP_SCHEDULE) return dev_sort_schedule(d, n_total, run_of);
-	if (op == BSX_SORT_OP_RESET) return dev_sort_reset(d);
-	return BSX_E_ARG;
-}
-
-static int be_bam_encode(void *c, const bsx_bam_refs_t *refs, const char *text, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len, int64_t *n_records,
-                         int64_t *bad_record, int *bad_why)
-{
-	return dev_bam_encode(((LaneRef*)c)->d, refs, text, len, out, out_cap, out_len, n_records, bad_record, bad_why);
-}
-static int be_bgzf_deflate(void *c, const uint8_t *payload, size_t len, uint8_t **out, size_t *out_cap, size_t *out_len)
-{
-	return dev_bgzf_deflate(((LaneRef*)c)->d, payload, len, out, out_cap, out_len);
-}
 
 static LaneRef g_lane_ref[8][BSX_LANES];   // ctx storage for the vtables (by device ordinal)
 
@@ -2974,8 +2088,8 @@ extern "C" int bsx_hip_backend_lane(bsx_device_t *dev, int lane, bsx_backend_t *
 	memset(out, 0, sizeof(*out));
 	out->ctx = r; out->name = "hip-gfx950";
 	out->set_opt = be_set_opt; out->set_reads = be_set_reads; out->seed_batch = be_seed; out->sa_batch = be_sa;
-	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx; out->qc_batch = be_qc; out->markdup_batch = be_markdup; out->cov_batch = be_cov; out->sort_batch = be_sort; out->meth_batch = be_meth; out->meth_sites = be_meth_sites;
-	out->bam_encode = be_bam_encode; out->bgzf_deflate = be_bgzf_deflate;
+	out->extend_batch = be_ext; out->sw_batch = be_sw; out->global_batch = be_glb; out->global_batch_tags = be_glb_tags; out->global_batch_tags_ctx = be_glb_tags_ctx;
+	shim_tables_backend(out);
 	out->regions_batch = bsx_tune_long("host_chain", 0) ? nullptr : be_regions;
 	out->regions_finish = out->regions_batch ? be_regions_finish : nullptr;   // BSX_HOST_CHAIN=1: host chaining for every task (A/B checks)
 	out->regions_dedup = out->regions_batch && !bsx_tune_long("host_dedup", 0) ? be_dedup : nullptr;   // BSX_HOST_DEDUP=1: C5 on the host for every read (A/B checks)

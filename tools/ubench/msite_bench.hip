@@ -81,7 +81,7 @@ int main(int argc, char **argv)
 		double emit_ms = 0, copy_ms = 0, sums_ms = 0, fmt_mem_ms = 0, fmt_file_ms = 0;
 		unsigned long long lines = 0, fmt_lines = 0, fmt_bytes = 0;
 		int windows = 0;
-		for (long long t0 = 0; t0 < nt; ) { // the window that fits the buffer, as dev_meth_sites (shim.hip) cuts it
+		for (long long t0 = 0; t0 < nt; ) { // the window that fits the buffer, as bsx_meth_sites (shim_tables.hip) cuts it
 			t = now_ms();
 			long long w = 0;
 			uint64_t total = 0;
