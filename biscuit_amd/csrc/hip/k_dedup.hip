@@ -21,7 +21,7 @@
 #define DD_CAP 32
 
 // klib introsort (ksort.h:184-236) over region indices with the control flow of csrc/host/util.c:bsx_introsort (see
-// rg_introsort_keys in k_regions.hip); LT(x, y) compares the regions the indices name
+// rg_introsort_keys in rg_task.hpp); LT(x, y) compares the regions the indices name
 template <int STK = 4, typename Arr, typename LT>
 __device__ __forceinline__ void dd_introsort(Arr a, int n, LT lt)
 {

@@ -1,13 +1,12 @@
 // parsort.hpp -- klib's introsort (ksort.h:184-236) run by a whole wavefront over packed 32-bit keys (weight << RG_KEY_BITS | index), larger
 // weights first, reproducing the reference's order of EQUAL keys: every partition of a segment made at once from the stop masks of the
 // original segment, klib's stack discipline and depth count, its comb-sort fallback, the closing insertion pass as a rank by counting.
-// Used by the chain filter (k_regions.hip: chains by weight) and by the de-duplication of long region lists (k_dedup.hip: regions by the
+// Used by the chain filter (rg_task.hpp: chains by weight) and by the de-duplication of long region lists (k_dedup.hip: regions by the
 // dense rank of their key, for the lists that have tied keys).  Checked against the sequential algorithm in tools/dbg/parsort_model.py and
 // tests/test_parsort_model.py.
 #pragma once
 #include "wave.hpp"
 #define RG_KEY_BITS 13   // chain indices < 8192 (RgHuge::CCAP)
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // The same sort by the whole wavefront with every partition made AT ONCE (round 4).  klib's partition loop (ksort.h:212-217) is Hoare's: i stops at the
 // positions whose weight is <= the pivot's ("L stops", the pivot at a[t] among them), j at those in (s, t) whose weight is >= it ("R

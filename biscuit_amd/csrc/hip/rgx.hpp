@@ -1,5 +1,5 @@
 // rgx.hpp -- what the chaining tiers (k_regions.hip) export per strand search for the launches that turn chains into regions:
-// k_x4prep + k_ext4 (k_ext4.hip: the extensions of every chain's best seed, four to a wavefront) and k_c2r (k_regions.hip: the
+// k_x4prep + k_ext4 (k_ext4.hip: the extensions of every chain's best seed, four to a wavefront) and k_c2r (k_c2r.hip: the
 // reference's seed loop, mem_chain2region1, memchain.c:742-870, which takes those extensions from the record).
 // A record = RgXHdr | RgXChain[n_chains] | RgXSeed[n_seeds] | RgXExt[n_chains] (the last only when hdr.has_ext), at xoff[t] in the pool.
 #pragma once

@@ -1676,7 +1676,7 @@ static int lane_sw_batch(bsx_device_t *d, int lane, int64_t n, const bsx_sw_job_
 	if (n == 0) return BSX_OK;
 	std::lock_guard<std::mutex> hi_lock(L.hi_mu);
 	HIPCHK(hipSetDevice(d->ordinal));
-	if (bsx_tune_is_set("sw_form")) { // tests: score-only jobs of up to 199 x 199 through the seed filter's alignments (k_regions.hip), in the order given
+	if (bsx_tune_is_set("sw_form")) { // tests: score-only jobs of up to 199 x 199 through the seed filter's alignments (k_seedsw.hip), in the order given
 		const char *form = bsx_tune_str("sw_form");
 		const bool f16 = strcmp(form, "ssw16") == 0;
 		if ((!f16 && strcmp(form, "ssw32") != 0) || n > 0x7fffffff || L.n_reads == 0) return BSX_E_ARG;

@@ -1,4 +1,4 @@
-// ssw16_bound.h -- when the packed 16-bit seed-filter alignment (k_swl16, k_regions.hip) is exact.  Plain C++ without device headers: the host
+// ssw16_bound.h -- when the packed 16-bit seed-filter alignment (k_swl16, k_seedsw.hip) is exact.  Plain C++ without device headers: the host
 // decides with it once per launch whether the chunk's seeds go through k_swl16 or through the 32-bit alignment of k_seedsw_apply, and the CPU
 // restatement of the kernel (tests/host_ssw16.cpp) range-checks every 16-bit value against it.
 //

@@ -1,5 +1,5 @@
 // sw_pass.hpp -- one pass of ksw_u8 / ksw_i16 (lib/aln/ksw.c:111-334) by one wavefront: see k_sw.hip for how the striped
-// SSE2 kernel's result is reproduced.  Shared by k_sw (K5, mate rescue) and the seed filter of long reads in k_regions.hip (C3).
+// SSE2 kernel's result is reproduced.  Shared by k_sw (K5, mate rescue) and the seed filter of long reads in k_seedsw.hip (C3).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dev_common.hpp"

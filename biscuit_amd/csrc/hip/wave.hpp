@@ -9,6 +9,8 @@
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 __device__ __forceinline__ int wave_lane() { return (int)(threadIdx.x & 63); }
+// a wave-uniform value lives in a scalar register: say so for what comes out of LDS, shuffles and reductions
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 // Cross-lane data movement goes through DPP (one VALU instruction, no LDS round trip) wherever the pattern allows:
 // shifts inside a row of 16 lanes, the row broadcasts that stitch rows together, the whole-wave shift by one lane.

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Generates tests/golden/ref_vectors_ssw.npz: ksw_align2 inputs and the REAL reference's outputs at the shapes of the seed-SW filter
-(mem_seed_sw, memchain.c:501-535): windows of up to 199 x 199, 16-bit mode, xtra = KSW_XSTART alone -- what k_swl16 (k_regions.hip: sixteen
+(mem_seed_sw, memchain.c:501-535): windows of up to 199 x 199, 16-bit mode, xtra = KSW_XSTART alone -- what k_swl16 (k_seedsw.hip: sixteen
 jobs to a wavefront in packed 16-bit) and the 32-bit alignment of a seed without room in the job list have to score.  Same entry points and
 array layout as make_vectors.py / make_vectors_long.py, under the key prefix ssw_, plus ssw_fam (a family id per vector, names in ssw_fams).
 

@@ -1,4 +1,4 @@
-// host_ssw16.cpp -- a lane-by-lane scalar restatement of the packed 16-bit seed-filter alignment (biscuit_amd/csrc/hip/k_regions.hip: k_swl16)
+// host_ssw16.cpp -- a lane-by-lane scalar restatement of the packed 16-bit seed-filter alignment (biscuit_amd/csrc/hip/k_seedsw.hip: k_swl16)
 // for the CPU tests: sixteen consecutive jobs to a wavefront, a job in 8 lanes, two jobs in the halves of a lane's registers -- here a
 // uint16_t each, with the kernel's three operations (an add that wraps, a subtraction that clamps at 0 as unsigned, a SIGNED maximum) --, one
 // stripe count and one row count for the sixteen, the query profile as biased bytes, the padding columns, the rows past a job's target, and

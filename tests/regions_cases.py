@@ -1,4 +1,4 @@
-"""Designed strand searches for the region kernels (csrc/hip/k_regions.hip), shared by tests/golden/make_vectors_regions.py (which records
+"""Designed strand searches for the region kernels (csrc/hip/k_regions.hip and, past the tiers, k_seedsw.hip and k_c2r.hip), shared by tests/golden/make_vectors_regions.py (which records
 what the reference's own mem_chain, mem_chain_flt, mem_flt_chained_seeds and mem_chain2region make of them), tests/test_regions_recorded_cpu.py
 and tests/test_gpu_regions_recorded.py.
 
@@ -41,7 +41,7 @@ RgHuge's caps (4096 / 8192) are out of scope.
 import zlib
 import numpy as np
 
-# ------------------------------------------------------------------------------------------ the caps (k_regions.hip; the CPU test compares)
+# ------------------------------------------------------------------------------------------ the caps (rg_common.hpp, k_c2r.hip; the CPU test compares)
 STORES = {      # ICAP, SCAP, CCAP, PCAP
     "RgSmall": (64, 128, 128, 32),
     "RgMid": (128, 256, 256, 64),

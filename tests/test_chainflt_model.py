@@ -1,5 +1,5 @@
 """CPU: the chain filter in the form the device runs it (a lane per candidate chain, integer thresholds, the undroppable prefix, nothing tested when
-every chain is kept: tools/dbg/chainflt_model.py, which mirrors k_regions.hip stage D step by step) keeps exactly the chains mem_chain_flt keeps
+every chain is kept: tools/dbg/chainflt_model.py, which mirrors stage D of rg_task, rg_task.hpp, step by step) keeps exactly the chains mem_chain_flt keeps
 (memchain.c:426-482 as written, float where the reference is float), and the same kept values wherever they can matter (max_chain_extend set)."""
 import os
 import random

@@ -18,7 +18,7 @@ HIP = os.path.join(ROOT, "biscuit_amd", "biscuit_align")
 def variant_dir(v):
     d = os.path.join(ROOT, "tests", "_build", "lds_dbg_%d" % v)
     lib = os.path.join(d, "libbiscuit_amd.so")
-    src = [os.path.join(ROOT, "biscuit_amd", "csrc", "hip", f) for f in ("k_regions.hip", "shim.hip", "rgx.hpp", "ext_dp.hpp", "dev_common.hpp")]
+    src = [os.path.join(ROOT, "biscuit_amd", "csrc", "hip", f) for f in ("k_regions.hip", "rg_common.hpp", "rg_task.hpp", "shim.hip", "rgx.hpp", "ext_dp.hpp", "dev_common.hpp")]
     if not os.path.exists(lib) or any(os.path.getmtime(f) > os.path.getmtime(lib) for f in src):
         p = subprocess.run([os.path.join(ROOT, "tools", "dbg", "lds_variants.sh"), str(v)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=1800)
         assert p.returncode == 0, p.stdout.decode()[-3000:]

@@ -1,4 +1,4 @@
-"""The region kernels (csrc/hip/k_regions.hip: SA intervals -> chains -> filtered chains -> regions, through the ladder of LDS and HBM stores)
+"""The region kernels (csrc/hip/k_occ.hip, k_regions.hip, k_seedsw.hip, k_c2r.hip: SA intervals -> chains -> filtered chains -> regions, through the ladder of LDS and HBM stores)
 against the reference's own regions, recorded: Device.regions over the designed strand searches of tests/regions_cases.py must equal
 tests/golden/ref_regions.npz per strand search -- every region, every field, in order, frac_rep by its bits -- with the cases alone, scattered
 among two thousand ordinary strand searches, under each routing setting of the library and under the option set that makes the seed filter run

@@ -1,5 +1,5 @@
 """-m gpu: the seed filter's two alignments against scores recorded from the reference's own ksw_align2 (tests/golden/ref_vectors_ssw.npz), through
-the test seam of bsx_sw_batch -- the setting sw_form.  ssw16: the very launch of k_swl16 (k_regions.hip: sixteen jobs to a wavefront in packed
+the test seam of bsx_sw_batch -- the setting sw_form.  ssw16: the very launch of k_swl16 (k_seedsw.hip: sixteen jobs to a wavefront in packed
 16-bit) that launch_seedsw makes, over the jobs in the order given, so that tests/ssw_cases.py decides who shares a wavefront and a register;
 ssw32: the 32-bit alignment k_seedsw_apply makes for a seed without room in the job list (sw_pass<2>, <3>, <4> by the padded query).  The e2e
 tests see these scores only as `score >= threshold`; here every score is compared, and every family's count."""

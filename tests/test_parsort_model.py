@@ -1,4 +1,4 @@
-"""CPU: the wave-parallel form of klib's introsort that the device's chain filter runs (k_regions.hip, rg_introsort_par: every Hoare partition
+"""CPU: the wave-parallel form of klib's introsort that the device's chain filter runs (parsort.hpp, rg_introsort_par: every Hoare partition
 made at once from the two stop masks, the closing insertion pass as a stable rank) leaves EXACTLY the permutation of the reference's own
 `ks_introsort` template (lib/aln/ksort.h:184-234, instantiated in oracle/_ref with mem_flt's comparator shape: records compared on one field,
 descending).  The order of chains of equal weight is part of mem_chain_flt's result (memchain.c:426), so the permutation is what is pinned, on

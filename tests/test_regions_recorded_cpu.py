@@ -6,7 +6,7 @@ tests/regions_cases.py) -- the parts that need no GPU:
   SA look-ups through the batch seams, bsx_chain_build / bsx_chain_filter, the seed filter, the extension rounds), over the CPU restatement
   of the kernels (oracle/port.c): list for list, field for field, in order, frac_rep by its bits
 * the Python restatement (oracle/e2e.align1_core), on the cases it gets through in seconds
-* the cap table of regions_cases against the typedefs and #defines of k_regions.hip, and the coverage table -- which case sits at which cap
+* the cap table of regions_cases against the typedefs and #defines of rg_common.hpp and k_c2r.hip, and the coverage table -- which case sits at which cap
   and on which side -- against the recorded counts, so that a case that drifts off its edge fails here instead of testing nothing
 
 tests/test_gpu_regions_recorded.py holds the device's side."""
@@ -138,7 +138,8 @@ def test_python_restatement_equals_the_recording(rec, index_base):
 
 # ------------------------------------------------------------------------------------------ the caps and the coverage
 def test_the_cap_table_is_the_headers():
-    src = open(os.path.join(ROOT, "biscuit_amd", "csrc", "hip", "k_regions.hip")).read()
+    # the stores and the capacities every region unit reads, then the workspaces of the chains -> regions launches
+    src = "".join(open(os.path.join(ROOT, "biscuit_amd", "csrc", "hip", f)).read() for f in ("rg_common.hpp", "k_c2r.hip"))
     for name, (icap, scap, ccap, pcap) in RC.STORES.items():
         m = re.search(r"^typedef RgStore<([^>]*)> %s;" % name, src, re.M)
         assert m, name

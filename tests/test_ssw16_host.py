@@ -1,4 +1,4 @@
-"""CPU: the packed 16-bit seed-filter alignment (k_swl16, csrc/hip/k_regions.hip) as a lane-by-lane scalar restatement (tests/host_ssw16.cpp:
+"""CPU: the packed 16-bit seed-filter alignment (k_swl16, csrc/hip/k_seedsw.hip) as a lane-by-lane scalar restatement (tests/host_ssw16.cpp:
 8 lanes x 2 halves a job pair, the wave's shared stripe and row counts, the biased byte profile, the closed form of the lazy-F loop; the guard
 is the kernel's own header) against the scores recorded from the reference's ksw_align2, under every ordering of tests/ssw_cases.py, with every
 16-bit value range-checked: no option set the guard admits leaves [0, 32767]."""

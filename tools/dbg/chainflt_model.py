@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Model of the chain filter as the LDS tiers run it (k_regions.hip, stage D of rg_task): mem_chain_flt's overlap loop (memchain.c:426-482) with a lane
+"""Model of the chain filter as the LDS tiers run it (rg_task.hpp, stage D of rg_task): mem_chain_flt's overlap loop (memchain.c:426-482) with a lane
 per candidate chain, the test in integers (thresholds T and D per chain), the chains nobody can drop entered up front and nothing tested at all
 when that is every chain.  Input: the chains of a strand search in the order klib's sort left them (begin, end, weight, alt).  Output: which
 survive.  `sequential` is the reference's loop as written, in float where the reference computes in float; tests/test_chainflt_model.py holds

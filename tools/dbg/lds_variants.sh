@@ -1,7 +1,8 @@
 #!/bin/bash
 # Debug builds of libbiscuit_amd.so (never the product's): k_regions.hip compiled under -DRG_DBG=<n> (1: guard words around the LDS objects of
-# the chaining tiers, 2: their tables filled with 0xff before every strand search -- see k_regions.hip) and shim.hip with the check of the
-# exported chain records (-DBSX_DEBUG_XCHECK), one per directory tests/_build/lds_dbg_<n>/.  A command line runs against one of them with
+# the chaining tiers, 2: their tables filled with 0xff before every strand search -- see k_regions.hip, the one unit RG_DBG reaches: the tier
+# kernels and, through rg_task.hpp, the chaining they run) and shim.hip with the check of the exported chain records (-DBSX_DEBUG_XCHECK),
+# one per directory tests/_build/lds_dbg_<n>/; every other unit is the product's object.  A command line runs against one of them with
 # LD_LIBRARY_PATH=tests/_build/lds_dbg_<n> (biscuit_align's RUNPATH comes after it).  Needs the product's objects under build/ (make all).
 # The compiler is the Makefile's ($HIPCC, else $ROCM/bin/hipcc); every compile is waited for by pid, so a failed one ends the script there.
 cd "$(dirname "$0")/../.."

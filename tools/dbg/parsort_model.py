@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Model of the wave-parallel form of klib's introsort (ksort.h:184-234) used by the chain filter's sort (k_regions.hip, rg_introsort_par):
+"""Model of the wave-parallel form of klib's introsort (ksort.h:184-234) used by the chain filter's sort (parsort.hpp, rg_introsort_par):
 every Hoare partition is computed at once from the two stop masks, the final insertion pass is a stable rank by counting.  Checked here
 against the sequential algorithm on random keys with many ties (the order of equal weights is part of the result)."""
 import random

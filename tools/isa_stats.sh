@@ -2,7 +2,7 @@
 # Static look at a kernel's gfx950 code without a GPU: instruction counts by kind, scalar-register spills (v_writelane /
 # v_readlane: "lane-moves", which also counts the kernel's own cross-lane reads), s_nop padding, and the same per loop nest, from the compiler's assembly.  What it is for: the region kernels are
 # bound by scalar issue, so a change that removes spills or scalar control flow shows here before it is timed.
-#   tools/isa_stats.sh biscuit_amd/csrc/hip/k_regions.hip _Z5k_c2r
+#   tools/isa_stats.sh biscuit_amd/csrc/hip/k_c2r.hip _Z5k_c2r
 #   tools/isa_stats.sh biscuit_amd/csrc/hip/k_seed.hip _Z6k_seedILi3
 set -eu
 SRC=$1; KERNEL=$2
