@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include "dev_common.hpp"
 #include "wave.hpp"
+#include "ext_stop.hpp"
 
 template <int NC>
 __device__ __forceinline__ bsx_ext_res_t ext_dp(const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t &J,
@@ -149,11 +150,13 @@ __device__ __forceinline__ bsx_ext_res_t ext_dp(const DevIndex &ix, const DevSco
 // LDS traffic and no barriers: the right-shift of H by one column is a lane shift, F is the same max-plus prefix
 // scan, and entries outside the band simply keep their old contents, exactly like the array they mirror.
 // Needs qlen + 1 <= 64 * NC entries.
-template <int NC>
+template <int NC, int XS_FAM = -1>
 __device__ __forceinline__ bsx_ext_res_t ext_dp_reg(const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t &J, int lane,
                                                     const uint8_t *win = nullptr, long long win_beg = 0, const uint8_t *qlds = nullptr, uint32_t qlds_off = 0)
 {   // win: the reference bases [win_beg, ...) already in LDS, one byte each, covering every row of this job (else HBM)
     // qlds: the read already in LDS, qlds[k] = reads[qlds_off + k] (else the chunk's read buffer in HBM)
+    // XS_FAM: the launch family whose counters the stopping rule counts in (ext_stop.hpp); -1: the rule is obeyed but not counted, and with the
+    // switch off not evaluated (the instantiations of the hot launches: a flag and two addresses less to keep in scalar registers)
 	const int qlen = J.qlen, tlen = J.tlen, h0 = J.h0;
 	// the lane's column of this strand's 5x5 matrix: five byte loads per register slot from the kernel's argument block, once per
 	// job (as 25 scalars selected per lane it was a hundred scalar instructions and 25 scalar registers in kernels that spill them)
@@ -186,7 +189,9 @@ __device__ __forceinline__ bsx_ext_res_t ext_dp_reg(const DevIndex &ix, const De
 	int beg = 0, end = qlen;
 	int tb_reg = 4;
 	const bool packed_max = qlen <= 512 && (long long)h0 + (long long)qlen * mx < (1 << 21);   // every H of this job fits 22 bits and every column 9
+	[[maybe_unused]] bool xs_fired = false;
 	for (int i = 0; i < tlen; ++i) {
+		if constexpr (XS_FAM >= 0) if (xs_fired) ext_stop_dead_row(sc, XS_FAM, lane);
 		if ((i & 63) == 0) {
 			const long long tp = J.tpos + (long long)(i + lane) * J.tdir;
 			tb_reg = (i + lane < tlen) ? (win ? (int)win[tp - win_beg] : dev_ref_base(ix.pac, ix.l_pac, tp)) : 4;
@@ -296,6 +301,12 @@ __device__ __forceinline__ bsx_ext_res_t ext_dp_reg(const DevIndex &ix, const De
 			}
 			beg = nb;
 			end = last + 2 < qlen ? last + 2 : qlen;
+		}
+		// no later row can change a result field (ext_stop_rule.h): as if i + 1 == tlen
+		if (ext_stop_gate(m, gscore) && i + 1 < tlen && (XS_FAM >= 0 ? !xs_fired && ext_stop_armed(sc) : sc.ext_stop != 0)) {
+			const int phi = ext_stop_phi_reg<NC>(Hr, Er, beg, qlen, J.parent ? sc.mx_ct : sc.mx_ga, lane);
+			if constexpr (XS_FAM >= 0) { if (ext_stop_decide(sc, XS_FAM, phi, gscore, tlen - 1 - i, lane, xs_fired)) break; }
+			else if (ext_stop_fires(phi, gscore)) break;
 		}
 	}
 	bsx_ext_res_t r;

@@ -12,6 +12,7 @@
 #include "dev_common.hpp"
 #include "wave.hpp"
 #include "ext_pk_bound.h"
+#include "ext_stop.hpp"
 
 typedef short pk2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ pk2 pk_of(uint32_t w) { return __builtin_bit_cast(pk2, w); }
@@ -44,10 +45,10 @@ __device__ __forceinline__ pk2 wave_scan_max_incl_pk(pk2 v)
 	return v;
 }
 
-template <int NP>
+template <int NP, int XS_FAM = -1>
 __device__ __forceinline__ bsx_ext_res_t ext_dp_pk(const DevIndex &ix, const DevScoring &sc, const uint8_t *reads, const bsx_ext_job_t &J, int lane,
                                                    const uint8_t *win = nullptr, long long win_beg = 0, const uint8_t *qlds = nullptr, uint32_t qlds_off = 0)
-{   // win, qlds: as ext_dp_reg
+{   // win, qlds, XS_FAM: as ext_dp_reg
 	const int qlen = J.qlen, tlen = J.tlen, h0 = J.h0;
 	const int8_t *mat = J.parent ? sc.ctmat : sc.gamat;
 	const int o_del = sc.o_del, e_del = sc.e_del, o_ins = sc.o_ins, e_ins = sc.e_ins;
@@ -84,7 +85,9 @@ __device__ __forceinline__ bsx_ext_res_t ext_dp_pk(const DevIndex &ix, const Dev
 	int max = h0, max_i = -1, max_j = -1, max_ie = -1, gscore = -1, max_off = 0;
 	int beg = 0, end = qlen;
 	int tb_reg = 4;
+	[[maybe_unused]] bool xs_fired = false;
 	for (int i = 0; i < tlen; ++i) {
+		if constexpr (XS_FAM >= 0) if (xs_fired) ext_stop_dead_row(sc, XS_FAM, lane);
 		if ((i & 63) == 0) {
 			const long long tp = J.tpos + (long long)(i + lane) * J.tdir;
 			tb_reg = (i + lane < tlen) ? (win ? (int)win[tp - win_beg] : dev_ref_base(ix.pac, ix.l_pac, tp)) : 4;
@@ -188,6 +191,12 @@ __device__ __forceinline__ bsx_ext_res_t ext_dp_pk(const DevIndex &ix, const Dev
 			if (last == -2) last = nb - 1;
 			beg = nb;
 			end = last + 2 < qlen ? last + 2 : qlen;
+		}
+		// no later row can change a result field (ext_stop_rule.h): as if i + 1 == tlen.  PHI in 32 bits from the packed halves
+		if (ext_stop_gate(m, gscore) && i + 1 < tlen && (XS_FAM >= 0 ? !xs_fired && ext_stop_armed(sc) : sc.ext_stop != 0)) {
+			const int phi = ext_stop_phi_pk<NP>(Hp, Ep, beg, qlen, J.parent ? sc.mx_ct : sc.mx_ga, lane);
+			if constexpr (XS_FAM >= 0) { if (ext_stop_decide(sc, XS_FAM, phi, gscore, tlen - 1 - i, lane, xs_fired)) break; }
+			else if (ext_stop_fires(phi, gscore)) break;
 		}
 	}
 	bsx_ext_res_t r;

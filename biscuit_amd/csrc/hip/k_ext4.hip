@@ -31,6 +31,7 @@
 #include "tune.h"
 #include "rgx.hpp"
 #include "x4.hpp"
+#include "ext_stop.hpp"
 
 size_t x4_job_bytes(void) { return sizeof(X4Job); }
 
@@ -258,6 +259,12 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 	for (int c = 0; c < NCQ; ++c) { Hr[c] = Er[c] = 0; sqp[c] = 0; }
 	unsigned int pf_rows = 0, pf_trips = 0, pf_jobs = 0, pf_cold = 0, pf_slots = 0, pf_nrows = 0;
 	[[maybe_unused]] unsigned int jrows = 0;   // (TALLY: rows of the job under way)
+	// the stopping rule (ext_stop_rule.h): the instantiations that count it (the batch form and $BSX_PHASES) also evaluate it with the switch off,
+	// and count the rows an extension runs after the rule has fired on it
+	constexpr bool COUNT = TALLY || !CHAIN;
+	const bool xs_armed = sc.ext_stop != 0 || (COUNT && sc.xs_ctr != nullptr);
+	[[maybe_unused]] bool xs_fired = false;
+	[[maybe_unused]] unsigned int pf_xstop = 0, pf_xeval = 0, pf_xleft = 0, pf_xdead = 0;
 	for (;;) {
 		// ---- between extensions: results, the next side or band, the next job.  Run when two rows of lanes wait for it, when a row has
 		// waited for a few trips, or when no extension is under way (a wave pays for this block whichever of its rows is in it)
@@ -369,6 +376,7 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 							else { if (l == 0) { bsx_ext_res_t r; r.score = X4_DECLINED; r.qle = r.tle = r.gtle = r.gscore = r.max_off = 0; ((bsx_ext_res_t*)res_)[e] = r; } st = X4_IDLE; }
 						} else {
 							max = h0; max_i = max_j = max_ie = -1; gscore = -1; max_off = 0;
+								if constexpr (COUNT) xs_fired = false;   // (an extension that leaves by another door -- sent on, declined -- must not leave it set)
 							beg = 0; end = qlen; i = 0;
 							if (tlen <= 0) st = X4_AFTER;   // no rows: what ksw_extend2 returns without entering its loop
 							else {
@@ -407,7 +415,7 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 		// ---- one row of every extension under way.  Straight-line code: what a row of lanes without an extension computes is thrown
 		// away by selects (a branch per 16 lanes costs the wave more than the instructions it skips)
 		const bool run = st == X4_ROW;
-		if (run) { ++pf_rows; if (CHAIN && s_len < X4_NARROW) ++pf_nrows; if constexpr (TALLY) ++jrows; }
+		if (run) { ++pf_rows; if (CHAIN && s_len < X4_NARROW) ++pf_nrows; if constexpr (TALLY) ++jrows; if constexpr (COUNT) pf_xdead += xs_fired ? 1u : 0u; }
 		// (what the lanes of a row without an extension do to these is of no consequence: the next set-up writes them all)
 		const int t = (int)(y0 & 3u) ^ tcomp;
 		y0 = __builtin_amdgcn_alignbit(y1, y0, 2); y1 = __builtin_amdgcn_alignbit(y2, y1, 2); y2 >>= 2; --yleft;
@@ -510,7 +518,37 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 				else if (yleft == 0) st = X4_REFILL;
 			}
 		}
+		// no later row can change a result field (ext_stop_rule.h): as if i == tlen.  PHI over eh[beg .. qlen] of the rows of lanes whose gate is
+		// open (m < gscore: shut while an extension climbs its diagonal), one pass over the slots and one maximum over the sixteen lanes
+		if (xs_armed) {
+			bool gate = shrink && !stop && ext_stop_gate(m, gscore);
+			if constexpr (COUNT) gate = gate && !xs_fired;
+			if (__ballot(gate)) {
+				const int mx = par ? sc.mx_ct : sc.mx_ga;
+				int phi = 0, q1mx = (qlen - 1 - l) * mx, left = beg - l;   // entry a = 16 c + l counts when 16 c >= left
+#pragma unroll
+				for (int c = 0; c < NCQ; ++c) {
+					const int tm = ext_stop_term(Hr[c], Er[c], q1mx, mx);   // (entries beyond qlen are zero: no potential)
+					phi = ((c << 4) >= left && tm > phi) ? tm : phi;
+					q1mx -= mx << 4;
+				}
+				phi = q_allmax(phi);
+				const bool fire = gate && ext_stop_fires(phi, gscore);
+				if constexpr (COUNT) {
+					if (gate) ++pf_xeval;
+					if (fire) { ++pf_xstop; pf_xleft += (unsigned int)(tlen - i); xs_fired = true; }   // (i is the next row already)
+				}
+				if (fire && sc.ext_stop) stop = true;
+			}
+		}
+		if constexpr (COUNT) if (run && stop) xs_fired = false;
 		if (run && stop) st = X4_AFTER;
+	}
+	if constexpr (COUNT) if (sc.xs_ctr) {
+		unsigned long long *xc = sc.xs_ctr + XS_N * XS_FAM_EXT4;
+		const unsigned int a0 = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_xstop : 0), a1 = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_xeval : 0);
+		const unsigned int a2 = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_xleft : 0), a3 = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_xdead : 0);
+		if (lane == 0) { atomicAdd(&xc[sc.ext_stop ? XS_STOPS : XS_WOULD], (unsigned long long)a0); atomicAdd(&xc[XS_EVALS], (unsigned long long)a1); atomicAdd(&xc[XS_LEFT], (unsigned long long)a2); atomicAdd(&xc[XS_DEAD], (unsigned long long)a3); }
 	}
 	if (prof) { // tracing: jobs, rows, trips (a trip advances up to four rows) and passes through the block between extensions
 		pf_rows = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_rows : 0); pf_jobs = (unsigned int)wave_sum_i32(l == 0 ? (int)pf_jobs : 0);

@@ -105,9 +105,9 @@ k_extend_pk(DevIndex ix, DevScoring sc, const uint8_t *reads, const bsx_ext_job_
 		const bsx_ext_job_t J = jobs[jj];
 		bsx_ext_res_t r;
 		if (J.qlen > EXT_PK_QMAX) { r.score = X4_DECLINED; r.qle = r.tle = r.gtle = r.gscore = r.max_off = 0; }
-		else if (!PK) r = ext_dp_reg<4>(ix, sc, reads, J, lane);
-		else if (J.qlen < 128) r = ext_dp_pk<1>(ix, sc, reads, J, lane);
-		else r = ext_dp_pk<2>(ix, sc, reads, J, lane);
+		else if (!PK) r = ext_dp_reg<4, XS_FAM_WAVE>(ix, sc, reads, J, lane);
+		else if (J.qlen < 128) r = ext_dp_pk<1, XS_FAM_WAVE>(ix, sc, reads, J, lane);
+		else r = ext_dp_pk<2, XS_FAM_WAVE>(ix, sc, reads, J, lane);
 		if (lane == 0) res[jj] = r;
 	}
 }

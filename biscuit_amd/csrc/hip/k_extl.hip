@@ -21,6 +21,7 @@
 #include "kernels.h"
 #include "rgx.hpp"
 #include "x4.hpp"
+#include "ext_stop.hpp"
 
 #define XL_W 64          // window positions (registers)
 #define XL_QCOLS 128     // query columns whose bases a lane holds (2 bits each, 8 registers)
@@ -79,6 +80,11 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 	for (int g = 0; g < XL_W / 16; ++g) QW[g] = 0;
 	unsigned int pf_rows = 0, pf_trips = 0, pf_jobs = 0, pf_cold = 0, pf_bail = 0;
 	[[maybe_unused]] unsigned int jrows = 0;   // (TALLY: rows of the job under way; a job sent on to k_ext4 is tallied there, from its first row again)
+	// the stopping rule (ext_stop_rule.h), counted as in k_ext4
+	constexpr bool COUNT = TALLY || !CHAIN;
+	const bool xs_armed = sc.ext_stop != 0 || (COUNT && sc.xs_ctr != nullptr);
+	[[maybe_unused]] bool xs_fired = false;
+	[[maybe_unused]] unsigned int pf_xstop = 0, pf_xeval = 0, pf_xleft = 0, pf_xdead = 0;
 #define XL_QWIN() do { const int b16_ = base >> 4; _Pragma("unroll") for (int g_ = 0; g_ < XL_W / 16; ++g_) { uint32_t v_ = 0; \
 		_Pragma("unroll") for (int k_ = 0; k_ < XL_QCOLS / 16; ++k_) v_ = b16_ + g_ == k_ ? QF[k_] : v_; QW[g_] = v_; } } while (0)
 	for (;;) {
@@ -199,6 +205,7 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 					if (qlen < 0 || h0 < 0 || jmax0 + 2 >= XL_W || (long long)h0 + (long long)qlen * mx >= 32768) st = XL_BAIL;
 					else {
 						max = h0; max_i = max_j = max_ie = -1; gscore = -1; max_off = 0;
+						if constexpr (COUNT) xs_fired = false;   // (an extension that leaves by another door -- sent on, declined -- must not leave it set)
 						beg = 0; end = qlen; i = 0; base = 0;
 						if (tlen <= 0) st = XL_AFTER;   // no rows: what ksw_extend2 returns without entering its loop
 						else {
@@ -254,7 +261,7 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 		++pf_trips;
 		// ---- one row of every lane's extension (ksw.c:410-470); lanes without one compute on stale registers and throw the result away
 		const bool run = st == XL_ROW;
-		if (run) { ++pf_rows; if constexpr (TALLY) ++jrows; }
+		if (run) { ++pf_rows; if constexpr (TALLY) ++jrows; if constexpr (COUNT) pf_xdead += xs_fired ? 1u : 0u; }
 		const int t = (int)(y0 & 3u) ^ tcomp;
 		y0 = __builtin_amdgcn_alignbit(y1, y0, 2); y1 = __builtin_amdgcn_alignbit(y2, y1, 2); y2 >>= 2; --yleft;
 		beg = beg > i - w ? beg : i - w;
@@ -315,6 +322,34 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 				if (i >= tlen) stop = true;
 				else if (yleft == 0) st = XL_REFILL;
 			}
+		}
+		// no later row can change a result field (ext_stop_rule.h): as if i == tlen.  PHI over eh[beg .. qlen]: the window's registers from
+		// the band's first column on; what lies right of the window is zero (a row that leaves it alive is `wide`: the job goes to k_ext4,
+		// which stops it on the same row).  A pass over the window when some lane's gate is open (m < gscore)
+		if (xs_armed) {
+			bool gate = run && !stop && !wide && ext_stop_gate(m, gscore);
+			if constexpr (COUNT) gate = gate && !xs_fired;
+			if (__ballot(gate)) {
+				const int mx = par ? sc.mx_ct : sc.mx_ga;
+				const int lo = beg - base, hi = qlen - base;
+				int q1mx = (qlen - 1 - base) * mx, phi = 0;
+#pragma unroll
+				for (int p = 0; p < XL_W; ++p) {
+					const uint32_t x = R[p];
+					const int tm = ext_stop_term((int)(x & 0xffffu), (int)(x >> 16), q1mx, mx);
+					phi = (p >= lo && p <= hi && tm > phi) ? tm : phi;
+					q1mx -= mx;
+				}
+				const bool fire = gate && ext_stop_fires(phi, gscore);
+				if constexpr (COUNT) {
+					if (gate) ++pf_xeval;
+					if (fire) { ++pf_xstop; pf_xleft += (unsigned int)(tlen - i); xs_fired = true; }   // (i is the next row already)
+				}
+				if (fire && sc.ext_stop) stop = true;
+			}
+		}
+		if (run) {
+			if constexpr (COUNT) if (stop || wide) xs_fired = false;
 			if (stop) st = XL_AFTER;
 			if (wide) st = XL_BAIL;
 		}
@@ -329,6 +364,12 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 			if (go) XL_QWIN();
 			if (sh && !go) base = beg;   // (leaves the loop: the job is on its way out)
 		}
+	}
+	if constexpr (COUNT) if (sc.xs_ctr) {
+		unsigned long long *xc = sc.xs_ctr + XS_N * XS_FAM_EXTL;
+		const unsigned int a0 = (unsigned int)wave_sum_i32((int)pf_xstop), a1 = (unsigned int)wave_sum_i32((int)pf_xeval);
+		const unsigned int a2 = (unsigned int)wave_sum_i32((int)pf_xleft), a3 = (unsigned int)wave_sum_i32((int)pf_xdead);
+		if (lane == 0) { atomicAdd(&xc[sc.ext_stop ? XS_STOPS : XS_WOULD], (unsigned long long)a0); atomicAdd(&xc[XS_EVALS], (unsigned long long)a1); atomicAdd(&xc[XS_LEFT], (unsigned long long)a2); atomicAdd(&xc[XS_DEAD], (unsigned long long)a3); }
 	}
 	if (prof) {
 		const unsigned int r = (unsigned int)wave_sum_i32((int)pf_rows), jb = (unsigned int)wave_sum_i32((int)pf_jobs), bl = (unsigned int)wave_sum_i32((int)pf_bail);

@@ -1069,13 +1069,15 @@ __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc
 						RG_STAGE(6);
 						// most extensions of a 150 bp read are shorter than a wavefront is wide: one register entry per lane then,
 						// and none of the per-chunk band tests and carries of the wider form
-						if (J.qlen < 64) res = ext_dp_reg<1>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
+						// (the stopping rule is counted in every instantiation of the tiers, which have no tallying form: the counter block's address is
+						// null unless $BSX_PHASES is on, and counting costs these kernels no register, profiles/ext_stop_measurements.md)
+						if (J.qlen < 64) res = ext_dp_reg<1, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
 						else if constexpr (PK) { // two columns per lane: one packed slot up to 127 query bases, two up to 255
-							if (J.qlen < 128) res = ext_dp_pk<1>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
-							else res = ext_dp_pk<2>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
+							if (J.qlen < 128) res = ext_dp_pk<1, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
+							else res = ext_dp_pk<2, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
 						}
-						else if (J.qlen < 128) res = ext_dp_reg<2>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
-						else res = ext_dp_reg<RG_NC>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);   // qlen <= l_query - 1 <= 255: fits the 256 register entries
+						else if (J.qlen < 128) res = ext_dp_reg<2, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
+						else res = ext_dp_reg<RG_NC, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);   // qlen <= l_query - 1 <= 255: fits the 256 register entries
 						res.score = uni(res.score); res.qle = uni(res.qle); res.tle = uni(res.tle); res.gtle = uni(res.gtle);
 						res.gscore = uni(res.gscore); res.max_off = uni(res.max_off);
 						R.score = res.score;

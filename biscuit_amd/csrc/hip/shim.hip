@@ -9,6 +9,7 @@
 #include "shim_dev.hpp"
 #include "index_build.h"
 #include "ext_pk_bound.h"
+#include "ext_stop.hpp"
 #include "rgx.hpp"
 
 #include <sys/time.h>
@@ -303,6 +304,7 @@ static int lane_set_opt(bsx_device_t *d, int lane, const bsx_opt_t *o)
 	sc.o_del = o->o_del; sc.e_del = o->e_del; sc.o_ins = o->o_ins; sc.e_ins = o->e_ins; sc.zdrop = o->zdrop; sc.a = o->a;
 	sc.mx_ct = sc.mx_ga = 0;   // as ksw_extend2 computes it: the maximum starts from 0
 	for (int k = 0; k < 25; ++k) { sc.mx_ct = std::max<int>(sc.mx_ct, sc.ctmat[k]); sc.mx_ga = std::max<int>(sc.mx_ga, sc.gamat[k]); }
+	sc.ext_stop = 0; sc.xs_ctr = nullptr;   // (every launch sequence that reads them arms them first: ext_stop_arm)
 	return BSX_OK;
 }
 extern "C" BSX_API int bsx_device_set_opt(bsx_device_t *d, const bsx_opt_t *o) { return lane_set_opt(d, 0, o); }   // the batch calls of include/bsx.h run on lane 0
@@ -493,6 +495,45 @@ extern "C" BSX_API int bsx_ext_forms(uint64_t c[2], int reset)
 {
 	if (!c) return BSX_E_ARG;
 	for (int k = 0; k < 2; ++k) { c[k] = g_ext_forms[k].load(); if (reset) g_ext_forms[k].store(0); }
+	return BSX_OK;
+}
+
+// The extensions' stopping rule (ext_stop_rule.h).  The setting ext_stop (default 1) goes to the kernels in the lane's DevScoring, together with the
+// rule's counter block where the rule is counted: the batch seam (always) and the region launches under $BSX_PHASES.  With the switch off and the
+// counters on, the kernels evaluate the rule without obeying it and count the rows that run after it would have fired.
+static std::atomic<uint64_t> g_ext_stops[XS_FAM_N * XS_N];
+static int ext_stop_arm(Lane &L, hipStream_t st, bool count)
+{
+	L.sc.ext_stop = bsx_tune_long("ext_stop", 1) != 0 ? 1 : 0;
+	L.sc.xs_ctr = nullptr;
+	if (!count) return BSX_OK;
+	if (!L.xstop.p) {
+		int rc = L.xstop.reserve(sizeof(unsigned long long) * XS_FAM_N * XS_N);
+		if (rc != BSX_OK) return rc;
+		HIPCHK(hipMemsetAsync(L.xstop.p, 0, sizeof(unsigned long long) * XS_FAM_N * XS_N, st));
+	}
+	L.sc.xs_ctr = (unsigned long long*)L.xstop.p;
+	return BSX_OK;
+}
+// the lane's counters, read, zeroed and added to the process-wide ones; c (may be null) gets this read-out
+static int ext_stop_collect(Lane &L, hipStream_t st, unsigned long long *c)
+{
+	unsigned long long h[XS_FAM_N * XS_N] = {0};
+	if (L.xstop.p) {
+		D2H(st, h, L.xstop.p, sizeof(h));
+		HIPCHK(hipMemsetAsync(L.xstop.p, 0, sizeof(h), st));
+	}
+	for (int k = 0; k < XS_FAM_N * XS_N; ++k) { g_ext_stops[k] += h[k]; if (c) c[k] = h[k]; }
+	return BSX_OK;
+}
+// c[5 * family + {0: extensions stopped, 1: evaluations, 2: rows left at the stops, 3: rows run after a stop that was not obeyed, 4: extensions that
+// would have stopped with the switch off}], families: k_ext4, k_extl, the HBM tiers, chains -> regions, the wavefront-per-job batch form
+// (ext_stop.hpp); c[25] = extensions stopped over all of them
+extern "C" BSX_API int bsx_ext_stops(uint64_t c[26], int reset)
+{
+	if (!c) return BSX_E_ARG;
+	c[XS_FAM_N * XS_N] = 0;
+	for (int k = 0; k < XS_FAM_N * XS_N; ++k) { c[k] = g_ext_stops[k].load(); if (k % XS_N == XS_STOPS) c[XS_FAM_N * XS_N] += c[k]; if (reset) g_ext_stops[k].store(0); }
 	return BSX_OK;
 }
 
@@ -922,6 +963,7 @@ static int rg_plan(RgBatch &B)
 	G.seeds_dense = (const DevIntv*)L.out.p;
 	G.out = (bsx_region_t*)L.regs.p; G.out_cap = B.regs_cap; G.out_cursor = &SH->region_cursor;
 	G.counters = dev_counters(L); G.pos = (unsigned long long*)L.pos.p;
+	TRY(ext_stop_arm(L, L.st, B.trace));   // the stopping rule's switch, and its counters under $BSX_PHASES
 	// once per chunk: reads of at most 256 bases under scoring options whose extension rows fit 16 bits take the packed instantiations
 	G.ext_pk = !B.long_reads && ext_pk_wanted() && ext_pk_scoring(L.sc, 0, B.max_len, true);
 	++g_ext_forms[G.ext_pk ? 0 : 1];
@@ -1377,6 +1419,15 @@ static int rg_report(RgBatch &B)
 	HIPCHK(hipMemsetAsync(ctr + CTR_EXT, 0, sizeof(xp), L.st));
 	if (xp[EXT4_JOBS] || xp[EXTL_JOBS]) fprintf(stderr, "[M::regions_batch] k_ext4: %llu jobs, %llu rows in %llu wave trips (%.2f rows per trip), %llu passes between extensions, %.2f slots per trip, %llu rows of narrow jobs\n", xp[0], xp[1], xp[2], xp[2] ? (double)xp[1] / xp[2] : 0.0, xp[3], xp[2] ? (double)xp[4] / xp[2] : 0.0, xp[5]);
 	if (xp[EXTL_JOBS]) fprintf(stderr, "[M::regions_batch] k_extl: %llu jobs (%llu sent on to k_ext4), %llu rows in %llu wave trips (%.1f rows per trip), %llu passes between extensions\n", xp[6], xp[10], xp[7], xp[8], xp[8] ? (double)xp[7] / xp[8] : 0.0, xp[9]);
+	{ // the extensions' stopping rule (ext_stop_rule.h), per launch family
+		unsigned long long xs[XS_FAM_N * XS_N];
+		int rc = ext_stop_collect(L, L.st, xs);
+		if (rc != BSX_OK) return rc;
+		static const char *fam[XS_FAM_N] = {"k_ext4", "k_extl", "tiers", "k_c2r", "batch"};
+		for (int k = 0; k < XS_FAM_N; ++k) if (xs[XS_N * k + XS_EVALS])
+			fprintf(stderr, "[M::regions_batch] ext_stop=%d %s: %llu extensions stopped by the rule, %llu evaluations, %llu rows still to run at the stops | the switch off: %llu would have stopped, %llu rows run after the rule would have fired\n",
+			        L.sc.ext_stop, fam[k], xs[XS_N * k + XS_STOPS], xs[XS_N * k + XS_EVALS], xs[XS_N * k + XS_LEFT], xs[XS_N * k + XS_WOULD], xs[XS_N * k + XS_DEAD]);
+	}
 	unsigned long long xw[CTR_X4W_N];
 	D2H(L.st, xw, ctr + CTR_X4W, sizeof(xw));
 	HIPCHK(hipMemsetAsync(ctr + CTR_X4W, 0, sizeof(xw), L.st));
@@ -1580,6 +1631,7 @@ static int lane_extend_batch(bsx_device_t *d, int lane, int64_t n, const bsx_ext
 	HIPCHK(hipSetDevice(d->ordinal));
 	if (bsx_tune_is_set("ext4")) { // tests: the batch through the quarter-wave kernel of the regions path (k_ext4.hip); jobs it declines fail the call
 		int rc, max_q = 0;
+		if ((rc = ext_stop_arm(L, L.st, true)) != BSX_OK) return rc;
 		for (int64_t i = 0; i < n; ++i) max_q = std::max(max_q, jobs[i].qlen);
 		if ((max_q > x4_max_query(16) && bsx_tune_long("ext4", 0) != 3) || n > 0x7fffffff) return BSX_E_ARG;
 		if (bsx_tune_long("ext4", 0) == 4) { // ... or the wavefront-per-job form of the region kernels' inline extensions: packed 16-bit rows (ext_dp_pk) when the batch passes the guard, else 32-bit
@@ -1593,6 +1645,8 @@ static int lane_extend_batch(bsx_device_t *d, int lane, int64_t n, const bsx_ext
 			++g_ext_forms[packed ? 0 : 1];
 			HIPCHK(hipGetLastError());
 			D2H(L.st, res, L.res.p, (size_t)n * sizeof(bsx_ext_res_t));
+			if ((rc = ext_stop_collect(L, L.st, nullptr)) != BSX_OK) return rc;
+			L.sc.xs_ctr = nullptr;
 			for (int64_t i = 0; i < n; ++i) if (res[i].score == X4_DECLINED) return BSX_E_ARG;
 			return BSX_OK;
 		}
@@ -1613,9 +1667,12 @@ static int lane_extend_batch(bsx_device_t *d, int lane, int64_t n, const bsx_ext
 		}
 		HIPCHK(hipGetLastError());
 		D2H(L.st, res, L.res.p, (size_t)n * sizeof(bsx_ext_res_t));
+		if ((rc = ext_stop_collect(L, L.st, nullptr)) != BSX_OK) return rc;
+		L.sc.xs_ctr = nullptr;
 		for (int64_t i = 0; i < n; ++i) if (res[i].score == X4_DECLINED) return BSX_E_ARG;
 		return BSX_OK;
 	}
+	// (the classes below run every row: ext_dp and ext_dp_win do not apply the stopping rule)
 	// classes by LDS footprint (query length) and row width (band): {qcap, max band columns, NC}
 	// The host chaining path calls this once per round of its strand searches' extensions -- a thousand rounds of a few hundred jobs for
 	// the reads inside satellite arrays of a repeat-rich genome -- while the front-half kernels of other chunks fill the device.

@@ -41,6 +41,7 @@ struct Lane {
 	int64_t rb_tasks = 0;    // strand searches of the last regions batch (their regions, offsets and counts are still in regs / regmeta)
 	int flt_key[3] = {-1, -1, -1};   // what fltab was made for
 	DevBuf fltab, jobs, res, scratch, scratch2, out, aux, pool, regs, regmeta, slabs, slabs3, slabflags, redo, pos, posoff, xpool, xmeta, x4jobs, tags, mdpool, gctx, qcjobs, qcpool, mdkeys, mdres, mdslot, dd, sswjobs, c2rslab;
+	DevBuf xstop;          // the counters of the extensions' stopping rule (ext_stop.hpp), XS_N words per launch family
 	DevBuf small;          // the counter block: SMALL_BYTES laid out by ctr_layout.hpp
 	HostBuf hstage;        // pinned staging for bulk results
 	HostBuf pin;           // two pinned halves through which large host<->device copies are streamed
@@ -68,7 +69,7 @@ struct Lane {
 	void release_buffers()   // every buffer of the lane but rs.hres; a buffer that is not in this list leaks when the device is closed
 	{
 		DevBuf *b[] = {&reads, &gath, &qpack, &fltab, &jobs, &res, &scratch, &scratch2, &out, &aux, &pool, &regs, &regmeta, &slabs, &slabs3, &slabflags, &redo, &pos, &posoff, &xpool, &xmeta,
-		               &x4jobs, &tags, &mdpool, &gctx, &qcjobs, &qcpool, &mdkeys, &mdres, &mdslot, &dd, &sswjobs, &c2rslab, &small, &msw_jobs, &msw_res, &msw_meta, &msw_roff};
+		               &x4jobs, &tags, &mdpool, &gctx, &qcjobs, &qcpool, &mdkeys, &mdres, &mdslot, &dd, &sswjobs, &c2rslab, &small, &xstop, &msw_jobs, &msw_res, &msw_meta, &msw_roff};
 		for (DevBuf *x : b) x->release();
 		hstage.release(); pin.release(); flt_key[0] = -1;
 	}

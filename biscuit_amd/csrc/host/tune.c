@@ -36,6 +36,7 @@ static knob_t g_knobs[] = {
 	{"ext4", "[off] tests: bsx_extend_batch through the quarter-wave kernel (1) / then the lane-per-job kernel (2) of the regions path / through the wavefront-per-job form with a register window (3) / with the rows of the region kernels' inline extensions, packed 16-bit when the batch allows (4)", 0},
 	{"sw_form", "[off] tests: bsx_sw_batch through the seed filter's alignments, score only, jobs of up to 199 x 199 in the order given -- ssw16: the packed 16-bit kernel (k_swl16), sixteen consecutive jobs to a wavefront, qlen = 0 an empty job; scoring options it cannot hold fail the call / ssw32: a wavefront per job through the 32-bit alignment of a seed without room in the job list", 0},
 	{"ext_pk", "[1] extension rows of 64 columns and more in packed 16-bit, two columns per lane (ext_pk.hpp), where the scoring options keep every intermediate inside 16 bits; 0: always the 32-bit rows", 0},
+	{"ext_stop", "[1] an extension ends once no row it still has to run can change a result field (ext_stop_rule.h); 0: every row runs, as in ksw_extend2 (same results; with phases the rows that would have been saved are counted)", 0},
 	{"chain_stages", "[3] how consecutive chunks' front halves are chained on the device: 0 none, 1 seeding, 2 seeding and regions, 3 the same but the HBM tiers hold nobody back, 4 strictly one after the other", 0},
 	{"small_copies_unmasked", "[1] the front half's copies of less than 256 KB go through the lane's unmasked stream (the CUs the front-half streams leave alone); 0: through the stream they are ordered on", 0},
 	{"reserve_cu_every", "[0] n >= 2: the front-half streams leave one compute unit in n (of every shader engine of every XCD) to the back half's short batches; < 2: none", 0},

@@ -606,6 +606,11 @@ int bsx_device_region_work(bsx_device_t *dev, uint64_t w[5], int reset);
 /* launches since the last reset whose extension rows were c[0] packed 16-bit (two columns per lane; the scoring options keep every
  * intermediate inside 16 bits) / c[1] 32-bit: a chunk of bsx_regions_batch or a bsx_extend_batch under the setting ext4=4 counts once */
 int bsx_ext_forms(uint64_t c[2], int reset);
+/* the extensions' stopping rule (the setting ext_stop) since the last reset, five words per launch family -- k_ext4, k_extl, the HBM
+ * tiers, chains -> regions, the wavefront-per-job batch form: extensions stopped, evaluations of the rule, rows left at the stops, and with
+ * the switch off rows run after the rule would have fired and extensions it would have stopped; c[25] = extensions stopped over all families.
+ * Counted by bsx_extend_batch under the setting ext4 and, with phases on, by the region launches */
+int bsx_ext_stops(uint64_t c[26], int reset);
 /* the seeding kernel's table of k-mer intervals: entries read since the last reset, depth K of the resident table (0: none) */
 int bsx_device_seed_table(bsx_device_t *dev, uint64_t *lookups, int *depth, int reset);
 /* average GPU time (ms, HIP events on the launch stream) and launch count of each kernel since
