@@ -21,7 +21,7 @@ $(BUILD)/host_%.o: biscuit_amd/csrc/host/%.c $(wildcard biscuit_amd/csrc/host/*.
 	@mkdir -p $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(BUILD)/hip_%.o: biscuit_amd/csrc/hip/%.hip $(wildcard biscuit_amd/csrc/hip/*.h) $(wildcard biscuit_amd/csrc/hip/*.hpp) include/bsx.h biscuit_amd/csrc/host/bam_rec.h biscuit_amd/csrc/host/bam.h
+$(BUILD)/hip_%.o: biscuit_amd/csrc/hip/%.hip $(wildcard biscuit_amd/csrc/hip/*.h) $(wildcard biscuit_amd/csrc/hip/*.hpp) include/bsx.h biscuit_amd/csrc/host/bam_rec.h biscuit_amd/csrc/host/bam.h biscuit_amd/csrc/host/c2r_rule.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

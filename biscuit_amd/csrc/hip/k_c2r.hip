@@ -1,5 +1,5 @@
 // k_c2r.hip -- chains -> regions for the strand searches the LDS tiers exported (mem_chain2region + mem_chain2region1, memchain.c:742-904):
-// the same seed loop as stage E of rg_task, over the exported lists.  One wavefront per strand search; nothing but the regions made
+// the seed loop of stage E of rg_task over the exported lists (what the two do with one seed is rg_ext_seed.hpp).  One wavefront per strand search; nothing but the regions made
 // so far, the read, the current chain's seeds and its reference window live in LDS (5.5 KB per wave), so the launch runs at the
 // occupancy the registers allow.
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include "ext_pk.hpp"
 #include "rgx.hpp"
 #include "rg_common.hpp"
+#include "rg_ext_seed.hpp"
 
 #define RG_XSEEDS 128    // seeds of one list (main or seeds_extra) of a chain held in LDS; longer lists: the next tier takes the strand search
 #define RG_XREGS 64      // regions of one strand search (a lane each in the containment test); a read inside a high-copy repeat has dozens
@@ -113,24 +114,17 @@ __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const Reg
 		if (n_main > WT::XSEEDS || n_extra > WT::XSEEDS) return 2;
 		if (seed_off + n_main > sd_hi) { WAVE_SYNC(); C2R_STAGE_SEEDS(seed_off); WAVE_SYNC(); }
 		// mem_chain_reference_span (memchain.c:585-605) over the main list + bns_fetch_seq's contig clamp
-		long long rmax0 = l_pac << 1, rmax1 = 0;
+		int64_t rmax0 = l_pac << 1, rmax1 = 0;
 		for (int o = lane; o < n_main; o += 64) {
 			const RgXSeed sd = W.sd[seed_off - sd_lo + o];
-			const long long b = sd.rbeg - (sd.qbeg + rg_gap(gap, P, sd.qbeg));
-			const long long e = sd.rbeg + sd.len + ((l_query - sd.qbeg - sd.len) + rg_gap(gap, P, l_query - sd.qbeg - sd.len));
+			int64_t b, e;
+			c2r_seed_span(sd.rbeg, sd.qbeg, sd.len, l_query, rg_gap(gap, P, sd.qbeg), rg_gap(gap, P, l_query - sd.qbeg - sd.len), &b, &e);
 			rmax0 = rmax0 < b ? rmax0 : b; rmax1 = rmax1 > e ? rmax1 : e;
 		}
 		if (n_main == 1) { // most chains are one seed: lane 0 holds the span
 			rmax0 = uni64(rmax0); rmax1 = uni64(rmax1);
 		} else { rmax0 = uni64(-wave_max_i64(-rmax0)); rmax1 = uni64(wave_max_i64(rmax1)); }
-		rmax0 = rmax0 > 0 ? rmax0 : 0; rmax1 = rmax1 < l_pac << 1 ? rmax1 : l_pac << 1;
-		if (rmax0 < l_pac && l_pac < rmax1) { if (ch_pos < l_pac) rmax1 = l_pac; else rmax0 = l_pac; }
-		{
-			const int is_rev = ch_pos >= l_pac;
-			long long far_beg = uni64(ctg[rid]), far_end = uni64(ctg[rid + 1]);
-			if (is_rev) { const long long tmp = far_beg; far_beg = (l_pac << 1) - far_end; far_end = (l_pac << 1) - tmp; }
-			rmax0 = rmax0 > far_beg ? rmax0 : far_beg; rmax1 = rmax1 < far_end ? rmax1 : far_end;
-		}
+		c2r_clamp_window(&rmax0, &rmax1, l_pac, ch_pos, uni64(ctg[rid]), uni64(ctg[rid + 1]));
 		const int n0 = uni(W.n_regs);
 		int win_ok = 0;
 		for (int pass = 0; pass < 2; ++pass) {
@@ -152,53 +146,20 @@ __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const Reg
 				if (uni(XS_BAD(sd))) continue;   // asymmetric_flt_seed (memchain.c:138-149), tested by the tier that exported the seed
 				const long long s_rbeg = uni64(sd.rbeg); const int s_qbeg = uni((int)sd.qbeg), s_len = uni((int)sd.len);
 				++pf_seen;
-				// contained in a region of this strand search? (memchain.c:761-819)
-				int u;
+				// contained in a region of this strand search, and no later seed of the list disagrees? (memchain.c:761-819)
+				const auto seed_at = [&](int i, long long &t_rbeg, int &t_qbeg, int &t_len) { const RgXSeed td = Lsd[i]; t_rbeg = td.rbeg; t_qbeg = td.qbeg; t_len = td.len; };
 				const int nr = uni(W.n_regs);
-				u = nr;
-				for (int rbase = 0; rbase < nr && u == nr; rbase += 64) { // a lane per region made so far, 64 at a time: the reference's loop stops at the first region that passes
-					bool hit = false;
-					if (rbase + lane < nr) {
-						const bsx_region_t &rg = W.regs[rbase + lane];
-						if (!(s_rbeg < rg.rb || s_rbeg + s_len > rg.re || s_qbeg < rg.qb || s_qbeg + s_len > rg.qe) && !(s_len - rg.seedlen0 > .1 * l_query)) {
-							int qd = s_qbeg - rg.qb; long long rd = s_rbeg - rg.rb;
-							int max_gap = rg_gap(gap, P, (int)(qd < rd ? qd : rd));
-							int w = max_gap < rg.w ? max_gap : rg.w;
-							hit = qd - rd < w && rd - qd < w;
-							qd = rg.qe - (s_qbeg + s_len); rd = rg.re - (s_rbeg + s_len);
-							max_gap = rg_gap(gap, P, (int)(qd < rd ? qd : rd));
-							w = max_gap < rg.w ? max_gap : rg.w;
-							hit = hit || (qd - rd < w && rd - qd < w);
-						}
+				const int u = rg_first_container(W.regs, nr, s_rbeg, s_qbeg, s_len, l_query, gap, P, lane);
+				if (u < nr && !rg_later_disagrees(W.srt, k, nl, s_rbeg, s_qbeg, s_len, lane, seed_at)) {
+					// the chain's extension was made ahead and is never read: this is the seed k_x4prep chose (the first one the loop reaches in the main list)
+					if constexpr (TALLY) if (has_ext == 1 && pass == 0 && uni(W.xe[ci - xc_lo].status) == 1 && uni(W.xe[ci - xc_lo].si) == si) {
+						const unsigned long long at = (unsigned long long)((const unsigned char*)(XEw + (size_t)ci * (sizeof(RgXExt) / 8)) - X.base);
+						const unsigned int rw = (unsigned int)uni((int)((const unsigned int*)(X.base + rgx_rows_offset(X.cap)))[RGX_ROWS_AT(at)]);
+						const unsigned long long rows = rw & ~RGX_ROWS_L;
+						const unsigned long long v = lane == X4W_JOBS ? 1ull : lane == X4W_ROWS ? rows : u != 0 ? 0ull : lane == X4W_JOBS_R0 ? 1ull : rows;
+						if (lane < 4 && v) atomicAdd(&counters[CTR_X4W + ((rw & RGX_ROWS_L) ? 4 : 0) + lane], v);
 					}
-					const unsigned long long hm = __ballot(hit);
-					if (hm) u = rbase + (int)__builtin_ctzll(hm);
-				}
-				if (u < nr) { // is there a later seed of the list (in sorted order) that may lead to a different alignment?  A lane per seed
-					bool any = false;
-					for (int base = k + 1; base < nl && !any; base += 64) {
-						const int i = base + lane;
-						bool alt = false;
-						if (i < nl && W.srt[i] != 0) {
-							const RgXSeed td = Lsd[(int)(uint32_t)W.srt[i]];
-							const long long t_rbeg = td.rbeg; const int t_qbeg = td.qbeg, t_len = td.len;
-							if (!(t_len < s_len * .95))
-								alt = (s_qbeg <= t_qbeg && s_qbeg + s_len - t_qbeg >= s_len >> 2 && t_qbeg - s_qbeg != t_rbeg - s_rbeg) ||
-								      (t_qbeg <= s_qbeg && t_qbeg + t_len - s_qbeg >= s_len >> 2 && s_qbeg - t_qbeg != s_rbeg - t_rbeg);
-						}
-						any = __ballot(alt) != 0;
-					}
-					if (!any) {
-						// the chain's extension was made ahead and is never read: this is the seed k_x4prep chose (the first one the loop reaches in the main list)
-						if constexpr (TALLY) if (has_ext == 1 && pass == 0 && uni(W.xe[ci - xc_lo].status) == 1 && uni(W.xe[ci - xc_lo].si) == si) {
-							const unsigned long long at = (unsigned long long)((const unsigned char*)(XEw + (size_t)ci * (sizeof(RgXExt) / 8)) - X.base);
-							const unsigned int rw = (unsigned int)uni((int)((const unsigned int*)(X.base + rgx_rows_offset(X.cap)))[RGX_ROWS_AT(at)]);
-							const unsigned long long rows = rw & ~RGX_ROWS_L;
-							const unsigned long long v = lane == X4W_JOBS ? 1ull : lane == X4W_ROWS ? rows : u != 0 ? 0ull : lane == X4W_JOBS_R0 ? 1ull : rows;
-							if (lane < 4 && v) atomicAdd(&counters[CTR_X4W + ((rw & RGX_ROWS_L) ? 4 : 0) + lane], v);
-						}
-						++pf_skip; WAVE_SYNC(); if (lane == 0) W.srt[k] = 0; WAVE_SYNC(); continue;
-					}
+					++pf_skip; WAVE_SYNC(); if (lane == 0) W.srt[k] = 0; WAVE_SYNC(); continue;
 				}
 				// extension (memchain.c:613-730): left then right, each with up to MAX_BAND_TRY band widths -- taken from the record when this
 				// is the seed k_ext4 extended ahead of the loop (the first one the loop reaches in a chain's main list)
@@ -221,79 +182,22 @@ __device__ int rg_c2r(WT &W, const DevIndex &ix, const DevScoring &sc, const Reg
 						WAVE_SYNC();
 					} else win_ok = -1;
 				}
-				bsx_region_t R; memset(&R, 0, sizeof(R));
-				int aw0 = P.w, aw1 = P.w;
-				const int qe = s_qbeg + s_len;
-				R.score = R.truesc = -1; R.rid = rid;
+				bsx_region_t R; int aw0, aw1;
+				rg_region_open(R, aw0, aw1, P.w, rid);
 				if (cached) {
 					R.rb = uni64(xe.rb); R.re = uni64(xe.re); R.qb = uni(xe.qb); R.qe = uni(xe.qe); R.score = uni(xe.score); R.truesc = uni(xe.truesc);
 					aw0 = uni(xe.aw0); aw1 = uni(xe.aw1);
-				} else
-				for (int side = 0; side < 2; ++side) {
-					if (side == 0 && s_qbeg == 0) { R.score = R.truesc = s_len * P.a; R.qb = 0; R.rb = s_rbeg; continue; }
-					if (side == 1 && qe == l_query) { R.qe = l_query; R.re = s_rbeg + s_len; continue; }
-					const int sc0 = R.score, clip = side ? P.pen_clip3 : P.pen_clip5;
-					int aw = P.w;
-					bsx_ext_res_t res; res.score = -1; res.qle = res.tle = res.gtle = 0; res.gscore = -1; res.max_off = 0;
-					bsx_ext_job_t J;
-					J.parent = (uint8_t)parent; J.pad = 0; J.end_bonus = clip;
-					if (side == 0) { J.qoff = qoff + (uint32_t)s_qbeg - 1; J.qdir = -1; J.qlen = s_qbeg; J.tpos = s_rbeg - 1; J.tdir = -1; J.tlen = (int)(s_rbeg - rmax0); J.h0 = s_len * P.a; }
-					else { J.qoff = qoff + (uint32_t)qe; J.qdir = 1; J.qlen = l_query - qe; J.tpos = s_rbeg + s_len; J.tdir = 1; J.tlen = (int)(rmax1 - (s_rbeg + s_len)); J.h0 = sc0; }
-					for (int i = 0; i < 2; ++i) {
-						const int prev = R.score;
-						aw = P.w << i;
-						J.w = aw;
-						if (P.prof) { const long long now_ = (long long)__builtin_readcyclecounter(); RG_PF_ADD(W, 6, now_ - pf_t); pf_t = now_; }
-						// rows in registers, 64 entries per lane slot: as few slots as the query needs (a row's cost grows with them)
-						constexpr int XC = TALLY ? XS_FAM_C2R : -1;   // ($BSX_PHASES: the stopping rule counted, ext_stop.hpp)
-						if (J.qlen < 64) res = ext_dp_reg<1, XC>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
-						else if constexpr (PK && WT::QCAP <= 256) {
-							if (J.qlen < 128) res = ext_dp_pk<1, XC>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
-							else res = ext_dp_pk<2, XC>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
-						}
-						else if (J.qlen < 128) res = ext_dp_reg<2, XC>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
-						else if (WT::QCAP <= 256 || J.qlen < 256) res = ext_dp_reg<RG_NC, XC>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);
-						else if (P.ext_win && 2 * J.w + 1 <= 256 && (long long)J.h0 + (long long)J.qlen * (parent ? sc.mx_ct : sc.mx_ga) < (1 << 21))
-							res = ext_dp_win<5>(ix, sc, reads, J, lane, win_ok > 0 ? W.win : nullptr, rmax0, W.q, qoff);   // rows in five register slots that follow the band (round 6)
-						else if (WT::ROWS && 2 * J.w + 1 <= 512) { WAVE_SYNC(); res = ext_dp<8>(ix, sc, reads, J, W.Hrow, W.Erow, W.qrow, lane); }   // rows in LDS, the band (<= 8 x 64 columns) in registers
-						else return 2;   // (-w above 127 with reads beyond 256 bases: left to the caller's batch kernels)
-						res.score = uni(res.score); res.qle = uni(res.qle); res.tle = uni(res.tle); res.gtle = uni(res.gtle);
-						res.gscore = uni(res.gscore); res.max_off = uni(res.max_off);
-						R.score = res.score;
-						if (P.prof) { const long long now_ = (long long)__builtin_readcyclecounter(); RG_PF_ADD(W, 7, now_ - pf_t); pf_t = now_; }
-						++pf_ext; pf_rows += (unsigned int)(res.tle > res.gtle ? res.tle : res.gtle);
-						if (P.prof && J.qlen >= 64) RG_PF_ADD(W, 15, (unsigned long long)(res.tle > res.gtle ? res.tle : res.gtle) << (J.qlen >= 128 ? 32 : 0));
-						if (R.score == prev || res.max_off < (aw >> 1) + (aw >> 2)) break;
-					}
-					const int local = res.gscore <= 0 || res.gscore <= R.score - clip;
-					if (side == 0) {
-						aw0 = aw;
-						if (local) { R.qb = s_qbeg - res.qle; R.rb = s_rbeg - res.tle; R.truesc = R.score; }
-						else { R.qb = 0; R.rb = s_rbeg - res.gtle; R.truesc = res.gscore; }
-					} else {
-						aw1 = aw;
-						if (local) { R.qe = qe + res.qle; R.re = s_rbeg + s_len + res.tle; R.truesc += R.score - sc0; }
-						else { R.qe = l_query; R.re = s_rbeg + s_len + res.gtle; R.truesc += res.gscore - sc0; }
-					}
+				} else {
+					constexpr int XC = TALLY ? XS_FAM_C2R : -1;   // ($BSX_PHASES: the stopping rule counted, ext_stop.hpp)
+					const int st = rg_ext_seed<PK, WT::QCAP, WT::ROWS, XC>(R, aw0, aw1, W, ix, sc, P, reads, qoff, l_query, parent, s_rbeg, s_qbeg, s_len, rmax0, rmax1, win_ok, lane, pf_t, pf_ext, pf_rows);
+					if (st) return st;
 				}
-				R.bss = (uint8_t)RG_BSS(parent, l_pac, R.rb); R.parent = (uint8_t)parent;
-				if (RG_BSS(parent, l_pac, R.re) != R.bss) continue;   // crosses the strand boundary (memchain.c:846-849)
-				int cov = 0;
-				for (int i = lane; i < nl; i += 64) {
-					const RgXSeed td = Lsd[i];
-					if (td.qbeg >= R.qb && td.qbeg + td.len <= R.qe && td.rbeg >= R.rb && td.rbeg + td.len <= R.re) cov += td.len;
-				}
-				R.seedcov = uni(wave_sum_i32(cov));
-				R.w = aw0 > aw1 ? aw0 : aw1; R.seedlen0 = s_len; R.frac_rep = frac_rep;
-				if (uni(W.n_regs) == WT::XREGS) return 6;
-				WAVE_SYNC();
-				if (lane == 0) { W.regs[W.n_regs] = R; ++W.n_regs; }
-				WAVE_SYNC();
+				if (rg_push_region(R, aw0, aw1, s_len, frac_rep, parent, l_pac, nl, seed_at, W.regs, W.n_regs, WT::XREGS, lane)) return 6;
 			}
 		}
 	}
-	if (P.prof) { RG_PF_ADD(W, 6, (long long)__builtin_readcyclecounter() - pf_t); RG_PF_ADD(W, 8, pf_ext); RG_PF_ADD(W, 9, pf_rows);
-	              RG_PF_ADD(W, 11, pf_seen); RG_PF_ADD(W, 12, pf_skip); RG_PF_ADD(W, 13, pf_cached); RG_PF_ADD(W, 14, pf_inl); }
+	RG_PF_STAGE(W, 6, pf_t);
+	if (P.prof) { RG_PF_ADD(W, 8, pf_ext); RG_PF_ADD(W, 9, pf_rows); RG_PF_ADD(W, 11, pf_seen); RG_PF_ADD(W, 12, pf_skip); RG_PF_ADD(W, 13, pf_cached); RG_PF_ADD(W, 14, pf_inl); }
 	return 0;
 #undef C2R_STAGE_CHAINS
 #undef C2R_STAGE_SEEDS

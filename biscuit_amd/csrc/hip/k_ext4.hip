@@ -29,6 +29,7 @@
 #include "wave.hpp"
 #include "kernels.h"
 #include "tune.h"
+#include "c2r_rule.h"
 #include "rgx.hpp"
 #include "x4.hpp"
 #include "ext_stop.hpp"
@@ -74,7 +75,7 @@ k_x4prep(DevIndex ix, RegParams P, const bsx_seed_task_t *tasks, RgXPool X, X4Jo
 		// the lane's chain: its window, and which of its seeds get a job -- the one the loop reaches first (has_ext 1), or every seed of the main
 		// list that passes asymmetric_flt_seed (has_ext 2); then the jobs, one per lane per round
 		int n_it = 0, mode = 0, best = -1, ci = 0, l_query = 0, parent = 0, s = 0;
-		long long rmax0 = 0, rmax1 = 0;
+		int64_t rmax0 = 0, rmax1 = 0;
 		const RgXSeed *XS = nullptr; RgXExt *XE = nullptr; RgXChain c; c.pos = 0; c.rid = 0; c.seed_off = 0; c.n_main = c.n_extra = 0; c.pad = 0;
 		RgXExt xe0; xe0.rb = xe0.re = 0; xe0.qb = xe0.qe = 0; xe0.score = xe0.truesc = -1; xe0.aw0 = xe0.aw1 = P.w; xe0.si = -1; xe0.status = 0;
 		if (j < tot) {
@@ -100,21 +101,14 @@ k_x4prep(DevIndex ix, RegParams P, const bsx_seed_task_t *tasks, RgXPool X, X4Jo
 				long long bkey = -1;
 				for (int o = 0; o < n_main; ++o) {
 					const RgXSeed sd = XS[c.seed_off + o];
-					const long long bb = sd.rbeg - (sd.qbeg + rg_gap(gap_tab, P, sd.qbeg));
-					const long long ee = sd.rbeg + sd.len + ((l_query - sd.qbeg - sd.len) + rg_gap(gap_tab, P, l_query - sd.qbeg - sd.len));
+					int64_t bb, ee;
+					c2r_seed_span(sd.rbeg, sd.qbeg, sd.len, l_query, rg_gap(gap_tab, P, sd.qbeg), rg_gap(gap_tab, P, l_query - sd.qbeg - sd.len), &bb, &ee);
 					rmax0 = rmax0 < bb ? rmax0 : bb; rmax1 = rmax1 > ee ? rmax1 : ee;
 					const long long key = (long long)((unsigned long long)(unsigned)XS_SCORE(sd) << 32 | (unsigned)o);
 					if (!XS_BAD(sd) && key > bkey) { bkey = key; best = o; }
 				}
 				if (best >= 0) {
-					rmax0 = rmax0 > 0 ? rmax0 : 0; rmax1 = rmax1 < l_pac << 1 ? rmax1 : l_pac << 1;
-					if (rmax0 < l_pac && l_pac < rmax1) { if (c.pos < l_pac) rmax1 = l_pac; else rmax0 = l_pac; }
-					{
-						const int is_rev = c.pos >= l_pac;
-						long long far_beg = ix.ctg_off[c.rid], far_end = ix.ctg_off[c.rid + 1];
-						if (is_rev) { const long long tmp = far_beg; far_beg = (l_pac << 1) - far_end; far_end = (l_pac << 1) - tmp; }
-						rmax0 = rmax0 > far_beg ? rmax0 : far_beg; rmax1 = rmax1 < far_end ? rmax1 : far_end;
-					}
+					c2r_clamp_window(&rmax0, &rmax1, l_pac, c.pos, ix.ctg_off[c.rid], ix.ctg_off[c.rid + 1]);
 					n_it = mode == 2 ? n_main : 1;
 				}
 			}
@@ -247,7 +241,7 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 	long long s_rbeg = 0, rmax0 = 0, rmax1 = 0; unsigned long long ext_at = 0;
 	unsigned int qoff0 = 0; int l_query = 0, s_qbeg = 0, s_len = 0, par = 0, si = 0;
 	int side = 0, attempt = 0, prev = 0, sc0 = 0, aw = 0, clip = 0;
-	int R_qb = 0, R_qe = 0, R_score = 0, R_truesc = 0, aw0 = 0, aw1 = 0; long long R_rb = 0, R_re = 0;
+	int R_qb = 0, R_qe = 0, R_score = 0, R_truesc = 0, aw0 = 0, aw1 = 0; int64_t R_rb = 0, R_re = 0;
 	// the extension under way
 	unsigned int jq = 0; int jqdir = 1, jtdir = 1, jbonus = 0; long long jtpos = 0;
 	int qlen = 0, tlen = 0, h0 = 0, w = 0, i = 0, beg = 0, end = 0;
@@ -287,18 +281,10 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 						// the band loop (memchain.c:640-667,698-725): once more with twice the band when the score changed and the alignment
 						// strayed beyond three quarters of it
 						R_score = r_score;
-						if (attempt == 0 && !(R_score == prev || r_off < (aw >> 1) + (aw >> 2))) { attempt = 1; st = X4_NEXT; }
+						if (attempt == 0 && c2r_band_again(R_score, prev, r_off, aw)) { attempt = 1; st = X4_NEXT; }
 						else {
-							const int local = r_gscore <= 0 || r_gscore <= R_score - clip;
-							if (side == 0) {
-								aw0 = aw;
-								if (local) { R_qb = s_qbeg - r_qle; R_rb = s_rbeg - r_tle; R_truesc = R_score; }
-								else { R_qb = 0; R_rb = s_rbeg - r_gtle; R_truesc = r_gscore; }
-							} else {
-								aw1 = aw;
-								if (local) { R_qe = s_qbeg + s_len + r_qle; R_re = s_rbeg + s_len + r_tle; R_truesc += R_score - sc0; }
-								else { R_qe = l_query; R_re = s_rbeg + s_len + r_gtle; R_truesc += r_gscore - sc0; }
-							}
+							if (side == 0) aw0 = aw; else aw1 = aw;
+							c2r_side_settle(side, R_score, r_qle, r_tle, r_gtle, r_gscore, clip, sc0, s_rbeg, s_qbeg, s_len, l_query, &R_qb, &R_rb, &R_qe, &R_re, &R_truesc);
 							++side; attempt = 0; st = X4_NEXT;
 						}
 					}
@@ -306,8 +292,8 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 				// a job's next step: sides that need no extension (memchain.c:617-623,674-678), the end of the job
 				auto x4_step = [&]() {
 					if (CHAIN && st == X4_NEXT && attempt == 0) {
-						if (side == 0 && s_qbeg == 0) { R_score = R_truesc = s_len * P.a; R_qb = 0; R_rb = s_rbeg; side = 1; }
-						if (side == 1 && s_qbeg + s_len == l_query) { R_qe = l_query; R_re = s_rbeg + s_len; side = 2; }
+						if (side == 0 && c2r_side_trivial(0, s_rbeg, s_qbeg, s_len, l_query, P.a, &R_qb, &R_rb, &R_qe, &R_re, &R_score, &R_truesc)) side = 1;
+						if (side == 1 && c2r_side_trivial(1, s_rbeg, s_qbeg, s_len, l_query, P.a, &R_qb, &R_rb, &R_qe, &R_re, &R_score, &R_truesc)) side = 2;
 						if (side >= 2) {
 							if (l == 0) {
 								RgXExt xe; xe.rb = R_rb; xe.re = R_re; xe.qb = R_qb; xe.qe = R_qe; xe.score = R_score; xe.truesc = R_truesc;
@@ -360,14 +346,12 @@ k_ext4(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, const void
 				if (st == X4_NEXT) { // the next extension of the job
 					const bool go = true;
 					if (CHAIN) {
-						const int qe = s_qbeg + s_len;
 						prev = R_score;
 						if (attempt == 0) sc0 = R_score;
 						aw = P.w << attempt;
-						clip = side ? P.pen_clip3 : P.pen_clip5;
-						jbonus = clip;
-						if (side == 0) { jq = qoff0 + (unsigned int)s_qbeg - 1; jqdir = -1; qlen = s_qbeg; jtpos = s_rbeg - 1; jtdir = -1; tlen = (int)(s_rbeg - rmax0); h0 = s_len * P.a; }
-						else { jq = qoff0 + (unsigned int)qe; jqdir = 1; qlen = l_query - qe; jtpos = s_rbeg + s_len; jtdir = 1; tlen = (int)(rmax1 - (s_rbeg + s_len)); h0 = sc0; }
+						const c2r_job_t j = c2r_side_job(side, qoff0, s_rbeg, s_qbeg, s_len, l_query, rmax0, rmax1, P.a, sc0, P.pen_clip5, P.pen_clip3);
+						clip = jbonus = j.end_bonus;
+						jq = j.qoff; jqdir = j.qdir; qlen = j.qlen; jtpos = j.tpos; jtdir = j.tdir; tlen = j.tlen; h0 = j.h0;
 					}
 					if (go) {
 						const int mx = par ? sc.mx_ct : sc.mx_ga;

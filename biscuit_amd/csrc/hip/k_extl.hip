@@ -22,6 +22,7 @@
 #include "rgx.hpp"
 #include "x4.hpp"
 #include "ext_stop.hpp"
+#include "c2r_rule.h"
 
 #define XL_W 64          // window positions (registers)
 #define XL_QCOLS 128     // query columns whose bases a lane holds (2 bits each, 8 registers)
@@ -62,7 +63,7 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 	long long s_rbeg = 0, rmax0 = 0, rmax1 = 0; unsigned long long ext_at = 0;
 	unsigned int qoff0 = 0; int l_query = 0, s_qbeg = 0, s_len = 0, par = 0, si = 0;
 	int side = 0, attempt = 0, prev = 0, sc0 = 0, aw = 0, clip = 0;
-	int R_qb = 0, R_qe = 0, R_score = 0, R_truesc = 0, aw0 = 0, aw1 = 0; long long R_rb = 0, R_re = 0;
+	int R_qb = 0, R_qe = 0, R_score = 0, R_truesc = 0, aw0 = 0, aw1 = 0; int64_t R_rb = 0, R_re = 0;
 	// the extension under way
 	int qlen = 0, tlen = 0, h0 = 0, w = 0, i = 0, beg = 0, end = 0, base = 0;
 	long long tF = 0; int tfd = 1, tcomp = 0, yleft = 0;
@@ -105,26 +106,18 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 						((bsx_ext_res_t*)res_)[e] = r;
 						st = XL_IDLE;
 					} else
-					if (attempt == 0 && !(R_score == prev || r_off < (aw >> 1) + (aw >> 2))) { attempt = 1; st = XL_NEXT; }
+					if (attempt == 0 && c2r_band_again(R_score, prev, r_off, aw)) { attempt = 1; st = XL_NEXT; }
 					else {
-						const int local = r_gscore <= 0 || r_gscore <= R_score - clip;
-						if (side == 0) {
-							aw0 = aw;
-							if (local) { R_qb = s_qbeg - r_qle; R_rb = s_rbeg - r_tle; R_truesc = R_score; }
-							else { R_qb = 0; R_rb = s_rbeg - r_gtle; R_truesc = r_gscore; }
-						} else {
-							aw1 = aw;
-							if (local) { R_qe = s_qbeg + s_len + r_qle; R_re = s_rbeg + s_len + r_tle; R_truesc += R_score - sc0; }
-							else { R_qe = l_query; R_re = s_rbeg + s_len + r_gtle; R_truesc += r_gscore - sc0; }
-						}
+						if (side == 0) aw0 = aw; else aw1 = aw;
+						c2r_side_settle(side, R_score, r_qle, r_tle, r_gtle, r_gscore, clip, sc0, s_rbeg, s_qbeg, s_len, l_query, &R_qb, &R_rb, &R_qe, &R_re, &R_truesc);
 						++side; attempt = 0; st = XL_NEXT;
 					}
 				}
 				// a job's next step: sides that need no extension (memchain.c:617-623,674-678), the end of the job
 				auto xl_step = [&]() {
 					if (CHAIN && st == XL_NEXT && attempt == 0) {
-						if (side == 0 && s_qbeg == 0) { R_score = R_truesc = s_len * P.a; R_qb = 0; R_rb = s_rbeg; side = 1; }
-						if (side == 1 && s_qbeg + s_len == l_query) { R_qe = l_query; R_re = s_rbeg + s_len; side = 2; }
+						if (side == 0 && c2r_side_trivial(0, s_rbeg, s_qbeg, s_len, l_query, P.a, &R_qb, &R_rb, &R_qe, &R_re, &R_score, &R_truesc)) side = 1;
+						if (side == 1 && c2r_side_trivial(1, s_rbeg, s_qbeg, s_len, l_query, P.a, &R_qb, &R_rb, &R_qe, &R_re, &R_score, &R_truesc)) side = 2;
 						if (side >= 2) {
 							RgXExt xe; xe.rb = R_rb; xe.re = R_re; xe.qb = R_qb; xe.qe = R_qe; xe.score = R_score; xe.truesc = R_truesc;
 							xe.aw0 = aw0; xe.aw1 = aw1; xe.si = si; xe.status = 1;
@@ -187,16 +180,15 @@ k_extl(DevIndex ix, DevScoring sc, RegParams P, const uint8_t *reads, void *jobs
 				}
 				xl_step();
 				if (st == XL_NEXT) { // the next extension of the job
-					const int qe = s_qbeg + s_len;
 					unsigned int jq; int jqdir, jtdir; long long jtpos;
 					if (!CHAIN) { jq = bq; jqdir = bqdir; jtdir = btdir; jtpos = btpos; }
 					else {
-					prev = R_score;
-					if (attempt == 0) sc0 = R_score;
-					aw = P.w << attempt;
-					clip = side ? P.pen_clip3 : P.pen_clip5;
-					if (side == 0) { jq = qoff0 + (unsigned int)s_qbeg - 1; jqdir = -1; qlen = s_qbeg; jtpos = s_rbeg - 1; jtdir = -1; tlen = (int)(s_rbeg - rmax0); h0 = s_len * P.a; }
-					else { jq = qoff0 + (unsigned int)qe; jqdir = 1; qlen = l_query - qe; jtpos = s_rbeg + s_len; jtdir = 1; tlen = (int)(rmax1 - (s_rbeg + s_len)); h0 = sc0; }
+						prev = R_score;
+						if (attempt == 0) sc0 = R_score;
+						aw = P.w << attempt;
+						const c2r_job_t j = c2r_side_job(side, qoff0, s_rbeg, s_qbeg, s_len, l_query, rmax0, rmax1, P.a, sc0, P.pen_clip5, P.pen_clip3);
+						clip = j.end_bonus;
+						jq = j.qoff; jqdir = j.qdir; qlen = j.qlen; jtpos = j.tpos; jtdir = j.tdir; tlen = j.tlen; h0 = j.h0;
 					}
 					const int mx = par ? sc.mx_ct : sc.mx_ga;
 					// the first row's non-zero entries: 0 .. jmax0 (ksw.c:395-397); they have to end inside the first window

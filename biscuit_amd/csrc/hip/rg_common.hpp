@@ -80,6 +80,7 @@ typedef RgStore<4096, 8192, 8192, 8192, 8192, unsigned short, short> RgHuge;   /
 #define RG_NPF 16            // 0-7 stage cycles, 8 extensions, 9 extension rows
 #define RG_PF_ZERO(D) do { if (P.prof) { (D).pf[lane & (RG_NPF - 1)] = 0; WAVE_SYNC(); } } while (0)
 #define RG_PF_ADD(D, k, v) do { const unsigned long long s_ = (D).pf[k] + (unsigned long long)(v); (D).pf[k] = s_; } while (0)
+#define RG_PF_STAGE(D, k, pf_t) do { if (P.prof) { const long long now_ = (long long)__builtin_readcyclecounter(); RG_PF_ADD(D, k, now_ - (pf_t)); (pf_t) = now_; } } while (0)   // the cycles since the last stamp go to sum k
 #define RG_PF_FLUSH(D) do { if (P.prof) { WAVE_SYNC(); if (lane < RG_NPF) { const unsigned long long v_ = (D).pf[lane]; if (v_) atomicAdd(&counters[CTR_STAGE + lane], v_); } } } while (0)
 struct RgDp {            // per-wave LDS scratch
 	static const int QCAP = RG_QCAP;

@@ -12,6 +12,7 @@
 #include "ext_pk.hpp"
 #include "rgx.hpp"
 #include "rg_common.hpp"
+#include "rg_ext_seed.hpp"
 
 // asymmetric_flt_seed (memchain.c:138-149) for the seed of `ln` bases at reference position rb (forward-reverse space) whose read bases are q[0, ln): a
 // reference T under a read C or a reference A under a read G.  The reference bases come 32 at a time (one unaligned 8-byte load of pac: a chance
@@ -306,7 +307,7 @@ __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc
 	// per-stage wave cycles (P.prof, set under $BSX_PHASES) into the wave's sums D.pf, see RG_PF_ADD
 	long long pf_t = P.prof ? (long long)__builtin_readcyclecounter() : 0;
 	unsigned int pf_ext = 0, pf_rows = 0;
-#define RG_STAGE(k) do { if (P.prof) { const long long now_ = (long long)__builtin_readcyclecounter(); RG_PF_ADD(D, k, now_ - pf_t); pf_t = now_; } } while (0)
+#define RG_STAGE(k) RG_PF_STAGE(D, k, pf_t)
 	if (lane == 0) {
 		S.n_chains = 0; S.n_regs = 0;
 		if (Store::NODES) { S.n_nodes = 0; S.root = rg_bt_alloc(S, 0); }
@@ -943,30 +944,21 @@ __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc
 		// most chains of a strand search against the wrong conversion are such
 		if (single && !ch_has_extra && (uni(S.s_extra[seed0]) & 2)) continue;
 		// mem_chain_reference_span (memchain.c:585-605) + bns_fetch_seq's contig clamp; one lane per seed
-		long long rmax0 = l_pac << 1, rmax1 = 0;
+		int64_t rmax0 = l_pac << 1, rmax1 = 0;
 		if (single) {
 			const long long rb = uni64(S.s_rbeg[seed0]); const int qb = uni(S.s_qbeg[seed0]), ln = uni(S.s_len[seed0]);
-			rmax0 = rb - (qb + rg_gap(gap, P, qb));
-			rmax1 = rb + ln + ((l_query - qb - ln) + rg_gap(gap, P, l_query - qb - ln));
+			c2r_seed_span(rb, qb, ln, l_query, rg_gap(gap, P, qb), rg_gap(gap, P, l_query - qb - ln), &rmax0, &rmax1);
 		} else {
 			for (int o = lane; o < ns; o += 64) if (S.s_chain[o] == c && !(S.s_extra[o] & 1)) {
 				const long long rb = S.s_rbeg[o]; const int qb = S.s_qbeg[o], ln = S.s_len[o];
-				const long long b = rb - (qb + rg_gap(gap, P, qb));
-				const long long e = rb + ln + ((l_query - qb - ln) + rg_gap(gap, P, l_query - qb - ln));
+				int64_t b, e;
+				c2r_seed_span(rb, qb, ln, l_query, rg_gap(gap, P, qb), rg_gap(gap, P, l_query - qb - ln), &b, &e);
 				rmax0 = rmax0 < b ? rmax0 : b; rmax1 = rmax1 > e ? rmax1 : e;
 			}
 			rmax0 = uni64(-wave_max_i64(-rmax0)); rmax1 = uni64(wave_max_i64(rmax1));
 		}
-		rmax0 = rmax0 > 0 ? rmax0 : 0; rmax1 = rmax1 < l_pac << 1 ? rmax1 : l_pac << 1;
-		if (rmax0 < l_pac && l_pac < rmax1) { if (ch_pos < l_pac) rmax1 = l_pac; else rmax0 = l_pac; }
-		int rid;
-		{
-			const int is_rev = ch_pos >= l_pac;
-			rid = uni(chn.rid);   // a chain's seeds share the contig of its first one (memchain.c:232)
-			long long far_beg = uni64(ctg[rid]), far_end = uni64(ctg[rid + 1]);
-			if (is_rev) { const long long tmp = far_beg; far_beg = (l_pac << 1) - far_end; far_end = (l_pac << 1) - tmp; }
-			rmax0 = rmax0 > far_beg ? rmax0 : far_beg; rmax1 = rmax1 < far_end ? rmax1 : far_end;
-		}
+		const int rid = uni(chn.rid);   // a chain's seeds share the contig of its first one (memchain.c:232)
+		c2r_clamp_window(&rmax0, &rmax1, l_pac, ch_pos, uni64(ctg[rid]), uni64(ctg[rid + 1]));
 		const int n0 = uni(S.n_regs);
 		int win_ok = 0;   // 0: not loaded yet, 1: in LDS, -1: too long for it
 		for (int pass = 0; pass < 2; ++pass) {
@@ -1000,46 +992,12 @@ __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc
 				if (uni(S.s_extra[o]) & 2) continue;   // asymmetric_flt_seed (memchain.c:138-149), tested for every seed after stage B
 				const long long s_rbeg = uni64(S.s_rbeg[o]); const int s_qbeg = uni(S.s_qbeg[o]), s_len = uni(S.s_len[o]);
 				++pf_seen;
-				// contained in a region of this strand search? (memchain.c:761-819)
-				int u;
+				// contained in a region of this strand search, and no later seed of the list disagrees? (memchain.c:761-819)
+				const auto seed_at = [&](int i, long long &t_rbeg, int &t_qbeg, int &t_len) { const int oo = S.lst[i]; t_rbeg = S.s_rbeg[oo]; t_qbeg = S.s_qbeg[oo]; t_len = S.s_len[oo]; };
 				const int nr = uni(S.n_regs);
-				u = nr;
-				for (int base = 0; base < nr && u == nr; base += 64) { // a lane per region made so far: the reference's loop stops at the first that passes
-					bool hit = false;
-					if (base + lane < nr) {
-						const bsx_region_t &rg = S.regs[base + lane];
-						if (!(s_rbeg < rg.rb || s_rbeg + s_len > rg.re || s_qbeg < rg.qb || s_qbeg + s_len > rg.qe) && !(s_len - rg.seedlen0 > .1 * l_query)) {
-							int qd = s_qbeg - rg.qb; long long rd = s_rbeg - rg.rb;
-							int max_gap = rg_gap(gap, P, (int)(qd < rd ? qd : rd));
-							int w = max_gap < rg.w ? max_gap : rg.w;
-							hit = qd - rd < w && rd - qd < w;
-							qd = rg.qe - (s_qbeg + s_len); rd = rg.re - (s_rbeg + s_len);
-							max_gap = rg_gap(gap, P, (int)(qd < rd ? qd : rd));
-							w = max_gap < rg.w ? max_gap : rg.w;
-							hit = hit || (qd - rd < w && rd - qd < w);
-						}
-					}
-					const unsigned long long hm = __ballot(hit);
-					if (hm) u = base + (int)__builtin_ctzll(hm);
-				}
-				if (u < nr) { // a later seed of the list (in sorted order) that may lead to a different alignment?  A lane per seed
-					bool any = false;
-					for (int base = k + 1; base < nl && !any; base += 64) {
-						const int i = base + lane;
-						bool alt = false;
-						if (i < nl && S.srt[i] != 0) {
-							const int oo = S.lst[(int)(uint32_t)S.srt[i]];
-							const long long t_rbeg = S.s_rbeg[oo]; const int t_qbeg = S.s_qbeg[oo], t_len = S.s_len[oo];
-							if (!(t_len < s_len * .95))
-								alt = (s_qbeg <= t_qbeg && s_qbeg + s_len - t_qbeg >= s_len >> 2 && t_qbeg - s_qbeg != t_rbeg - s_rbeg) ||
-								      (t_qbeg <= s_qbeg && t_qbeg + t_len - s_qbeg >= s_len >> 2 && s_qbeg - t_qbeg != s_rbeg - t_rbeg);
-						}
-						any = __ballot(alt) != 0;
-					}
-					if (!any) { ++pf_skip; WAVE_SYNC(); if (lane == 0) S.srt[k] = 0; WAVE_SYNC(); continue; }
-				}
+				const int u = rg_first_container(S.regs, nr, s_rbeg, s_qbeg, s_len, l_query, gap, P, lane);
+				if (u < nr && !rg_later_disagrees(S.srt, k, nl, s_rbeg, s_qbeg, s_len, lane, seed_at)) { ++pf_skip; WAVE_SYNC(); if (lane == 0) S.srt[k] = 0; WAVE_SYNC(); continue; }
 				++pf_inl;
-				// extension (memchain.c:613-730): left then right, each with up to MAX_BAND_TRY band widths
 				if (win_ok == 0) { // the chain's reference window (bns_fetch_seq, memchain.c:889) into LDS, once, when a seed of it is first extended
 					const int span = (int)(rmax1 - rmax0);
 					if (span > 0 && span <= RG_WIN) {
@@ -1048,69 +1006,12 @@ __device__ int rg_task(Store &S, DP &D, const DevIndex &ix, const DevScoring &sc
 						WAVE_SYNC();
 					} else win_ok = -1;
 				}
-				bsx_region_t R; memset(&R, 0, sizeof(R));
-				int aw0 = P.w, aw1 = P.w;
-				const int qe = s_qbeg + s_len;
-				R.score = R.truesc = -1; R.rid = rid;
-				for (int side = 0; side < 2; ++side) {
-					if (side == 0 && s_qbeg == 0) { R.score = R.truesc = s_len * P.a; R.qb = 0; R.rb = s_rbeg; continue; }
-					if (side == 1 && qe == l_query) { R.qe = l_query; R.re = s_rbeg + s_len; continue; }
-					const int sc0 = R.score, clip = side ? P.pen_clip3 : P.pen_clip5;
-					int aw = P.w;
-					bsx_ext_res_t res; res.score = -1; res.qle = res.tle = res.gtle = 0; res.gscore = -1; res.max_off = 0;
-					bsx_ext_job_t J;
-					J.parent = (uint8_t)parent; J.pad = 0; J.end_bonus = clip;
-					if (side == 0) { J.qoff = qoff + (uint32_t)s_qbeg - 1; J.qdir = -1; J.qlen = s_qbeg; J.tpos = s_rbeg - 1; J.tdir = -1; J.tlen = (int)(s_rbeg - rmax0); J.h0 = s_len * P.a; }
-					else { J.qoff = qoff + (uint32_t)qe; J.qdir = 1; J.qlen = l_query - qe; J.tpos = s_rbeg + s_len; J.tdir = 1; J.tlen = (int)(rmax1 - (s_rbeg + s_len)); J.h0 = sc0; }
-					for (int i = 0; i < 2; ++i) {
-						const int prev = R.score;
-						aw = P.w << i;
-						J.w = aw;
-						RG_STAGE(6);
-						// most extensions of a 150 bp read are shorter than a wavefront is wide: one register entry per lane then,
-						// and none of the per-chunk band tests and carries of the wider form
-						// (the stopping rule is counted in every instantiation of the tiers, which have no tallying form: the counter block's address is
-						// null unless $BSX_PHASES is on, and counting costs these kernels no register, profiles/ext_stop_measurements.md)
-						if (J.qlen < 64) res = ext_dp_reg<1, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
-						else if constexpr (PK) { // two columns per lane: one packed slot up to 127 query bases, two up to 255
-							if (J.qlen < 128) res = ext_dp_pk<1, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
-							else res = ext_dp_pk<2, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
-						}
-						else if (J.qlen < 128) res = ext_dp_reg<2, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);
-						else res = ext_dp_reg<RG_NC, XS_FAM_TIER>(ix, sc, reads, J, lane, win_ok > 0 ? D.win : nullptr, rmax0, D.q, qoff);   // qlen <= l_query - 1 <= 255: fits the 256 register entries
-						res.score = uni(res.score); res.qle = uni(res.qle); res.tle = uni(res.tle); res.gtle = uni(res.gtle);
-						res.gscore = uni(res.gscore); res.max_off = uni(res.max_off);
-						R.score = res.score;
-						RG_STAGE(7);
-						++pf_ext; pf_rows += (unsigned int)(res.tle > res.gtle ? res.tle : res.gtle);
-						if (P.prof && J.qlen >= 64) RG_PF_ADD(D, 15, (unsigned long long)(res.tle > res.gtle ? res.tle : res.gtle) << (J.qlen >= 128 ? 32 : 0));   // rows by query class: [64, 128) | 128 and more
-						if (R.score == prev || res.max_off < (aw >> 1) + (aw >> 2)) break;
-					}
-					const int local = res.gscore <= 0 || res.gscore <= R.score - clip;
-					if (side == 0) {
-						aw0 = aw;
-						if (local) { R.qb = s_qbeg - res.qle; R.rb = s_rbeg - res.tle; R.truesc = R.score; }
-						else { R.qb = 0; R.rb = s_rbeg - res.gtle; R.truesc = res.gscore; }
-					} else {
-						aw1 = aw;
-						if (local) { R.qe = qe + res.qle; R.re = s_rbeg + s_len + res.tle; R.truesc += R.score - sc0; }
-						else { R.qe = l_query; R.re = s_rbeg + s_len + res.gtle; R.truesc += res.gscore - sc0; }
-					}
-				}
-				R.bss = (uint8_t)RG_BSS(parent, l_pac, R.rb); R.parent = (uint8_t)parent;
-				if (RG_BSS(parent, l_pac, R.re) != R.bss) continue;   // crosses the strand boundary (memchain.c:846-849)
-				int cov = 0;
-				for (int i = lane; i < nl; i += 64) {
-					const int oo = S.lst[i];
-					const long long t_rbeg = S.s_rbeg[oo]; const int t_qbeg = S.s_qbeg[oo], t_len = S.s_len[oo];
-					if (t_qbeg >= R.qb && t_qbeg + t_len <= R.qe && t_rbeg >= R.rb && t_rbeg + t_len <= R.re) cov += t_len;
-				}
-				R.seedcov = uni(wave_sum_i32(cov));
-				R.w = aw0 > aw1 ? aw0 : aw1; R.seedlen0 = s_len; R.frac_rep = frac_rep;
-				if (uni(S.n_regs) == Store::RCAP) return 6;
-				WAVE_SYNC();
-				if (lane == 0) { S.regs[S.n_regs] = R; ++S.n_regs; }
-				WAVE_SYNC();
+				// (the stopping rule is counted in every instantiation of the tiers, which have no tallying form: the counter block's address is
+				// null unless $BSX_PHASES is on, and counting costs these kernels no register, profiles/ext_stop_measurements.md)
+				bsx_region_t R; int aw0, aw1;
+				rg_region_open(R, aw0, aw1, P.w, rid);
+				rg_ext_seed<PK, RG_QCAP, false, XS_FAM_TIER>(R, aw0, aw1, D, ix, sc, P, reads, qoff, l_query, parent, s_rbeg, s_qbeg, s_len, rmax0, rmax1, win_ok, lane, pf_t, pf_ext, pf_rows);
+				if (rg_push_region(R, aw0, aw1, s_len, frac_rep, parent, l_pac, nl, seed_at, S.regs, S.n_regs, Store::RCAP, lane)) return 6;
 			}
 		}
 	}

@@ -8,8 +8,7 @@
  */
 #include <math.h>
 #include "align_types.h"
-
-#define getbss(parent, l_pac, rb) ((((rb) > (l_pac)) == (parent)) ? 1 : 0)   /* mem_getbss, memchain.c:265 */
+#include "c2r_rule.h"
 
 /* merge_seed_to_chain, memchain.c:227-256: 1 if the seed was absorbed by chain c */
 static int chain_absorb(const bsx_opt_t *opt, int64_t l_pac, chain_t *c, const seed_t *s, int seed_rid)
@@ -86,7 +85,7 @@ int bsx_chain_build(const bsx_opt_t *opt, const bsx_refmeta_t *ref, int l_seq, i
 			s.score = s.len = slen;
 			rid = bsx_intv2rid(ref, s.rbeg, s.rbeg + s.len);
 			if (rid < 0) continue;   /* spans two contigs or the strand boundary */
-			if ((opt->bsstrand & 1) && getbss(parent, l_pac, s.rbeg) != opt->bsstrand >> 1) continue;
+			if ((opt->bsstrand & 1) && c2r_bss(parent, l_pac, s.rbeg) != opt->bsstrand >> 1) continue;
 			if (bsx_bt_size(tree)) {
 				int32_t lower = bsx_bt_lower(tree, s.rbeg);
 				if (lower < 0 || !chain_absorb(opt, l_pac, &pool.a[lower], &s, rid)) to_add = 1;
@@ -219,15 +218,11 @@ void bsx_chain_ref_span(const bsx_opt_t *opt, int l_query, int64_t l_pac, const 
 	rmax[0] = l_pac << 1; rmax[1] = 0;
 	for (i = 0; i < c->seeds.n; ++i) {
 		const seed_t *s = &c->seeds.a[i];
-		int64_t b = s->rbeg - (s->qbeg + bsx_cal_max_gap(opt, s->qbeg));
-		int64_t e = s->rbeg + s->len + ((l_query - s->qbeg - s->len) + bsx_cal_max_gap(opt, l_query - s->qbeg - s->len));
+		int64_t b, e;
+		c2r_seed_span(s->rbeg, s->qbeg, s->len, l_query, bsx_cal_max_gap(opt, s->qbeg), bsx_cal_max_gap(opt, l_query - s->qbeg - s->len), &b, &e);
 		rmax[0] = rmax[0] < b ? rmax[0] : b;
 		rmax[1] = rmax[1] > e ? rmax[1] : e;
 	}
-	rmax[0] = rmax[0] > 0 ? rmax[0] : 0;
-	rmax[1] = rmax[1] < l_pac << 1 ? rmax[1] : l_pac << 1;
-	if (rmax[0] < l_pac && l_pac < rmax[1]) {
-		if (c->seeds.a[0].rbeg < l_pac) rmax[1] = l_pac;
-		else rmax[0] = l_pac;
-	}
+	/* (every seed of a chain is on one strand: the first one's says which.  The contig is the caller's bsx_fetch_span: none here) */
+	c2r_clamp_window(&rmax[0], &rmax[1], l_pac, c->seeds.a[0].rbeg, 0, l_pac << 1);
 }

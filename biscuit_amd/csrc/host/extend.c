@@ -10,8 +10,9 @@
 #include "align_types.h"
 #include "pipeline.h"
 
+#include "c2r_rule.h"
+
 #define MAX_BAND_TRY 2   /* memchain.c:611 */
-#define getbss(parent, l_pac, rb) ((((rb) > (l_pac)) == (parent)) ? 1 : 0)
 
 /* asymmetric_flt_seed, memchain.c:138-149: reference T under a read C, or reference A under a read G */
 static int seed_violates_conversion(const bsx_index_t *idx, const uint8_t *query, const seed_t *s)
@@ -35,39 +36,30 @@ static void c2r_open_list(c2r_t *t, const seed_v *seeds)
 	t->k = t->n_srt - 1;
 }
 
-static void c2r_left_job(const bsx_opt_t *opt, c2r_t *t, const seed_t *s)
+/* the job of side t->stage - 1 (0 left, 1 right) at band width opt->w << t->tryi */
+static void c2r_post_job(const bsx_opt_t *opt, c2r_t *t, const seed_t *s)
 {
 	bsx_ext_job_t *j = &t->job;
+	const c2r_job_t f = c2r_side_job(t->stage - 1, t->qoff, s->rbeg, s->qbeg, s->len, t->l_query, t->rmax[0], t->rmax[1], opt->a, t->sc0, opt->pen_clip5, opt->pen_clip3);
 	memset(j, 0, sizeof(*j));
-	j->qoff = t->qoff + (uint32_t)s->qbeg - 1; j->qdir = -1; j->qlen = s->qbeg;
-	j->tpos = s->rbeg - 1; j->tdir = -1; j->tlen = (int32_t)(s->rbeg - t->rmax[0]);
-	j->h0 = s->len * opt->a; j->w = opt->w << t->tryi; j->end_bonus = opt->pen_clip5; j->parent = (uint8_t)t->parent;
+	j->qoff = f.qoff; j->qdir = (int8_t)f.qdir; j->qlen = f.qlen;
+	j->tpos = f.tpos; j->tdir = (int8_t)f.tdir; j->tlen = f.tlen;
+	j->h0 = f.h0; j->w = opt->w << t->tryi; j->end_bonus = f.end_bonus; j->parent = (uint8_t)t->parent;
 	t->has_job = 1;
 }
 
-static void c2r_right_job(const bsx_opt_t *opt, c2r_t *t, const seed_t *s)
-{
-	bsx_ext_job_t *j = &t->job;
-	int qe = s->qbeg + s->len;
-	memset(j, 0, sizeof(*j));
-	j->qoff = t->qoff + (uint32_t)qe; j->qdir = 1; j->qlen = t->l_query - qe;
-	j->tpos = s->rbeg + s->len; j->tdir = 1; j->tlen = (int32_t)(t->rmax[1] - (s->rbeg + s->len));
-	j->h0 = t->sc0; j->w = opt->w << t->tryi; j->end_bonus = opt->pen_clip3; j->parent = (uint8_t)t->parent;
-	t->has_job = 1;
-}
-
-/* region complete: strand-boundary check, seed coverage, book-keeping (memchain.c:839-869) */
+/* region complete: strand-boundary check, seed coverage, book-keeping (memchain.c:842-868) */
 static void c2r_finish_region(const bsx_index_t *idx, c2r_t *t, const chain_t *c, const seed_v *seeds, const seed_t *s)
 {
 	reg_t *r = &t->cur;
 	int64_t l_pac = idx->ref.l_pac;
 	size_t i;
-	r->bss = (uint8_t)getbss(t->parent, l_pac, r->rb);
+	r->bss = (uint8_t)c2r_bss(t->parent, l_pac, r->rb);
 	r->parent = (uint8_t)t->parent;
-	if (getbss(t->parent, l_pac, r->re) == r->bss) {
+	if (c2r_bss(t->parent, l_pac, r->re) == r->bss) {
 		for (i = 0, r->seedcov = 0; i < seeds->n; ++i) {
 			const seed_t *q = &seeds->a[i];
-			if (q->qbeg >= r->qb && q->qbeg + q->len <= r->qe && q->rbeg >= r->rb && q->rbeg + q->len <= r->re) r->seedcov += q->len;
+			if (c2r_covers(r->qb, r->qe, r->rb, r->re, q->rbeg, q->qbeg, q->len)) r->seedcov += q->len;
 		}
 		r->w = t->aw[0] > t->aw[1] ? t->aw[0] : t->aw[1];
 		r->seedlen0 = s->len;
@@ -78,18 +70,20 @@ static void c2r_finish_region(const bsx_index_t *idx, c2r_t *t, const chain_t *c
 	t->stage = 0;
 }
 
-/* after the left side is settled: skip or post the right extension (memchain.c:689-693) */
-static void c2r_begin_right(const bsx_opt_t *opt, const bsx_index_t *idx, c2r_t *t, const chain_t *c, const seed_v *seeds, const seed_t *s)
+/* From side `side` on: a side that needs no extension is settled here, the first one that needs one posts its job (t->has_job); with
+ * both sides settled the region is finished. */
+static void c2r_begin_side(const bsx_opt_t *opt, const bsx_index_t *idx, c2r_t *t, const chain_t *c, const seed_v *seeds, const seed_t *s, int side)
 {
-	if (s->qbeg + s->len == t->l_query) {
-		t->cur.qe = t->l_query; t->cur.re = s->rbeg + s->len;
-		c2r_finish_region(idx, t, c, seeds, s);
+	reg_t *r = &t->cur;
+	for (; side < 2; ++side) {
+		if (c2r_side_trivial(side, s->rbeg, s->qbeg, s->len, t->l_query, opt->a, &r->qb, &r->rb, &r->qe, &r->re, &r->score, &r->truesc)) continue;
+		t->sc0 = r->score;
+		t->tryi = 0;
+		t->stage = side + 1;
+		c2r_post_job(opt, t, s);
 		return;
 	}
-	t->sc0 = t->cur.score;
-	t->tryi = 0;
-	t->stage = 2;
-	c2r_right_job(opt, t, s);
+	c2r_finish_region(idx, t, c, seeds, s);
 }
 
 /* Run the task until it posts a job (returns 1) or is finished (returns 0). */
@@ -122,18 +116,15 @@ int bsx_c2r_advance(const bsx_opt_t *opt, const bsx_index_t *idx, c2r_t *t)
 			/* is the seed inside a region this strand search already produced? (memchain.c:761-790) */
 			for (u = 0; u < t->regs.n; ++u) {
 				const reg_t *reg = &t->regs.a[u];
-				int64_t rd;
-				int qd, w, max_gap;
-				if (s->rbeg < reg->rb || s->rbeg + s->len > reg->re || s->qbeg < reg->qb || s->qbeg + s->len > reg->qe) continue;
-				if (s->len - reg->seedlen0 > .1 * t->l_query) continue;
-				qd = s->qbeg - reg->qb; rd = s->rbeg - reg->rb;
-				max_gap = bsx_cal_max_gap(opt, (int)(qd < rd ? qd : rd));
-				w = max_gap < reg->w ? max_gap : reg->w;
-				if (qd - rd < w && rd - qd < w) break;
-				qd = reg->qe - (s->qbeg + s->len); rd = reg->re - (s->rbeg + s->len);
-				max_gap = bsx_cal_max_gap(opt, (int)(qd < rd ? qd : rd));
-				w = max_gap < reg->w ? max_gap : reg->w;
-				if (qd - rd < w && rd - qd < w) break;
+				int end;
+				if (!c2r_in_box(s->rbeg, s->qbeg, s->len, t->l_query, reg->rb, reg->re, reg->qb, reg->qe, reg->seedlen0)) continue;
+				for (end = 0; end < 2; ++end) {
+					int64_t rd;
+					int qd;
+					c2r_end_dist(end, s->rbeg, s->qbeg, s->len, reg->rb, reg->re, reg->qb, reg->qe, &qd, &rd);
+					if (c2r_near_diagonal(qd, rd, bsx_cal_max_gap(opt, c2r_gap_len(qd, rd)), reg->w)) break;
+				}
+				if (end < 2) break;
 			}
 			if (u < t->regs.n) { /* contained: extend anyway only if an overlapping long seed disagrees (memchain.c:794-819) */
 				int i;
@@ -141,9 +132,7 @@ int bsx_c2r_advance(const bsx_opt_t *opt, const bsx_index_t *idx, c2r_t *t)
 					const seed_t *o;
 					if (t->srt[i] == 0) continue;
 					o = &seeds->a[(uint32_t)t->srt[i]];
-					if (o->len < s->len * .95) continue;
-					if (s->qbeg <= o->qbeg && s->qbeg + s->len - o->qbeg >= s->len >> 2 && o->qbeg - s->qbeg != o->rbeg - s->rbeg) break;
-					if (o->qbeg <= s->qbeg && o->qbeg + o->len - s->qbeg >= s->len >> 2 && s->qbeg - o->qbeg != s->rbeg - o->rbeg) break;
+					if (c2r_disagrees(s->rbeg, s->qbeg, s->len, o->rbeg, o->qbeg, o->len)) break;
 				}
 				if (i == t->n_srt) { t->srt[t->k] = 0; --t->k; continue; }
 			}
@@ -152,16 +141,8 @@ int bsx_c2r_advance(const bsx_opt_t *opt, const bsx_index_t *idx, c2r_t *t)
 			t->cur.w = t->aw[0] = t->aw[1] = opt->w;
 			t->cur.score = t->cur.truesc = -1;
 			t->cur.rid = t->rid;
-			if (s->qbeg == 0) { /* nothing to the left (memchain.c:623-626) */
-				t->cur.score = t->cur.truesc = s->len * opt->a; t->cur.qb = 0; t->cur.rb = s->rbeg;
-				c2r_begin_right(opt, idx, t, c, seeds, s);
-				if (t->has_job) return 1;
-				continue;
-			}
-			t->tryi = 0;
-			t->stage = 1;
-			c2r_left_job(opt, t, s);
-			return 1;
+			c2r_begin_side(opt, idx, t, c, seeds, s, 0);   /* (a seed that spans the read is a region without a job) */
+			if (t->has_job) return 1;
 		}
 		/* list exhausted: fall back to the contained seeds if the chain produced nothing (memchain.c:898-901) */
 		if (t->pass == 0 && (int)t->regs.n == t->n0 && c->seeds_extra.n > 0) {
@@ -180,33 +161,16 @@ void bsx_c2r_consume(const bsx_opt_t *opt, const bsx_index_t *idx, c2r_t *t, con
 	const seed_v *seeds = t->pass ? &c->seeds_extra : &c->seeds;
 	const seed_t *s = &seeds->a[(uint32_t)t->srt[t->k]];
 	reg_t *r = &t->cur;
-	int prev = r->score, aw = opt->w << t->tryi;
+	const int side = t->stage - 1, prev = r->score, aw = opt->w << t->tryi;
 	t->has_job = 0;
 	r->score = res->score;
-	if (t->stage == 1) {
-		t->aw[0] = aw;
-		if (!(r->score == prev || res->max_off < (aw >> 1) + (aw >> 2)) && t->tryi + 1 < MAX_BAND_TRY) {
-			++t->tryi; c2r_left_job(opt, t, s); return;
-		}
-		if (res->gscore <= 0 || res->gscore <= r->score - opt->pen_clip5) { /* local */
-			r->qb = s->qbeg - res->qle; r->rb = s->rbeg - res->tle; r->truesc = r->score;
-		} else { /* to the read end */
-			r->qb = 0; r->rb = s->rbeg - res->gtle; r->truesc = res->gscore;
-		}
-		c2r_begin_right(opt, idx, t, c, seeds, s);
-	} else {
-		int qe = s->qbeg + s->len;
-		t->aw[1] = aw;
-		if (!(r->score == prev || res->max_off < (aw >> 1) + (aw >> 2)) && t->tryi + 1 < MAX_BAND_TRY) {
-			++t->tryi; c2r_right_job(opt, t, s); return;
-		}
-		if (res->gscore <= 0 || res->gscore <= r->score - opt->pen_clip3) {
-			r->qe = qe + res->qle; r->re = s->rbeg + s->len + res->tle; r->truesc += r->score - t->sc0;
-		} else {
-			r->qe = t->l_query; r->re = s->rbeg + s->len + res->gtle; r->truesc += res->gscore - t->sc0;
-		}
-		c2r_finish_region(idx, t, c, seeds, s);
+	t->aw[side] = aw;
+	if (c2r_band_again(r->score, prev, res->max_off, aw) && t->tryi + 1 < MAX_BAND_TRY) {
+		++t->tryi; c2r_post_job(opt, t, s); return;
 	}
+	c2r_side_settle(side, r->score, res->qle, res->tle, res->gtle, res->gscore, t->job.end_bonus, t->sc0,
+	                s->rbeg, s->qbeg, s->len, t->l_query, &r->qb, &r->rb, &r->qe, &r->re, &r->truesc);
+	c2r_begin_side(opt, idx, t, c, seeds, s, side + 1);
 }
 
 void bsx_c2r_release(c2r_t *t)

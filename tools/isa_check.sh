@@ -8,7 +8,7 @@ mkdir -p build/asm
 pids=()
 for f in biscuit_amd/csrc/hip/*.hip; do
 	b=$(basename $f .hip)
-	if [ ! -s build/asm/$b.s ] || [ $f -nt build/asm/$b.s ] || [ -n "$(find biscuit_amd/csrc/hip -name '*.hpp' -newer build/asm/$b.s 2>/dev/null)" ] || [ -n "$(find biscuit_amd/csrc/hip -name '*.h' -newer build/asm/$b.s 2>/dev/null)" ]; then
+	if [ ! -s build/asm/$b.s ] || [ $f -nt build/asm/$b.s ] || [ -n "$(find biscuit_amd/csrc/hip -name '*.hpp' -newer build/asm/$b.s 2>/dev/null)" ] || [ -n "$(find biscuit_amd/csrc/hip biscuit_amd/csrc/host -name '*.h' -newer build/asm/$b.s 2>/dev/null)" ]; then
 		/opt/rocm/bin/hipcc -Wno-unused-command-line-argument --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Ibiscuit_amd/csrc/host -Ibiscuit_amd/csrc/hip "$@" \
 			-S --cuda-device-only $f -o build/asm/$b.s &
 		pids+=($!)
